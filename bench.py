@@ -2,6 +2,7 @@
 """bench.py — cell-updates/s of the fused RLDaisyWorld step on MI355X, with roofline and CPU baseline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target|c2|c3|c4|c5|c1] [--precision exact|fast]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (ref RLDaisyWorld.step, daisy_world_rl.py:475-497) over the whole
 batch of synthetic worlds: update_agents (if the workload has agents) + the fused stencil/reaction
@@ -12,15 +13,20 @@ max-over-ranks timing and a final gather of per-world statistics.  `--gpus N` wi
 environment launches the N ranks itself (children only: the parent never touches the GPU).
 
 Default workload: the north-star shape, 1024 worlds of 4096x4096 on ONE GPU (128 GiB of binary16 ping-pong
-state; if the allocation fails the world count is halved until it fits and the line says so).  The other
-BASELINE configs - c2 (1024 x 256^2 over the whole ramp), c3 (256 x 1024^2, a greedy agent), c4 (the 1000 x 256^2
+state; if the allocation fails the world count is halved until it fits and the line says so).  With --full the
+other BASELINE configs - c2 (1024 x 256^2 over the whole ramp), c3 (256 x 1024^2, a greedy agent), c4 (the 1000 x 256^2
 shard with 4 greedy agents and per-step biosphere flags; also at the README's 8x8 grid) and c5 (the 8 x 8192^2
 shard, 16 mixed-policy agents) - are measured in the same invocation, both modes, and reported under "workloads".  Arithmetic modes: the headline is `fast` - float32 arithmetic, the "stated fp32 tolerance" of the
 north star: from identical states every cell within one quantum (1e-3) and >= 99.98 % of the cell values
 identical per step (measured >= 99.994 % on developed states over the whole luminosity ramp,
 profiles/r02_fast_tolerance.json; asserted by tests/test_gpu_parity.py); `exact` - float32 plus a float64
 re-evaluation of every near-tie cell, bit-identical to the float64 reference and the default of the drop-in
-class - is measured in the same invocation and reported under "modes".
+class - is measured in the same invocation with --full and reported under "modes".
+
+A plain run (no --full) sets up, pre-heats, warms up, times the K steps of the headline workload and prints the line;
+"power" and "cpu_baseline" are null and "modes", "workloads" and "roofline.copy_ceiling" are absent.  --full adds every
+measurement named above (the --no-* options drop single ones).  --dump-outputs DIR writes what the timed steps
+computed (dump_outputs); runs with the same arguments start the timed steps from the same state.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
   roofline     per launch of the dominant kernel (the fused step-pair kernel: one launch = 2 steps):
@@ -32,14 +38,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with these extra
                committed under profiles/ (collected separately, as the guide prescribes), `measured_frac` =
                traffic / launch time / peak; `valu` = VALU instructions per cell-evaluation and SIMD busy
                fraction from the committed SQ counters; `bound` is what those counters say.  `copy_ceiling` =
-               what a plain device copy reaches on this card, measured live (the practical ceiling
-               beside the spec peak), `measured_over_copy_ceiling` = the kernel's measured HBM rate / that.
+               what a plain device copy reaches on this card, measured live with --full (the practical
+               ceiling beside the spec peak), `measured_over_copy_ceiling` = the kernel's measured HBM rate / that.
   power        {"board_w", "limit_w", "sclk_mhz", "samples"}: the board's power and engine clock read with rocm-smi beside an
-               UNTIMED extra pass of the same launches after the timed region (N = 1, data-parallel workloads; null when
-               rocm-smi cannot be read).  At the north-star shape the step-pair kernels hold the card at its package power
+               UNTIMED extra pass of the same launches after the timed region (--full, N = 1, data-parallel workloads; null
+               otherwise or when rocm-smi cannot be read).  At the north-star shape the step-pair kernels hold the card at its package power
                limit and the engine clock is what the power manager leaves (profiles/r04_power_trace.txt).
   cpu_baseline the oracle's C restatement (oracle/daisy_oracle.c, "port") timed on this host's cores
-               on a bounded sample of the same workload (rank 0, N=1 only).
+               on a bounded sample of the same workload (--full, rank 0, N=1 only).
 """
 from __future__ import annotations
 
@@ -69,7 +75,7 @@ WORKLOADS = {
     "c4_dim8": (1000, 8, 4, "BASELINE configs[3] per-GPU shard at the README's own grid: 1000 worlds, 8x8, 4 greedy agents, "
                             "LDS-resident episode kernel (dw_run_episode)"),
 }
-# what the default invocation measures beside the headline workload: (timed steps, warm-up steps, pre-heat seconds)
+# what --full measures beside the headline workload: (timed steps, warm-up steps, pre-heat seconds)
 # (c4_dim8 is a latency-bound launch of 1000 waves: half a second of pre-heat, or the timed region measures the clock ramp)
 EXTRA_WORKLOADS = {"c2": (512, 64, 0.5), "c3": (64, 8, 0.3), "c4": (64, 8, 0.3), "c4_dim8": (512, 64, 0.5), "c5": (32, 8, 0.3)}
 
@@ -83,7 +89,7 @@ def parse(argv=None):
     ap.add_argument("--worlds", type=int, default=0, help="override worlds per GPU")
     ap.add_argument("--precision", default="fast", choices=["exact", "fast", "f64"],
                     help="arithmetic mode of the headline number (default fast = float32 within the stated, tested "
-                         "tolerance; the other of exact/fast is measured too and reported under 'modes')")
+                         "tolerance; with --full the other of exact/fast is measured too and reported under 'modes')")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--preheat-s", type=float, default=2.0,
                     help="seconds of untimed stepping before the warm-up steps, so that a short timed region does "
@@ -97,6 +103,11 @@ def parse(argv=None):
     ap.add_argument("--no-modes", action="store_true", help="skip the extra run in the other arithmetic mode")
     ap.add_argument("--no-power", action="store_true", help="skip the untimed extra pass that reads board power / clock")
     ap.add_argument("--no-workloads", action="store_true", help="skip the extra measurements of c2 ... c5")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the other arithmetic mode, the other BASELINE "
+                         "workloads, the device-copy ceiling, board power and the CPU baseline (each --no-* drops one)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--selftest-spawn", action="store_true",
                     help="CPU rehearsal of the N > 1 plumbing (rank launch, rendezvous, barrier, max-over-ranks, "
                          "gather, rank-0 relay) without touching a GPU: prints the JSON skeleton")
@@ -196,6 +207,51 @@ def json_round(path):
         return 0
 
 
+DUMP_WORLDS, DUMP_ROWS = 16, 32          # the fixed plane sample of --dump-outputs: <= 16 x 32 rows of 8192 cells per plane
+
+
+def plane_sample(eng, seed=0):
+    """Whole rows of the current binary16 planes (per-mille covers, [B][H][W] on the device) at a fixed, seeded sample of
+    at most DUMP_WORLDS worlds x DUMP_ROWS rows, copied straight from the device: the whole state is up to 128 GiB.
+    Returns {"light_permille": (w, r, W) float32, "dark_permille": ...} (every value an integer in [0, 1000])."""
+    import ctypes as C
+    import numpy as np
+    from therldaisyworld_amd import _ffi
+    rs = np.random.RandomState(seed)
+    worlds = np.sort(rs.choice(eng.B, min(eng.B, DUMP_WORLDS), replace=False))
+    rows = np.sort(rs.choice(eng.H, min(eng.H, DUMP_ROWS), replace=False))
+    # hipMemcpy of the HIP runtime the library itself links (dlsym on its handle searches its dependencies)
+    memcpy = eng._lib.hipMemcpy
+    memcpy.restype, memcpy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    row_bytes = 2 * eng.W
+    eng.sync()
+    out = {}
+    for name, base in zip(("light_permille", "dark_permille"), eng.device_planes(_ffi.STATE_CURRENT)):
+        host = np.empty((len(worlds), len(rows), eng.W), dtype=np.float16)
+        for i, b in enumerate(worlds):
+            for j, r in enumerate(rows):
+                src = base + (int(b) * eng.H + int(r)) * row_bytes          # b < B, r < H: inside the B*H*W plane
+                rc = memcpy(host[i, j].ctypes.data, src, row_bytes, 2)    # 2 = hipMemcpyDeviceToHost
+                if rc != 0:
+                    raise RuntimeError(f"hipMemcpy of a plane row failed: {rc}")
+        out[name] = host.astype(np.float32)
+    return out
+
+
+def dump_outputs(outdir, outputs, stats):
+    """--dump-outputs DIR: what the timed path computed, as DIR/<name>.npy in float32 / float64 (17 MB at the default shapes, 34 MB at most):
+    light_permille, dark_permille (plane_sample of the final state), the per-world reductions of the last step
+    world_max_k, world_sum_light_k, world_sum_dark_k (every world of every rank), luminosity (the value the ramp reached)
+    and, with agents, agent_rows_cols and agent_state (rank 0's worlds)."""
+    import numpy as np
+    arrays = dict(outputs)
+    for k in ("max_k", "sum_light_k", "sum_dark_k"):
+        arrays["world_" + k] = stats[k].astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def selftest_spawn(args):
     """The N > 1 plumbing on CPU (gloo): what tests/test_bench_spawn.py runs."""
     import numpy as np
@@ -267,6 +323,15 @@ def main():
 
     min_L, max_L, dL = 0.75, 1.5, 0.75 / 512
 
+    def draw(eng):
+        """The initial state of a run: device Philox, `--seed`."""
+        try:
+            eng.init_random(args.seed)                      # un-quantised like the reference's initialize_grid
+        except amd.DaisyHipError as e:
+            if e.code != _ffi.DW_ENOMEM:
+                raise
+            eng.init_random(args.seed, quantised=True)       # no room for the float32 staging: rounded draw
+
     def make_engine(B, G, N, precision):
         """Engine for B worlds; the world count is halved while the device cannot hold the state."""
         while True:
@@ -277,12 +342,7 @@ def main():
             eng = None
             try:
                 eng = amd.Engine(p)
-                try:
-                    eng.init_random(args.seed)              # un-quantised like the reference's initialize_grid
-                except amd.DaisyHipError as e:
-                    if e.code != _ffi.DW_ENOMEM:
-                        raise
-                    eng.init_random(args.seed, quantised=True)   # no room for the float32 staging: rounded draw
+                draw(eng)
                 return eng, B
             except amd.DaisyHipError as e:
                 if eng is not None:
@@ -291,8 +351,9 @@ def main():
                     raise
                 B //= 2
 
-    def measure(workload, precision, steps, warmup, preheat_s, worlds=0, power=False):
-        """One timed run of `steps` steps of `workload` in the given arithmetic mode."""
+    def measure(workload, precision, steps, warmup, preheat_s, worlds=0, power=False, sample=False):
+        """One timed run of `steps` steps of `workload` in the given arithmetic mode; sample=True: also what the timed
+        steps computed (res["outputs"], for dump_outputs)."""
         B, G, N, desc = WORKLOADS[workload]
         if worlds:
             B = worlds
@@ -349,13 +410,22 @@ def main():
                 nsteps -= k
             return L
 
-        # pre-heat at constant luminosity (develops the daisies, does not advance the ramp), then warm-up
+        # pre-heat at constant luminosity (develops the daisies, does not advance the ramp), then warm-up.  The warm-up
+        # always starts from the draw + ONE chunk of pre-heat steps, however many chunks the clocks took: after a longer
+        # pre-heat the state is drawn again and that chunk repeated, so that runs with the same arguments time the same steps
         L = min_L
         t_pre = time.perf_counter()
         pre_steps = 0
         chunk = 64                                          # 31 fused launches + 2 single steps per call
         while time.perf_counter() - t_pre < preheat_s:
             L = run(chunk, L, 0.0)
+            eng.sync()
+            pre_steps += chunk
+        if pre_steps > chunk:
+            draw(eng)
+            rng = np.random.RandomState(args.seed + rank)
+            run.started = False
+            L = run(chunk, min_L, 0.0)
             eng.sync()
             pre_steps += chunk
         preheat = time.perf_counter() - t_pre
@@ -378,6 +448,12 @@ def main():
         stats = eng.reduce()
         info = eng.kernel_info()
         fixups = eng.last_fixup_count()
+        outputs = None
+        if sample:
+            outputs = dict(plane_sample(eng), luminosity=np.array([L], dtype=np.float64))
+            if N:
+                idx, st = eng.download_agents()
+                outputs.update(agent_rows_cols=idx.astype(np.float64), agent_state=st)
         pw = None
         if power and N == 0:
             # ~2 s more of the same launches at the luminosity reached, untimed (everything the line reports was read
@@ -390,7 +466,7 @@ def main():
                "rank_value": cells * steps / own_elapsed,
                "event_ms_per_step": ev_ms / steps, "fused_ms": fused_ms, "fused_launches": fused_n,
                "plane_elem_bytes": elem_bytes, "fixups": fixups, "kernel": info, "stats": stats,
-               "preheat_s": preheat, "preheat_steps": pre_steps}
+               "preheat_s": preheat, "preheat_steps": pre_steps, "outputs": outputs}
         eng.close()
         return res
 
@@ -468,8 +544,11 @@ def main():
                                                                      "steps_per_launch")}}
 
     m = measure(args.workload, args.precision, args.steps, args.warmup, args.preheat_s, args.worlds,
-                power=rank == 0 and n_gpus == 1 and not args.no_power)
+                power=args.full and rank == 0 and n_gpus == 1 and not args.no_power,
+                sample=bool(args.dump_outputs) and rank == 0)
     all_stats = ensemble.gather_per_world(m["stats"]) if dist is not None else m["stats"]   # end-of-run gather (RCCL)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["outputs"], all_stats)
     group = ensemble.describe_group()                       # backend, world size, RCCL version, ranks that answered
     per_rank = ensemble.gather_scalars(m["rank_value"])     # each rank's own cell-updates/s over ITS elapsed time
     B, G, N = m["B"], m["G"], m["N"]
@@ -503,20 +582,20 @@ def main():
     }
     if WORKLOADS[args.workload][0] != B and not args.worlds:
         out["config"]["note"] = f"{WORKLOADS[args.workload][0]} worlds did not fit this device: measured {B}"
-    if not args.no_modes and args.precision in ("exact", "fast"):
+    if args.full and not args.no_modes and args.precision in ("exact", "fast"):
         other = "fast" if args.precision == "exact" else "exact"
         out["modes"] = {other: brief(measure(args.workload, other, args.steps, args.warmup, min(args.preheat_s, 1.0), B))}
-    if not args.no_workloads and args.workload == "target":
+    if args.full and not args.no_workloads and args.workload == "target":
         # every BASELINE config in the same invocation, both arithmetic modes: c2 over the whole luminosity ramp
         # (512 steps after 64 of warm-up), the agent workloads c3 / c4 / c5 as short runs of their per-GPU shard
         out["workloads"] = {w: {p: brief(measure(w, p, k, wu, ph)) for p in ("exact", "fast")}
                             for w, (k, wu, ph) in EXTRA_WORKLOADS.items()}
-    if rank == 0:
+    if args.full and rank == 0:
         cc = copy_ceiling()
         out["roofline"]["copy_ceiling"] = cc
         if out["roofline"]["traffic"]:
             out["roofline"]["measured_over_copy_ceiling"] = out["roofline"]["measured_frac"] * HBM_PEAK_GBS / cc["GB/s"]
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(G)
         out["vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
     elif rank == 0:

@@ -1,6 +1,7 @@
 """bench.py's output contract on a GPU box (`-m gpu`): ONE JSON line with the keys the driver parses, the roofline
-object computed per SURVEY 8(d) (4 x sizeof(plane element) bytes per cell-update, never above the peak) and the CPU
-baseline beside it - on a small ensemble so that the test takes seconds."""
+object computed per SURVEY 8(d) (4 x sizeof(plane element) bytes per cell-update, never above the peak) and, with
+--full, the CPU baseline beside it; a plain run's lean line and its --dump-outputs - on small ensembles so that each
+test takes seconds."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def _bench(*args):
 
 
 def test_bench_line_follows_the_contract():
-    d = _bench("--workload", "target", "--worlds", "8", "--steps", "12", "--warmup", "4", "--preheat-s", "0.2")
+    d = _bench("--workload", "target", "--worlds", "8", "--steps", "12", "--warmup", "4", "--preheat-s", "0.2", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -86,3 +87,34 @@ def test_bench_through_a_one_rank_rccl_group():
     assert d["rccl"]["backend"] == "nccl" and d["rccl"]["world_size"] == 1 and d["rccl"]["ranks_reporting"] == [0]
     assert d["rccl"]["nccl_version"]                        # RCCL answered for itself
     assert len(d["per_rank_value"]) == 1 and d["per_rank_value"][0] >= d["value"] * 0.999
+
+
+@pytest.mark.parametrize("workload,worlds", [("target", "8"), ("c5", "1")])
+def test_plain_run_is_lean_and_dumps_the_same_outputs_whatever_the_preheat(tmp_path, workload, worlds):
+    """Without --full the line carries the headline alone; --dump-outputs writes float32 / float64 arrays (within 64 MB)
+    of what the timed steps computed.  A pre-heat of one chunk and one of many chunks (the state is drawn again after it)
+    hand the timed steps the same state: the outputs are identical (c5: the host-drawn random actions too)."""
+    import numpy as np
+    outs = []
+    for preheat in ("0.0001", "1.0"):                      # one chunk / many chunks, then a fresh draw + one chunk
+        d = _bench("--workload", workload, "--worlds", worlds, "--steps", "7", "--warmup", "2", "--preheat-s", preheat,
+                   "--dump-outputs", str(tmp_path / preheat))
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+        assert abs(d["value"] - d["config"]["worlds_per_gpu"] * d["config"]["grid"][0] ** 2 / (d["ms_per_step"] * 1e-3)) \
+            / d["value"] < 1e-6
+        assert d["cpu_baseline"] is None and d["power"] is None
+        assert "modes" not in d and "workloads" not in d and "copy_ceiling" not in d["roofline"]
+        files = sorted(os.listdir(tmp_path / preheat))
+        arrays = {f: np.load(tmp_path / preheat / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        outs.append(arrays)
+    names = {"light_permille.npy", "dark_permille.npy", "luminosity.npy", "world_max_k.npy", "world_sum_light_k.npy",
+             "world_sum_dark_k.npy"} | ({"agent_rows_cols.npy", "agent_state.npy"} if workload == "c5" else set())
+    assert set(outs[0]) == set(outs[1]) == names
+    B = int(worlds)
+    assert outs[0]["world_max_k.npy"].shape == (B,) and outs[0]["light_permille.npy"].shape[:2] == (B, 32)
+    assert 0 <= outs[0]["light_permille.npy"].min() and outs[0]["light_permille.npy"].max() <= 1000
+    assert 0.75 <= outs[0]["luminosity.npy"][0] <= 1.5
+    for f in names:
+        assert np.array_equal(outs[0][f], outs[1][f]), f

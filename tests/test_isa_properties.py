@@ -18,11 +18,12 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
 @pytest.fixture(scope="module")
-def asm():
+def asm(tmp_path_factory):
     import shutil
     if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
         pytest.skip("hipcc not available")
     import isa_report
+    isa_report.OUT = str(tmp_path_factory.mktemp("dw_isa"))   # a private build directory, not the tool's shared default
     return open(isa_report.build([])).read()
 
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Evidence of a round's FINAL tree, in one session on the GPU box (repo root):  bash tools/final_evidence.sh <tag> [fuzz seed]
 # Writes gpurun_out/final_<tag>/…; copy what is to be judged into profiles/ afterwards (names as in profiles/README.md).
-#   bench_default.json            the driver's command, python bench.py --gpus 1 --steps 20 --warmup 5
+#   bench_default.json            the default command with every extra, python bench.py --gpus 1 --steps 20 --warmup 5 --full
 #   bench_default_profiled.json   the same command under rocprofv3 --kernel-trace --stats (+ its kernel_stats csv)
 #   soak_exact.txt                tools/soak_exact.py over five shapes (ring, packed, overlapped strips, odd width)
 #   kbench_small_ensembles.txt    tools/kbench.py on ensembles of reference-sized worlds and on small jobs
@@ -14,10 +14,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/final_$TAG
 mkdir -p "$OUT"
 cd "$R"
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || exit 1
 echo "bench done"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d "$OUT/prof_default" -o s --output-format csv -- \
-    python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_default_profiled.json" 2> "$OUT/bench_default_profiled.err" ) || exit 1
+    python3 "$R/bench.py" --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_default_profiled.json" 2> "$OUT/bench_default_profiled.err" ) || exit 1
 cp "$(find "$OUT/prof_default" -name '*kernel_stats.csv' | head -n 1)" "$OUT/bench_default_kernel_stats.csv"
 echo "profiled bench done"
 : > "$OUT/soak_exact.txt"

@@ -5,7 +5,7 @@ set -e -o pipefail
 TAG=${1:-rXX}
 OUT=gpurun_out/table_$TAG
 mkdir -p $OUT
-COMMON="--no-cpu-baseline --no-workloads"
+COMMON="--full --no-cpu-baseline --no-workloads"
 python3 bench.py --workload target --steps 20 --warmup 5 $COMMON > $OUT/target.json 2> $OUT/target.err; echo "target done"
 python3 bench.py --workload c2 --steps 512 --warmup 64 $COMMON > $OUT/c2.json 2> $OUT/c2.err; echo "c2 done"
 for w in c3 c5; do
