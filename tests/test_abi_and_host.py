@@ -306,51 +306,144 @@ def test_fitness_bookkeeping_per_chunk_equals_the_reference_loop(chunk, p_done):
         assert acc["sum_reward"][m] == s
 
 
-def test_pair_allocation_is_all_or_nothing(tmp_path):
-    """when the second of two plane allocations fails, neither pointer may stay set - the next call
-    must report the failure again (or retry), never find one plane and launch on a null second one.  The helper
-    has no HIP types (csrc/dw_host_util.hpp), so it is exercised here with a mock allocator under g++."""
+def test_group_allocation_is_all_or_nothing(tmp_path):
+    """when one allocation of a group of buffers used together fails, no buffer of the group may stay set -
+    the next call must report the failure again (or retry), never find some of them and launch on a null other one.
+    The owner type and the group allocator have no HIP types (csrc/dw_host_util.hpp), so they are exercised here with a
+    mock allocator under g++: groups, geometric and exact-size growth, and that moves, reset and destructors give back
+    every allocation exactly once."""
     import shutil
     import subprocess
-    src = tmp_path / "pair.cpp"
-    src.write_text(r'''
+    src = tmp_path / "group.cpp"
+    src.write_text(r"""
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 #include "dw_host_util.hpp"
-static int n_alloc = 0, n_free = 0, fail_on = 0;
+static int n_alloc = 0, n_free = 0, fail_on = 0, live = 0;
+struct Mock {
+    static int alloc(void** p, size_t n) { if (++n_alloc == fail_on) { *p = (void*)0x1; return 7; } *p = std::malloc(n ? n : 1); ++live; return 0; }
+    static int release(void* p) { ++n_free; --live; std::free(p); return 0; }
+};
+using B = dw::Block<Mock>;
 int main() {
-    auto alloc = [](void** p, size_t n) { if (++n_alloc == fail_on) { *p = (void*)0x1; return 7; } *p = std::malloc(n); return *p ? 0 : 1; };
-    auto release = [](void* p) { ++n_free; std::free(p); return 0; };
-    void *a = nullptr, *b = nullptr;
-    fail_on = 2;                                            // the SECOND allocation fails
-    int rc = dw::alloc_pair_all_or_nothing(&a, &b, 64, alloc, release);
-    if (rc != 7 || a || b || n_free != 1) { std::printf("after failure: rc=%d a=%p b=%p frees=%d\n", rc, a, b, n_free); return 1; }
-    fail_on = 3;                                            // the retry fails at once: still nothing held
-    rc = dw::alloc_pair_all_or_nothing(&a, &b, 64, alloc, release);
-    if (rc != 7 || a || b) return 2;
+    {
+        dw::Buf<int, Mock> a, b;
+        fail_on = 2;                                        // the SECOND allocation fails
+        int rc = dw::alloc_group<Mock>({{a, 64}, {b, 64}});
+        if (rc != 7 || a.get() || b.get() || a.bytes() || b.bytes() || n_free != 1) { std::printf("after failure: rc=%d frees=%d\n", rc, n_free); return 1; }
+        fail_on = n_alloc + 1;                              // the retry fails at once: still nothing held
+        rc = dw::alloc_group<Mock>({{a, 64}, {b, 64}});
+        if (rc != 7 || a.get() || b.get()) return 2;
+        fail_on = 0;
+        rc = dw::alloc_group<Mock>({{a, 64}, {b, 64}});
+        if (rc != 0 || !a.get() || !b.get() || a.bytes() != 64 || b.bytes() != 64) return 3;
+        int *a0 = a.get(), *b0 = b.get();
+        const int before = n_alloc;
+        rc = dw::alloc_group<Mock>({{a, 64}, {b, 64}});    // complete: nothing happens
+        if (rc != 0 || a.get() != a0 || b.get() != b0 || n_alloc != before) return 4;
+        b.reset();                                          // a partly held group is released and rebuilt whole
+        const int frees = n_free;
+        rc = dw::alloc_group<Mock>({{a, 64}, {b, 64}});
+        if (rc != 0 || !a.get() || !b.get() || n_free != frees + 1 || n_alloc != before + 2) return 5;
+    }
+    if (live != 0) return 6;
+    for (int k = 1; k <= 5; ++k) {                          // a group of five: the failure on each position in turn
+        B g[5];
+        const int start = n_alloc, frees = n_free;
+        fail_on = start + k;
+        const int rc = dw::alloc_group<Mock>({{g[0], 8}, {g[1], 16}, {g[2], 24}, {g[3], 32}, {g[4], 40}});
+        for (auto& o : g) if (o.raw() || o.bytes()) return 10 + k;
+        if (rc != 7 || n_alloc != start + k || n_free != frees + k - 1 || live != 0) return 20 + k;
+    }
     fail_on = 0;
-    rc = dw::alloc_pair_all_or_nothing(&a, &b, 64, alloc, release);
-    if (rc != 0 || !a || !b) return 3;
-    void *a0 = a, *b0 = b;
-    const int before = n_alloc;
-    rc = dw::alloc_pair_all_or_nothing(&a, &b, 64, alloc, release);   // both present: nothing happens
-    if (rc != 0 || a != a0 || b != b0 || n_alloc != before) return 4;
-    void* lone = std::malloc(8);                            // a half-allocated pair left behind by older code
-    void* none = nullptr;
-    const int frees = n_free;
-    rc = dw::alloc_pair_all_or_nothing(&lone, &none, 64, alloc, release);
-    if (rc != 0 || !lone || !none || n_free != frees + 1) return 5;
+    {
+        B e;                                                // exact size: exactly what is asked for, never shrunk
+        if (e.reserve(100) || e.bytes() != 100) return 30;
+        if (e.reserve(60) || e.bytes() != 100) return 31;
+        if (e.reserve(130) || e.bytes() != 130) return 32;
+        B g;                                                // geometric: first_size, then twice the OLD size, at least need
+        if (g.reserve(10, 64) || g.bytes() != 64) return 33;
+        void* g0 = g.raw();
+        if (g.reserve(64, 64) || g.bytes() != 64 || g.raw() != g0) return 34;
+        if (g.reserve(65, 64) || g.bytes() != 128) return 35;
+        if (g.reserve(129, 64) || g.bytes() != 256) return 36;
+        if (g.reserve(1000, 64) || g.bytes() != 1000) return 37;
+        B big;
+        if (big.reserve(500, 64) || big.bytes() != 500) return 38;
+        fail_on = n_alloc + 1;                              // a failed growth leaves the block empty
+        if (g.reserve(5000, 64) != 7 || g.raw() || g.bytes()) return 39;
+        fail_on = 0;
+        if (live != 2) return 40;
+        B m(std::move(e));                                  // moves hand the allocation over, once
+        if (e.raw() || e.bytes() || m.bytes() != 130 || live != 2) return 41;
+        B n;
+        n = std::move(m);
+        if (m.raw() || n.bytes() != 130 || live != 2) return 42;
+        n = std::move(big);                                 // the target's own allocation is released
+        if (big.raw() || n.bytes() != 500 || live != 1) return 43;
+        const int frees = n_free;
+        n.reset();
+        n.reset();                                          // an empty block releases nothing
+        if (n.raw() || n.bytes() || n_free != frees + 1 || live != 0) return 44;
+        if (n.reserve(32) || live != 1) return 45;
+    }                                                       // destructors
+    if (live != 0) return 46;
     std::puts("ok");
     return 0;
 }
-''')
+""")
     gxx = shutil.which("g++")
     assert gxx
-    exe = tmp_path / "pair"
-    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "therldaisyworld_amd", "csrc"), str(src),
-                           "-o", str(exe)])
+    exe = tmp_path / "group"
+    subprocess.check_call([gxx, "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "therldaisyworld_amd", "csrc"),
+                           str(src), "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip() == "ok", (out.returncode, out.stdout)
+
+
+def test_drop_in_retries_a_handle_that_failed(monkeypatch):
+    """_ensure_engine records the parameters it pushed only once the handle took them: when Engine() raises, the error
+    surfaces, the closed old engine is not kept, and the next call constructs again; when set_params raises, the next
+    call pushes again instead of running on the old constants."""
+    from therldaisyworld_amd import daisy_world_rl as mod
+    made, raise_next = [], {"ctor": False, "set": False}
+
+    class StandIn:
+        def __init__(self, p):
+            if raise_next["ctor"]:
+                raise_next["ctor"] = False
+                raise mod._ffi.DaisyHipError(mod._ffi.DW_ENOMEM, "injected")
+            self.closed, self.pushed = False, [p]
+            made.append(self)
+
+        def set_params(self, p):
+            if raise_next["set"]:
+                raise_next["set"] = False
+                raise mod._ffi.DaisyHipError(mod._ffi.DW_ENOMEM, "injected")
+            self.pushed.append(p)
+
+        def close(self):
+            self.closed = True
+
+    monkeypatch.setattr(mod, "Engine", StandIn)
+    env = _bare_env(device=0, precision="exact", collision_mode=0, world_offset=0, neighborhood=np.ones((3, 3)),
+                    _engine=None, _shape=None, **{k: 0.5 for k in mod.RLDaisyWorld._PARAM_FLOATS})
+    env._params = lambda: (env.dim, env.g)
+    first = env._ensure_engine()
+    assert made == [first] and env._ensure_engine() is first
+    env.g = 0.25                                            # same shape: set_params fails once
+    raise_next["set"] = True
+    with pytest.raises(mod._ffi.DaisyHipError):
+        env._ensure_engine()
+    assert env._ensure_engine() is first and first.pushed[-1] == (16, 0.25)
+    env.dim = 24                                            # new shape: the constructor fails once
+    raise_next["ctor"] = True
+    with pytest.raises(mod._ffi.DaisyHipError):
+        env._ensure_engine()
+    assert first.closed and env._engine is None
+    second = env._ensure_engine()
+    assert second is not first and not second.closed and made == [first, second] and second.pushed == [(24, 0.25)]
 
 
 def test_division_free_permille_quotient_is_exact_below_2_pow_22(tmp_path):

@@ -62,10 +62,145 @@ print("ok")
 """
 
 
-def test_failed_plane_pair_allocation_is_reported_again_and_retryable():
-    env = dict(os.environ, DW_TEST_FAIL_PAIR_ALLOC="2")
-    p = subprocess.run([sys.executable, "-c", _ALLOC_SCRIPT, ROOT], capture_output=True, text=True, env=env, timeout=300)
+def _run_child(script, *args, **env):
+    env = dict(os.environ, **env)
+    p = subprocess.run([sys.executable, "-c", script, ROOT, *args], capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode == 0 and p.stdout.strip().endswith("ok"), (p.returncode, p.stdout[-500:], p.stderr[-2000:])
+
+
+def test_failed_plane_group_allocation_is_reported_again_and_retryable():
+    _run_child(_ALLOC_SCRIPT, DW_TEST_FAIL_GROUP_ALLOC="2")
+
+
+# ---------------------------------------------------------------------------------------------
+# A snapshot whose regions could not be allocated is not valid: restore refuses it instead of copying from null buffers,
+# and once memory is there again the same slot saves and restores bit for bit
+# ---------------------------------------------------------------------------------------------
+_SNAPSHOT_SCRIPT = r"""
+import os
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import therldaisyworld_amd as amd
+from therldaisyworld_amd import _ffi
+valid_before = sys.argv[2] == "valid"
+p = amd.default_params(3, 64, 64, 2)
+L, dL = 0.9, 0.001
+
+
+def start():
+    e = amd.Engine(p)
+    e.init_random(7, quantised=True)                    # straight into the binary16 planes: no group allocated
+    return e
+
+
+def expect(code, call):
+    try:
+        call()
+    except amd.DaisyHipError as err:
+        assert err.code == code, err
+    else:
+        raise SystemExit(f"expected error {code}")
+
+
+def state(e):
+    return (*e.download_planes(), *e.download_agents(), e.reduce())
+
+
+def same(a, b):
+    return all(np.array_equal(x, y) for x, y in zip(a, b))
+
+
+eng = start()
+if valid_before:
+    eng.snapshot_save(0)                                # not stepped yet: regions, no previous state
+    eng.snapshot_restore(0)
+    os.environ["DW_TEST_FAIL_GROUP_ALLOC"] = "1"        # the next group that is allocated: the previous state's
+eng.step_n(2, L, dL, 0.75, 1.5)
+expect(_ffi.DW_ENOMEM, lambda: eng.snapshot_save(0))
+expect(_ffi.DW_ESTATE, lambda: eng.snapshot_restore(0))
+eng.snapshot_save(0)                                    # the hook is spent
+want = state(eng)
+eng.step_n(3, L, dL, 0.75, 1.5)
+eng.snapshot_restore(0)
+ref = start()
+ref.step_n(2, L, dL, 0.75, 1.5)
+assert same(state(eng), want) and same(want, state(ref))
+eng.step_n(3, L, dL, 0.75, 1.5)                         # the retained previous state was restored as well
+ref.step_n(3, L, dL, 0.75, 1.5)
+assert same(state(eng), state(ref))
+print("ok")
+"""
+
+
+@pytest.mark.parametrize("slot_state", ["fresh", "valid"])
+def test_failed_snapshot_allocation_leaves_the_slot_invalid(slot_state):
+    _run_child(_SNAPSHOT_SCRIPT, slot_state, **({"DW_TEST_FAIL_GROUP_ALLOC": "1"} if slot_state == "fresh" else {}))
+
+
+_SET_PARAMS_SCRIPT = r"""
+import ctypes
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import therldaisyworld_amd as amd
+from therldaisyworld_amd import _ffi
+from oracle import c_oracle
+p = amd.default_params(3, 128, 128, 0)
+p.precision = _ffi.PRECISION["fast"]
+eng = amd.Engine(p)                                     # fast: no near-tie queues
+ref = amd.Engine(p)
+for e in (eng, ref):
+    e.init_random(11, quantised=True)
+x = amd.default_params(3, 128, 128, 0)
+x.precision = _ffi.PRECISION["exact"]
+try:
+    eng.set_params(x)                                   # the tiled exact kernel's queues cannot be allocated
+except amd.DaisyHipError as err:
+    assert err.code == _ffi.DW_ENOMEM, err
+else:
+    raise SystemExit("the injected allocation failure was not reported")
+got = _ffi.DwParams()
+assert eng._lib.dw_get_params(eng._h, ctypes.byref(got)) == 0 and got.precision == p.precision
+for e in (eng, ref):
+    e.step_n(3, 0.9, 0.001, 0.75, 1.5)
+a, b = eng.download_planes(), ref.download_planes()
+assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+eng.set_params(x)                                       # the hook is spent
+light, dark = eng.download_planes()
+L, dL = 0.95, 0.75 / 512
+Lo = c_oracle.step_n(light, dark, L, dL, 20)
+Lg = eng.step_n(20, L, dL, 0.75, 1.5)
+gl, gd = eng.download_planes()
+k = lambda v: np.rint(np.asarray(v) * 1000.0).astype(np.int64)
+assert Lo == Lg and np.array_equal(k(gl), k(light)) and np.array_equal(k(gd), k(dark))
+print("ok")
+"""
+
+
+def test_failed_switch_to_exact_precision_leaves_the_handle_as_it_was():
+    _run_child(_SET_PARAMS_SCRIPT, DW_TEST_FAIL_GROUP_ALLOC="1")
+
+
+def test_handles_give_back_all_their_device_memory():
+    """create -> init_random -> step_n -> both snapshot slots -> run_episode -> env_step -> destroy, ten times: free device
+    memory after the tenth round equals that after the first (within 2 MiB; the first round may leave caches behind)."""
+    import torch
+    import therldaisyworld_amd as amd
+    from therldaisyworld_amd import _ffi
+    free = []
+    for _ in range(10):
+        eng = amd.Engine(amd.default_params(4, 256, 256, 3))
+        eng.init_random(5)
+        eng.step_n(2, 0.9, 0.001, 0.75, 1.5)
+        eng.snapshot_save(0)
+        eng.snapshot_save(1)
+        eng.run_episode(np.full(4, 0.9), _ffi.POLICY_ARGMAX)
+        eng.env_step(0.9, np.zeros((4, 3), dtype=np.int64))
+        eng.close()
+        torch.cuda.synchronize()
+        free.append(torch.cuda.mem_get_info()[0])
+    assert abs(free[9] - free[0]) <= 2 << 20, free
 
 
 # ---------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -99,38 +100,57 @@ static Switches read_switches() {
     return w;
 }
 
+// The handle owns its buffers (dw_host_util.hpp): device memory, and page-locked host memory for the staging images.
+// DW_TEST_FAIL_GROUP_ALLOC=<n> (tests, under DW_TEST_HOOKS; process-wide countdown, read when a group is first allocated
+// while it is set): the last allocation of each of the next n groups (alloc_group) fails with out-of-memory.  Groups
+// that dw_create allocates are not counted.
+static thread_local int t_fail_in = 0;     // > 0: the t_fail_in-th device allocation from now fails (armed by alloc_group)
+struct DeviceMem {
+    static int alloc(void** p, size_t n) {
+        if (t_fail_in > 0 && --t_fail_in == 0) return hipErrorOutOfMemory;
+        return hipMalloc(p, n);
+    }
+    static int release(void* p) { return hipFree(p); }
+};
+struct PinnedMem {
+    static int alloc(void** p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+    static int release(void* p) { return hipHostFree(p); }
+};
+template <class T> using DevBuf = Buf<T, DeviceMem>;
+template <class T> using PinnedBuf = Buf<T, PinnedMem>;
+
 struct dw_handle {
     dw_params prm;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     size_t cells = 0;                 // B*H*W
-    plane_t* L16[2] = {nullptr, nullptr};   // canonical planes (binary16 per-mille integers), ping-pong
-    plane_t* D16[2] = {nullptr, nullptr};
+    DevBuf<plane_t> L16[2];           // canonical planes (binary16 per-mille integers), ping-pong
+    DevBuf<plane_t> D16[2];
     int cur = 0;
-    double* L64 = nullptr;            // un-quantised state, float64 natural units (lazily allocated, kept)
-    double* D64 = nullptr;
-    float* U32L = nullptr;            // un-quantised state, float32 per-mille (lazily allocated; freed again
-    float* U32D = nullptr;            //   after use when it is large, see release_unquantised)
+    DevBuf<double> L64;               // un-quantised state, float64 natural units (lazily allocated, kept)
+    DevBuf<double> D64;
+    DevBuf<float> U32L;               // un-quantised state, float32 per-mille (lazily allocated; freed again
+    DevBuf<float> U32D;               //   after use when it is large, see release_unquantised)
     UnqKind unq_kind = UNQ_F64;
     UnqOwner unq = OWN_NONE;
     bool have_state = false;
     bool stepped = false;             // prev/cur form a forward() pair
     double L_last = 0.0;              // luminosity of the last forward()
-    int* idx = nullptr;               // [B][N][2]
-    double* st = nullptr;             // [B][N]
-    int* action = nullptr;            // [B][N]
-    int* action_tmp = nullptr;        // staging for host-supplied (possibly sub-shaped) actions
+    DevBuf<int> idx;                  // [B][N][2]
+    DevBuf<double> st;                // [B][N]
+    DevBuf<int> action;               // [B][N]
+    DevBuf<int> action_tmp;           // staging for host-supplied (possibly sub-shaped) actions
     bool have_agents = false;
     // per-world reductions, double-buffered: each step kernel accumulates into stats2[1-sp] and
     // clears stats2[sp] for the step after it, so the step loop needs no memset launches.
     // Element [B] of each buffer carries the float64 fix-up counter (in sum_l).
     // Each buffer is one allocation: [(B+1) StatsDev][kNumQueues*16 uint queue counters].
-    StatsDev* stats2[2] = {nullptr, nullptr};
+    DevBuf<StatsDev> stats2[2];
     size_t stats_bytes = 0;           // bytes of one such buffer
     int sp = 0;                       // buffer holding the CURRENT state's reductions
-    uint4* fixq = nullptr;            // exact mode: global near-tie queues [kNumQueues][qcap][3]
+    DevBuf<uint4> fixq;               // exact mode: global near-tie queues [kNumQueues][qcap][3]
     unsigned int qcap = 0;
-    int* redo_tiles = nullptr;        // exact mode: tiles to recompute whole (queue overflow)
+    DevBuf<int> redo_tiles;           // exact mode: tiles to recompute whole (queue overflow)
     // streaming kernel (W >= 256)
     bool use_stream = false;
     Switches sw{};                    // experiment / test switches as they were when the handle was created
@@ -140,45 +160,42 @@ struct dw_handle {
     bool sym_albedo = false;          // a_dark - a_bare == -(a_light - a_bare) exactly: the exact wave-strip kernels use
                                       // the two-term coefficient chain (growth_t<.., SYM>)
     FusedGeom fgeom{};
-    int* done_at = nullptr;           // [B]
-    int* agents_done_at = nullptr;    // [B][N]
-    int* n_alive = nullptr;
-    double* scratch = nullptr;        // device staging for float64 downloads / uploads
-    size_t scratch_bytes = 0;
-    unsigned char* ep_buf = nullptr;  // device staging of dw_run_episode (schedules, tables, flags)
-    size_t ep_bytes = 0;
-    double* mlp_w = nullptr;              // parameter sets of the last dw_run_episode_mlp call that passed them
+    DevBuf<int> done_at;              // [B]
+    DevBuf<int> agents_done_at;       // [B][N]
+    DevBuf<int> n_alive;
+    DevBuf<double> scratch;           // device staging for float64 downloads / uploads
+    DevBuf<unsigned char> ep_buf;     // device staging of dw_run_episode (schedules, tables, flags)
+    DevBuf<double> mlp_w;             // parameter sets of the last dw_run_episode_mlp call that passed them
     int mlp_members = 0;
-    unsigned char* ep_pinned = nullptr;   // page-locked host image of ep_buf (LDS-resident episode kernels: ONE upload
-    size_t ep_pinned_bytes = 0;           // and ONE download per chunk instead of six pageable copies)
-    double* reward_d = nullptr;       // [B][N]
-    unsigned char* done_d = nullptr;  // [B][N]
+    PinnedBuf<unsigned char> ep_pinned;   // page-locked host image of ep_buf (LDS-resident episode kernels: ONE upload
+                                          // and ONE download per chunk instead of six pageable copies)
+    DevBuf<double> reward_d;          // [B][N]
+    DevBuf<unsigned char> done_d;     // [B][N]
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t evf0 = nullptr, evf1 = nullptr;   // around the fused launches of the last dw_step_n call
     int fused_launches = 0;           // ... and how many there were (dw_last_step_n_timing); 0 unless BOTH events
                                       // of that call were recorded (an error return in between leaves 0)
-    StatsDev* side_stats = nullptr;   // reductions of dw_forward_f64's side computation (not the handle's)
-    unsigned char* pinned = nullptr;  // page-locked host staging of dw_env_step (actions in, obs/reward/done out)
-    size_t pinned_bytes = 0;
+    DevBuf<StatsDev> side_stats;      // reductions of dw_forward_f64's side computation (not the handle's)
+    PinnedBuf<unsigned char> pinned;  // page-locked host staging of dw_env_step (actions in, obs/reward/done out)
     // dw_snapshot_save[_slot] / dw_snapshot_restore[_slot]: device copies of the current state (two slots: a harness
     // that runs chunk c + 1 while it still accounts for chunk c keeps the starts of both)
     struct Snapshot {
-        plane_t* L = nullptr;
-        plane_t* D = nullptr;
-        plane_t* PL = nullptr;        // the retained previous state (observations, caches) when there is one
-        plane_t* PD = nullptr;
+        DevBuf<plane_t> L, D;
+        DevBuf<plane_t> PL, PD;       // the retained previous state (observations, caches) when there is one
         bool stepped = false;
         double L_last = 0.0;
         UnqOwner unq = OWN_NONE;
-        int* idx = nullptr;
-        double* st = nullptr;
-        unsigned char* stats = nullptr;
+        DevBuf<int> idx;
+        DevBuf<double> st;
+        DevBuf<unsigned char> stats;
         bool valid = false, agents = false;
     } snap[DW_SNAPSHOT_SLOTS];
     // kernel selection
     int tcq = 0, rpt = 0;             // 0 => generic
     Geom geom{};
     size_t tile_lds = 0;
+    std::vector<std::pair<const void*, size_t>> lds_limit;   // set_lds_limit: kernel -> dynamic LDS limit set
+    bool created = false;             // dw_create has returned it (DW_TEST_FAIL_GROUP_ALLOC counts from then on)
 };
 
 static inline bool cur_quantised(const dw_handle* h) { return h->unq != OWN_CUR; }
@@ -195,48 +212,55 @@ struct SyncOnExit {
     void disarm() { armed = false; }
 };
 
+// A failed allocation: clear the sticky error it leaves (it must not poison later checks) and report it.
+static int alloc_failed(int rc, const char* what, size_t bytes) {
+    (void)hipGetLastError();
+    const hipError_t e = static_cast<hipError_t>(rc);
+    return fail(e == hipErrorOutOfMemory ? DW_ENOMEM : DW_EHIP, "allocating %s (%zu bytes) failed: %s", what, bytes,
+                hipGetErrorString(e));
+}
+template <class B>
+static int reserve(B& buf, const char* what, size_t need, size_t first_size = 0) {
+    const int rc = buf.reserve(need, first_size);
+    return rc ? alloc_failed(rc, what, need) : DW_OK;
+}
+
+// Buffers used together come and go together (dw_host_util.hpp): a failed allocation leaves NONE of them, so a retry on
+// the same handle reports DW_ENOMEM again instead of launching on a null buffer.
+static int alloc_group(dw_handle* h, const char* what, std::initializer_list<GroupItem<DeviceMem>> group) {
+    static int fail_left = -1;                                  // -1: the variable was not set yet
+    if (h->created && fail_left < 0)
+        if (const char* e = test_hook("DW_TEST_FAIL_GROUP_ALLOC")) fail_left = std::atoi(e);
+    const bool armed = h->created && fail_left > 0;
+    if (armed) t_fail_in = (int)group.size();
+    const int rc = dw::alloc_group(group);
+    if (armed && t_fail_in == 0) --fail_left;                  // the injected failure happened (not a complete group)
+    t_fail_in = 0;
+    size_t bytes = 0;
+    for (const auto& g : group) bytes += g.bytes;
+    return rc ? alloc_failed(rc, what, bytes) : DW_OK;
+}
+
 // the un-quantised float32 buffers are as large as all four canonical planes together: give them back once
 // nothing refers to them any more if they are big (the north-star shape: 128 GiB)
 static void release_unquantised(dw_handle* h) {
-    if (h->unq != OWN_NONE || !h->U32L) return;
+    if (h->unq != OWN_NONE || !h->U32L.get()) return;
     for (const auto& sn : h->snap)
         if (sn.valid && sn.unq == OWN_PREV) return;              // a snapshot's previous state lives there
     if (h->cells * 2 * sizeof(float) < ((size_t)1 << 30)) return;
     (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->U32L); (void)hipFree(h->U32D);
-    h->U32L = nullptr; h->U32D = nullptr;
-}
-
-// The two planes of an un-quantised state come and go together (dw_host_util.hpp): a failed second allocation
-// leaves NEITHER, so a retry on the same handle reports DW_ENOMEM again instead of launching on a null plane.
-// DW_TEST_FAIL_PAIR_ALLOC=<n> (tests, under DW_TEST_HOOKS; process-wide countdown): the second allocation of the next n
-// pairs fails with out-of-memory.
-static int alloc_plane_pair(void** a, void** b, size_t bytes) {
-    static int fail_left = [] { const char* e = test_hook("DW_TEST_FAIL_PAIR_ALLOC"); return e ? std::atoi(e) : 0; }();
-    int calls = 0;
-    hipError_t last = hipSuccess;
-    const int rc = alloc_pair_all_or_nothing(
-        a, b, bytes,
-        [&](void** p, size_t n) {
-            if (++calls == 2 && fail_left > 0) { --fail_left; last = hipErrorOutOfMemory; *p = nullptr; return 1; }
-            last = hipMalloc(p, n);
-            return last == hipSuccess ? 0 : 1;
-        },
-        [](void* p) { return hipFree(p) == hipSuccess ? 0 : 1; });
-    if (rc == 0) return DW_OK;
-    (void)hipGetLastError();                                     // the failed hipMalloc must not poison later checks
-    return fail(last == hipErrorOutOfMemory ? DW_ENOMEM : DW_EHIP, "allocating two planes of %zu bytes failed: %s",
-                bytes, hipGetErrorString(last));
+    h->U32L.reset();
+    h->U32D.reset();
 }
 
 static int ensure_u32(dw_handle* h) {
-    return alloc_plane_pair(reinterpret_cast<void**>(&h->U32L), reinterpret_cast<void**>(&h->U32D),
-                            sizeof(float) * h->cells);
+    const size_t n = sizeof(float) * h->cells;
+    return alloc_group(h, "two float32 planes", {{h->U32L, n}, {h->U32D, n}});
 }
 
 static int ensure_f64(dw_handle* h) {
-    return alloc_plane_pair(reinterpret_cast<void**>(&h->L64), reinterpret_cast<void**>(&h->D64),
-                            sizeof(double) * h->cells);
+    const size_t n = sizeof(double) * h->cells;
+    return alloc_group(h, "two float64 planes", {{h->L64, n}, {h->D64, n}});
 }
 
 static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
@@ -245,44 +269,26 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
 static bool episode_kernel_applies(const dw_handle* h);
 static int observe_into_scratch(dw_handle* h, double L_init, size_t extra_bytes, bool reward_tail = false);
 
-static int ensure_scratch(dw_handle* h, size_t bytes) {
-    if (h->scratch_bytes >= bytes) return DW_OK;
-    if (h->scratch) HIPCHK(hipFree(h->scratch));
-    h->scratch = nullptr;
-    h->scratch_bytes = 0;
-    HIPCHK(hipMalloc(&h->scratch, bytes));
-    h->scratch_bytes = bytes;
-    return DW_OK;
-}
+static int ensure_scratch(dw_handle* h, size_t bytes) { return reserve(h->scratch, "scratch", bytes); }
 
 // episode staging buffer (schedules, tables, per-step flags): grown geometrically from 4 MiB so that a
-// longer chunk after a short one does not pay a synchronous hipFree + hipMalloc inside a timed run
+// longer chunk after a short one does not pay a synchronous free + allocation inside a timed run
 static int ensure_ep_buf(dw_handle* h, size_t bytes) {
-    if (h->ep_bytes >= bytes) return DW_OK;
-    size_t want = h->ep_bytes ? h->ep_bytes * 2 : ((size_t)4 << 20);
-    if (want < bytes) want = bytes;
-    if (h->ep_buf) HIPCHK(hipFree(h->ep_buf));
-    h->ep_buf = nullptr;
-    h->ep_bytes = 0;
-    HIPCHK(hipMalloc(&h->ep_buf, want));
-    h->ep_bytes = want;
-    return DW_OK;
+    return reserve(h->ep_buf, "the episode staging buffer", bytes, (size_t)4 << 20);
 }
 
-// near-tie queues of the exact mode: room for 1/64 of all cells (the bound flags ~0.3-0.5 %), at
-// least 2048 entries per queue; 48 bytes per entry, i.e. 0.75 B per cell on top of the 16 B of state
-static int ensure_fixq(dw_handle* h) {
-    const dw_params& p = h->prm;
-    if (p.precision != DW_PRECISION_EXACT) return DW_OK;
-    if (h->use_stream) return DW_OK;        // the streaming kernel keeps its near-tie queues in LDS
-    if (h->fixq || p.width % 4 != 0 || p.width < 64) return DW_OK;
-    size_t per_q = (h->cells / 64 + kNumQueues - 1) / kNumQueues;
-    if (per_q < 2048) per_q = 2048;
-    per_q = (per_q + 255) / 256 * 256;
-    h->qcap = (unsigned int)per_q;
-    HIPCHK(hipMalloc(&h->fixq, sizeof(uint4) * 3 * per_q * kNumQueues));
-    const size_t max_tiles = (size_t)p.batch * ((p.height + 7) / 8) * ((p.width / 4 + 15) / 16);
-    HIPCHK(hipMalloc(&h->redo_tiles, sizeof(int) * max_tiles));
+// Dynamic LDS above the default limit: the attribute belongs to the device's copy of the kernel (a handle is bound to
+// one device), so the handle remembers the largest value it set per kernel and sets it again only to raise it.
+template <class Kernel>
+static int set_lds_limit(dw_handle* h, Kernel kern, size_t bytes) {
+    const void* k = reinterpret_cast<const void*>(kern);
+    size_t* set = nullptr;
+    for (auto& e : h->lds_limit)
+        if (e.first == k) set = &e.second;
+    if (set && *set >= bytes) return DW_OK;
+    HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (set) *set = bytes;
+    else h->lds_limit.emplace_back(k, bytes);
     return DW_OK;
 }
 
@@ -525,6 +531,27 @@ static void set_strip_rows(dw_handle* h, int sr) {
     f.chunk = (f.nwg + 7) / 8;
 }
 
+// Packed mode of the wave-strip kernels: narrow worlds whose width divides 256 sit side by side in one 256-column wave
+// row (256/W worlds per wave) - only for ensembles with enough wave-strips to occupy the GPU: a lone strip is a serial
+// march down 64 rows, ~50 us, where the tiled kernel answers in ~9 us; DW_PACK_MIN_STRIPS overrides for tests.
+// Any width below 256 that is a multiple of 4, provided at least 70 % of the 64 lanes get columns (W = 96: 2 worlds on
+// 48 lanes; W = 132: one world on 33 lanes - left to the tiled kernel).  Returns the worlds per wave row, 0 if unpacked.
+static int packed_worlds_per_row(const dw_handle* h, const dw_params& p) {
+    const int pack_min_strips = h->sw.pack_min_strips >= 0 ? h->sw.pack_min_strips : 512;
+    const int pk_lpw = p.width / 4, pk_wpr = pk_lpw ? 64 / pk_lpw : 0;
+    const bool pack_shape = p.width >= 8 && p.width < 256 && pk_wpr >= 1 && pk_wpr * pk_lpw * 10 >= 64 * 7 &&
+                            !h->sw.no_pack;
+    const long pack_strips = pack_shape ? (long)((p.batch + pk_wpr - 1) / pk_wpr) * ((p.height + 63) / 64) : 0;
+    return pack_shape && pack_strips >= pack_min_strips ? pk_wpr : 0;
+}
+
+// the wave-strip (streaming) kernels take the step: W >= 256 or a packed ensemble, unless DW_KERNEL=tiled (A/B experiments)
+static bool picks_stream(const dw_handle* h, const dw_params& p) {
+    if (p.precision == DW_PRECISION_F64 || p.width % 4 != 0) return false;
+    const bool force_tiled = std::strcmp(h->sw.kernel, "tiled") == 0;
+    return (p.width >= 256 || packed_worlds_per_row(h, p) > 0) && !force_tiled;
+}
+
 static void select_kernel(dw_handle* h) {
     const dw_params& p = h->prm;
     h->tcq = 0;
@@ -535,21 +562,9 @@ static void select_kernel(dw_handle* h) {
     if (p.precision == DW_PRECISION_F64) return;
     if (p.width % 4 != 0) return;
     const int Wq = p.width / 4;
-    const char* force = h->sw.kernel[0] ? h->sw.kernel : nullptr;   // "tiled" | "stream": A/B experiments
-    // packed mode of the wave-strip kernels: narrow worlds whose width divides 256 sit side by side in one
-    // 256-column wave row (256/W worlds per wave)
-    // (only for ensembles with enough wave-strips to occupy the GPU: a lone strip is a serial march down
-    // 64 rows, ~50 us, where the tiled kernel answers in ~9 us; DW_PACK_MIN_STRIPS overrides for tests)
-    int pack_min_strips = 512;
-    if (h->sw.pack_min_strips >= 0) pack_min_strips = h->sw.pack_min_strips;
-    // any width below 256 that is a multiple of 4, provided at least 70 % of the 64 lanes get columns
-    // (W = 96: 2 worlds on 48 lanes; W = 132: one world on 33 lanes - left to the tiled kernel)
-    const int pk_lpw = p.width / 4, pk_wpr = pk_lpw ? 64 / pk_lpw : 0;
-    const bool pack_shape = p.width >= 8 && p.width < 256 && pk_wpr >= 1 && pk_wpr * pk_lpw * 10 >= 64 * 7 &&
-                            !h->sw.no_pack;
-    const long pack_strips = pack_shape ? (long)((p.batch + pk_wpr - 1) / pk_wpr) * ((p.height + 63) / 64) : 0;
-    const bool packable = pack_shape && pack_strips >= pack_min_strips;
-    if ((p.width >= 256 || packable) && !(force && std::strcmp(force, "tiled") == 0)) {
+    const int pk_wpr = packed_worlds_per_row(h, p);
+    const bool packable = pk_wpr > 0;
+    if (picks_stream(h, p)) {
         h->use_stream = true;
         StripGeom& g = h->sgeom;
         g.B = p.batch; g.H = p.height; g.W = p.width;
@@ -606,16 +621,30 @@ static void select_kernel(dw_handle* h) {
     h->tile_lds = (size_t)2 * (TR + 2) * (h->tcq + 2) * 4 * sizeof(float);
 }
 
+// near-tie queues of the tiled exact kernel (the streaming kernel keeps them in LDS) for the parameters `p`: room for 1/64
+// of all cells (the bound flags ~0.3-0.5 %), at least 2048 entries per queue; 48 bytes per entry, i.e. 0.75 B per cell
+// on top of the 16 B of state
+static int ensure_fixq(dw_handle* h, const dw_params& p) {
+    if (p.precision != DW_PRECISION_EXACT || p.width % 4 != 0 || p.width < 64 || picks_stream(h, p)) return DW_OK;
+    size_t per_q = (h->cells / 64 + kNumQueues - 1) / kNumQueues;
+    if (per_q < 2048) per_q = 2048;
+    per_q = (per_q + 255) / 256 * 256;
+    const size_t max_tiles = (size_t)p.batch * ((p.height + 7) / 8) * ((p.width / 4 + 15) / 16);
+    if (int rc = alloc_group(h, "the near-tie queues", {{h->fixq, sizeof(uint4) * 3 * per_q * kNumQueues},
+                                                         {h->redo_tiles, sizeof(int) * max_tiles}}))
+        return rc;
+    h->qcap = (unsigned int)per_q;
+    return DW_OK;
+}
+
 template <int TCQ, int RPT, bool EXACT>
 static int launch_tiled(dw_handle* h, const plane_t* iL, const plane_t* iD, plane_t* oL, plane_t* oD,
                         const PhysF32& P, const PhysF64& P64, StatsDev* stats,
                         unsigned long long* fixups, unsigned long long* zero_me, int zero_n, const FixQ& fq) {
     auto kern = step_tiled<TCQ, RPT, EXACT>;
-    // only the 32-row tuning tiles exceed the 64 KB a launch may ask for without opting in; the attribute belongs
-    // to the CURRENT device's copy of the kernel, so it is set per call (no process-wide flag: one handle per GPU)
+    // only the 32-row tuning tiles exceed the 64 KB a launch may ask for without opting in
     if constexpr (TileCfg<TCQ, RPT>::LDS_BYTES > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(TileCfg<TCQ, RPT>::LDS_BYTES)));
+        if (int rc = set_lds_limit(h, kern, TileCfg<TCQ, RPT>::LDS_BYTES)) return rc;
     const unsigned grid = (unsigned)h->geom.chunk * 8u;
     constexpr size_t lds_bytes = TileCfg<TCQ, RPT>::LDS_BYTES;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, h->stream, iL, iD, oL, oD, h->geom, P, stats,
@@ -640,15 +669,15 @@ static int launch_forward(dw_handle* h, double L) {
     const int in = h->cur, out = 1 - h->cur;
     const PhysF32 P = derive_f32(p, L);
     const PhysF64 P64 = make_f64(p, L);
-    StatsDev* stats = h->stats2[1 - h->sp];                       // invariant: all zero
+    StatsDev* stats = h->stats2[1 - h->sp].get();                       // invariant: all zero
     unsigned long long* fixups = &stats[p.batch].sum_l;
-    unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp]);
+    unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get());
     const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
     FixQ fq;
-    fq.entries = h->fixq;
+    fq.entries = h->fixq.get();
     fq.counts = reinterpret_cast<unsigned int*>(stats + p.batch + 1);
     fq.qcap = h->qcap;
-    fq.redo_tiles = h->redo_tiles;
+    fq.redo_tiles = h->redo_tiles.get();
     const int gcpt = generic_cells_per_thread(p.batch, (long long)p.height * p.width);
     const dim3 ggrid((unsigned)(((long long)p.height * p.width + 256LL * gcpt - 1) / (256LL * gcpt)), (unsigned)p.batch);
     int prec = p.precision;
@@ -657,8 +686,8 @@ static int launch_forward(dw_handle* h, double L) {
         if (std::strcmp(e, "copy") == 0) {
             const size_t n4 = h->cells * sizeof(plane_t) / 16;
             hipLaunchKernelGGL(copy_planes, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, h->stream,
-                               reinterpret_cast<const float4*>(h->L16[in]), reinterpret_cast<const float4*>(h->D16[in]),
-                               reinterpret_cast<float4*>(h->L16[out]), reinterpret_cast<float4*>(h->D16[out]), n4);
+                               reinterpret_cast<const float4*>(h->L16[in].get()), reinterpret_cast<const float4*>(h->D16[in].get()),
+                               reinterpret_cast<float4*>(h->L16[out].get()), reinterpret_cast<float4*>(h->D16[out].get()), n4);
             HIPCHK(hipGetLastError());
             h->cur = out; h->sp = 1 - h->sp; h->stepped = true; h->L_last = L;
             return DW_OK;
@@ -671,7 +700,7 @@ static int launch_forward(dw_handle* h, double L) {
         // first step from an un-quantised state: one thread per cell straight from the upload format, in
         // float64 (exact and f64 modes: bit-identical to the reference's first step) or float32 (fast mode)
 #define DW_GEN(T, PR, IL, ID)                                                                                     \
-    hipLaunchKernelGGL((step_generic<T, PR>), ggrid, dim3(256), 0, h->stream, IL, ID, h->L16[out], h->D16[out],   \
+    hipLaunchKernelGGL((step_generic<T, PR>), ggrid, dim3(256), 0, h->stream, IL, ID, h->L16[out].get(), h->D16[out].get(),   \
                        p.height, p.width, P, P64, stats, fixups, zero_me, zero_n, gcpt)
         // exact mode: float32 with the tie bound for non-integer inputs, float64 only for the flagged cells
         // (DW_FIRST_STEP_F64=1: every cell in float64, as in round 2 - experiments)
@@ -679,7 +708,7 @@ static int launch_forward(dw_handle* h, double L) {
         const bool f32arith = prec == DW_PRECISION_FAST;
         const bool bounded = prec == DW_PRECISION_EXACT && !first_f64;
 #define DW_GEN3(T, IL, ID, FB)                                                                                    \
-    hipLaunchKernelGGL((step_generic<T, 3>), ggrid, dim3(256), 0, h->stream, IL, ID, h->L16[out], h->D16[out],    \
+    hipLaunchKernelGGL((step_generic<T, 3>), ggrid, dim3(256), 0, h->stream, IL, ID, h->L16[out].get(), h->D16[out].get(),    \
                        p.height, p.width, P, P64, stats, fixups, zero_me, zero_n, gcpt, FB)
         // every shape the steady-state wave-strip kernels take (select_kernel: W >= 256 a multiple of 4, or the packed
         // mode of narrower worlds; and any multiple of 256): the wave-strip form of the same arithmetic (dw_step_first.hpp;
@@ -702,35 +731,35 @@ static int launch_forward(dw_handle* h, double L) {
             const dim3 fgrid((unsigned)((fg.nstrips + 3) / 4));
             const FirstStepBound fb = bounded ? derive_first_bound(p, L, P, h->unq_kind == UNQ_F64, h->sw.first_slack) : FirstStepBound{};
 #define DW_FIRST(T, PR, HL, IL, ID)                                                                               \
-    hipLaunchKernelGGL((step_first_stream<T, PR, HL>), fgrid, dim3(256), 0, h->stream, IL, ID, h->L16[out],       \
-                       h->D16[out], fg, P, P64, stats, fixups, zero_me, zero_n, fb)
+    hipLaunchKernelGGL((step_first_stream<T, PR, HL>), fgrid, dim3(256), 0, h->stream, IL, ID, h->L16[out].get(),       \
+                       h->D16[out].get(), fg, P, P64, stats, fixups, zero_me, zero_n, fb)
 #define DW_FIRST_HL(T, PR, IL, ID)                                                                                \
     do { if (fhalo == 0) DW_FIRST(T, PR, 0, IL, ID); else if (fhalo == 1) DW_FIRST(T, PR, 1, IL, ID);           \
          else if (fhalo == 2) DW_FIRST(T, PR, 2, IL, ID); else DW_FIRST(T, PR, 3, IL, ID); } while (0)
             if (h->unq_kind == UNQ_F64) {
-                if (f32arith) DW_FIRST_HL(double, 1, h->L64, h->D64);
-                else DW_FIRST_HL(double, 3, h->L64, h->D64);
+                if (f32arith) DW_FIRST_HL(double, 1, h->L64.get(), h->D64.get());
+                else DW_FIRST_HL(double, 3, h->L64.get(), h->D64.get());
             } else {
-                if (f32arith) DW_FIRST_HL(float, 1, h->U32L, h->U32D);
-                else DW_FIRST_HL(float, 3, h->U32L, h->U32D);
+                if (f32arith) DW_FIRST_HL(float, 1, h->U32L.get(), h->U32D.get());
+                else DW_FIRST_HL(float, 3, h->U32L.get(), h->U32D.get());
             }
 #undef DW_FIRST_HL
 #undef DW_FIRST
         } else if (h->unq_kind == UNQ_F64) {
-            if (f32arith) DW_GEN(double, 1, h->L64, h->D64);
-            else if (bounded) DW_GEN3(double, h->L64, h->D64, derive_first_bound(p, L, P, true, h->sw.first_slack));
-            else DW_GEN(double, 2, h->L64, h->D64);
+            if (f32arith) DW_GEN(double, 1, h->L64.get(), h->D64.get());
+            else if (bounded) DW_GEN3(double, h->L64.get(), h->D64.get(), derive_first_bound(p, L, P, true, h->sw.first_slack));
+            else DW_GEN(double, 2, h->L64.get(), h->D64.get());
         } else {
-            if (f32arith) DW_GEN(float, 1, h->U32L, h->U32D);
-            else if (bounded) DW_GEN3(float, h->U32L, h->U32D, derive_first_bound(p, L, P, false, h->sw.first_slack));
-            else DW_GEN(float, 2, h->U32L, h->U32D);
+            if (f32arith) DW_GEN(float, 1, h->U32L.get(), h->U32D.get());
+            else if (bounded) DW_GEN3(float, h->U32L.get(), h->U32D.get(), derive_first_bound(p, L, P, false, h->sw.first_slack));
+            else DW_GEN(float, 2, h->U32L.get(), h->U32D.get());
         }
 #undef DW_GEN3
         HIPCHK(hipGetLastError());
     } else if (prec == DW_PRECISION_F64 || (h->tcq == 0 && !h->use_stream)) {
-        if (prec == DW_PRECISION_F64) DW_GEN(plane_t, 2, h->L16[in], h->D16[in]);
-        else if (prec == DW_PRECISION_EXACT) DW_GEN(plane_t, 0, h->L16[in], h->D16[in]);
-        else DW_GEN(plane_t, 1, h->L16[in], h->D16[in]);
+        if (prec == DW_PRECISION_F64) DW_GEN(plane_t, 2, h->L16[in].get(), h->D16[in].get());
+        else if (prec == DW_PRECISION_EXACT) DW_GEN(plane_t, 0, h->L16[in].get(), h->D16[in].get());
+        else DW_GEN(plane_t, 1, h->L16[in].get(), h->D16[in].get());
 #undef DW_GEN
         HIPCHK(hipGetLastError());
     } else if (h->use_stream) {
@@ -739,10 +768,10 @@ static int launch_forward(dw_handle* h, double L) {
         const dim3 grid((unsigned)g.chunk * 8u);
         const int halo = p.width < 256 ? 3 : (p.width == 256 ? 0 : (p.width % 256 == 0 ? 1 : 2));
 #define DW_STREAM(K, HL)                                                                                \
-    hipLaunchKernelGGL((K<HL>), grid, dim3(256), 0, h->stream, h->L16[in], h->D16[in], h->L16[out],     \
-                       h->D16[out], g, P, P64, stats, fixups, zero_me, zero_n)
+    hipLaunchKernelGGL((K<HL>), grid, dim3(256), 0, h->stream, h->L16[in].get(), h->D16[in].get(), h->L16[out].get(),     \
+                       h->D16[out].get(), g, P, P64, stats, fixups, zero_me, zero_n)
         if (ex) {
-            const StreamExactArgs A{h->L16[in], h->D16[in], h->L16[out], h->D16[out], g, P, stats, fixups, zero_me,
+            const StreamExactArgs A{h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P, stats, fixups, zero_me,
                                     zero_n, P64};
 #define DW_SX(HL)                                                                                     \
     do {                                                                                              \
@@ -764,9 +793,9 @@ static int launch_forward(dw_handle* h, double L) {
         const bool ex = prec == DW_PRECISION_EXACT;
         int rc;
 #define DW_TILED(T, R)                                                                              \
-    rc = ex ? launch_tiled<T, R, true>(h, h->L16[in], h->D16[in], h->L16[out], h->D16[out], P, P64,  \
+    rc = ex ? launch_tiled<T, R, true>(h, h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), P, P64,  \
                                        stats, fixups, zero_me, zero_n, fq)                           \
-            : launch_tiled<T, R, false>(h, h->L16[in], h->D16[in], h->L16[out], h->D16[out], P, P64, \
+            : launch_tiled<T, R, false>(h, h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), P, P64, \
                                         stats, fixups, zero_me, zero_n, fq)
         if (h->tcq == 64 && h->rpt == 8) { DW_TILED(64, 8); }
         else if (h->tcq == 64 && h->rpt == 4) { DW_TILED(64, 4); }
@@ -795,13 +824,13 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
     PhysF32 P1, P2;
     if (p.precision == DW_PRECISION_EXACT) derive_f32_pair(p, L1, L2, &P1, &P2);
     else { P1 = derive_f32(p, L1); P2 = derive_f32(p, L2); }
-    unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp]);
+    unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get());
     const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
     const FusedGeom& g = h->fgeom;
     const dim3 grid((unsigned)g.chunk * 8u);
     const bool rot = p.width == 256, pack = p.width < 256, ring = h->fused_ring;
     if (p.precision == DW_PRECISION_EXACT) {
-        const FusedExactArgs A{h->L16[in], h->D16[in], h->L16[out], h->D16[out], g, P1, lum_part(P2), zero_me, zero_n,
+        const FusedExactArgs A{h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P1, lum_part(P2), zero_me, zero_n,
                                pstats, thr_hi, make_f64(p, L1), L1, L2};
 #define DW_FX(R, P, S)                                                                                            \
     do {                                                                                                          \
@@ -818,8 +847,8 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
 #undef DW_FX
     } else {
 #define DW_FF(R, P, S)                                                                                           \
-    hipLaunchKernelGGL((step_stream_fused2<R, P, S>), grid, dim3(256), 0, h->stream, h->L16[in], h->D16[in],      \
-                       h->L16[out], h->D16[out], g, P1, P2, zero_me, zero_n, pstats, thr_hi)
+    hipLaunchKernelGGL((step_stream_fused2<R, P, S>), grid, dim3(256), 0, h->stream, h->L16[in].get(), h->D16[in].get(),      \
+                       h->L16[out].get(), h->D16[out].get(), g, P1, P2, zero_me, zero_n, pstats, thr_hi)
         if (pstats) {
             if (pack) DW_FF(kFusedRot, true, true); else if (rot) DW_FF(kFusedRot, false, true);
             else if (ring) DW_FF(kFusedRing, false, true); else DW_FF(kFusedOvl, false, true);
@@ -850,13 +879,13 @@ static int launch_agents(dw_handle* h, const int* d_action, int act_b, int act_n
          "downloaded agent states, upload them, then dw_step without actions");
     const int blocks = (p.batch + 63) / 64;
 #define DW_AG(T, PL, PD)                                                                                          \
-    hipLaunchKernelGGL(agents_update<T>, dim3(blocks), dim3(64), 0, h->stream, PL, PD, h->idx, h->st, d_action,    \
+    hipLaunchKernelGGL(agents_update<T>, dim3(blocks), dim3(64), 0, h->stream, PL, PD, h->idx.get(), h->st.get(), d_action,    \
                        act_b, act_n, p.batch, p.n_agents, p.height, p.width, p.agent_gamma,                        \
                        p.collision_mode == 0 ? 1 : 0, d_reward, d_done, d_ok)
     if (h->unq == OWN_CUR) {                       // grazing on the un-quantised state, in its own format
-        if (h->unq_kind == UNQ_F64) DW_AG(double, h->L64, h->D64); else DW_AG(float, h->U32L, h->U32D);
+        if (h->unq_kind == UNQ_F64) DW_AG(double, h->L64.get(), h->D64.get()); else DW_AG(float, h->U32L.get(), h->U32D.get());
     } else {
-        DW_AG(plane_t, h->L16[h->cur], h->D16[h->cur]);
+        DW_AG(plane_t, h->L16[h->cur].get(), h->D16[h->cur].get());
     }
 #undef DW_AG
     HIPCHK(hipGetLastError());
@@ -868,7 +897,7 @@ static int stage_host_actions(dw_handle* h, const int32_t* action, int b, int n)
     NEED(b >= 0 && n >= 0 && b <= p.batch && n <= p.n_agents, DW_EINVAL,
          "action block %dx%d exceeds (B,N)=(%d,%d)", b, n, p.batch, p.n_agents);
     if ((size_t)b * n)
-        HIPCHK(hipMemcpyAsync(h->action_tmp, action, sizeof(int) * (size_t)b * n, hipMemcpyHostToDevice,
+        HIPCHK(hipMemcpyAsync(h->action_tmp.get(), action, sizeof(int) * (size_t)b * n, hipMemcpyHostToDevice,
                               h->stream));
     return DW_OK;
 }
@@ -947,55 +976,39 @@ int dw_create(const dw_params* p, dw_handle** out) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(DW_ENODEVICE, "device %d is %s; this library is built for gfx950 only", p->device,
                     prop.gcnArchName);
-    dw_handle* h = new (std::nothrow) dw_handle();
+    // a handle that is not complete is destroyed on the way out (dw_destroy; its buffers by their owners)
+    std::unique_ptr<dw_handle, int (*)(dw_handle*)> h(new (std::nothrow) dw_handle(), dw_destroy);
     NEED(h, DW_ENOMEM, "host allocation failed");
     h->prm = *p;
     h->cells = (size_t)p->batch * p->height * p->width;
-    auto cleanup = [&](int code) { dw_destroy(h); return code; };
-#define TRY(expr)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return cleanup(fail(e_ == hipErrorOutOfMemory ? DW_ENOMEM : DW_EHIP, "%s failed: %s", #expr, \
-                                hipGetErrorString(e_)));                                           \
-    } while (0)
-    TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = true;
-    for (int i = 0; i < 2; ++i) {
-        TRY(hipMalloc(&h->L16[i], sizeof(plane_t) * h->cells));
-        TRY(hipMalloc(&h->D16[i], sizeof(plane_t) * h->cells));
-    }
     const size_t bn = (size_t)p->batch * (p->n_agents > 0 ? p->n_agents : 1);
-    TRY(hipMalloc(&h->idx, sizeof(int) * bn * 2));
-    TRY(hipMalloc(&h->st, sizeof(double) * bn));
-    TRY(hipMalloc(&h->action, sizeof(int) * bn));
-    TRY(hipMalloc(&h->action_tmp, sizeof(int) * bn));
-    TRY(hipMalloc(&h->reward_d, sizeof(double) * bn));
-    TRY(hipMalloc(&h->done_d, bn));
-    TRY(hipMalloc(&h->agents_done_at, sizeof(int) * bn));
-    TRY(hipMalloc(&h->done_at, sizeof(int) * p->batch));
-    TRY(hipMalloc(&h->n_alive, sizeof(int)));
+    const size_t pb = sizeof(plane_t) * h->cells;
     // [(B+1) StatsDev][(kNumQueues+1)*16 uint queue counters]
     h->stats_bytes = sizeof(StatsDev) * (p->batch + 1) + sizeof(unsigned int) * (kNumQueues + 1) * 16;
-    for (int i = 0; i < 2; ++i) {
-        TRY(hipMalloc(&h->stats2[i], h->stats_bytes));
-        TRY(hipMemsetAsync(h->stats2[i], 0, h->stats_bytes, h->stream));
-    }
+    if (int rc = alloc_group(h.get(), "the handle's state",
+                             {{h->L16[0], pb}, {h->D16[0], pb}, {h->L16[1], pb}, {h->D16[1], pb},
+                              {h->idx, sizeof(int) * bn * 2}, {h->st, sizeof(double) * bn}, {h->action, sizeof(int) * bn},
+                              {h->action_tmp, sizeof(int) * bn}, {h->reward_d, sizeof(double) * bn}, {h->done_d, bn},
+                              {h->agents_done_at, sizeof(int) * bn}, {h->done_at, sizeof(int) * p->batch},
+                              {h->n_alive, sizeof(int)}, {h->stats2[0], h->stats_bytes}, {h->stats2[1], h->stats_bytes},
+                              {h->side_stats, sizeof(StatsDev) * (p->batch + 1)}}))
+        return rc;
+    for (int i = 0; i < 2; ++i) HIPCHK(hipMemsetAsync(h->stats2[i].get(), 0, h->stats_bytes, h->stream));
     h->sw = read_switches();                                    // the environment is read here and nowhere else
-    select_kernel(h);
-    if (int qrc = ensure_fixq(h)) return cleanup(qrc);
-    TRY(hipMemsetAsync(h->action, 0, sizeof(int) * bn, h->stream));
-    TRY(hipMemsetAsync(h->done_at, 0, sizeof(int) * p->batch, h->stream));
-    TRY(hipMemsetAsync(h->agents_done_at, 0, sizeof(int) * bn, h->stream));
-    TRY(hipMemsetAsync(h->n_alive, 0, sizeof(int), h->stream));
-    TRY(hipMalloc(&h->side_stats, sizeof(StatsDev) * (p->batch + 1)));
-    TRY(hipEventCreate(&h->ev0));
-    TRY(hipEventCreate(&h->ev1));
-    TRY(hipEventCreate(&h->evf0));
-    TRY(hipEventCreate(&h->evf1));
-#undef TRY
-    select_kernel(h);
-    *out = h;
+    if (int rc = ensure_fixq(h.get(), *p)) return rc;
+    HIPCHK(hipMemsetAsync(h->action.get(), 0, sizeof(int) * bn, h->stream));
+    HIPCHK(hipMemsetAsync(h->done_at.get(), 0, sizeof(int) * p->batch, h->stream));
+    HIPCHK(hipMemsetAsync(h->agents_done_at.get(), 0, sizeof(int) * bn, h->stream));
+    HIPCHK(hipMemsetAsync(h->n_alive.get(), 0, sizeof(int), h->stream));
+    HIPCHK(hipEventCreate(&h->ev0));
+    HIPCHK(hipEventCreate(&h->ev1));
+    HIPCHK(hipEventCreate(&h->evf0));
+    HIPCHK(hipEventCreate(&h->evf1));
+    select_kernel(h.get());
+    h->created = true;
+    *out = h.release();
     return DW_OK;
 }
 
@@ -1003,27 +1016,12 @@ int dw_destroy(dw_handle* h) {
     if (!h) return DW_OK;
     (void)hipSetDevice(h->prm.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 2; ++i) { (void)hipFree(h->L16[i]); (void)hipFree(h->D16[i]); }
-    (void)hipFree(h->L64); (void)hipFree(h->D64);
-    (void)hipFree(h->U32L); (void)hipFree(h->U32D); (void)hipFree(h->side_stats);
-    (void)hipFree(h->idx); (void)hipFree(h->st); (void)hipFree(h->action); (void)hipFree(h->action_tmp);
-    (void)hipFree(h->reward_d); (void)hipFree(h->done_d);
-    if (h->pinned) (void)hipHostFree(h->pinned);
-    if (h->ep_pinned) (void)hipHostFree(h->ep_pinned);
-    (void)hipFree(h->mlp_w);
-    for (auto& sn : h->snap) {
-        (void)hipFree(sn.L); (void)hipFree(sn.D); (void)hipFree(sn.idx); (void)hipFree(sn.st);
-        (void)hipFree(sn.PL); (void)hipFree(sn.PD);
-        (void)hipFree(sn.stats);
-    }
-    (void)hipFree(h->agents_done_at); (void)hipFree(h->done_at); (void)hipFree(h->n_alive);
-    (void)hipFree(h->stats2[0]); (void)hipFree(h->stats2[1]); (void)hipFree(h->scratch); (void)hipFree(h->ep_buf); (void)hipFree(h->fixq); (void)hipFree(h->redo_tiles);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->evf0) (void)hipEventDestroy(h->evf0);
     if (h->evf1) (void)hipEventDestroy(h->evf1);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                                   // the owners give the buffers back
     return DW_OK;
 }
 
@@ -1035,9 +1033,11 @@ int dw_set_params(dw_handle* h, const dw_params* p) {
     NEED(p->batch == o.batch && p->height == o.height && p->width == o.width && p->n_agents == o.n_agents &&
              p->device == o.device,
          DW_EINVAL, "dw_set_params cannot change shape or device; create a new handle");
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = ensure_fixq(h, *p))) return rc;                   // a failure leaves the handle as it was
     h->prm = *p;
     select_kernel(h);
-    return ensure_fixq(h);
+    return DW_OK;
 }
 
 int dw_get_params(const dw_handle* h, dw_params* out) {
@@ -1050,7 +1050,7 @@ int dw_get_params(const dw_handle* h, dw_params* out) {
 
 // reductions of the current state, whatever its format (after uploads / init, so that dw_reduce is always valid)
 static int clear_stats(dw_handle* h) {
-    for (int i = 0; i < 2; ++i) HIPCHK(hipMemsetAsync(h->stats2[i], 0, h->stats_bytes, h->stream));
+    for (int i = 0; i < 2; ++i) HIPCHK(hipMemsetAsync(h->stats2[i].get(), 0, h->stats_bytes, h->stream));
     return DW_OK;
 }
 static int refresh_stats(dw_handle* h) {
@@ -1059,11 +1059,11 @@ static int refresh_stats(dw_handle* h) {
     const int n = p.height * p.width;
     const dim3 g((unsigned)((n + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
     if (h->unq != OWN_CUR)
-        hipLaunchKernelGGL((stats_only<plane_t>), g, dim3(256), 0, h->stream, h->L16[h->cur], h->D16[h->cur], n, h->stats2[h->sp]);
+        hipLaunchKernelGGL((stats_only<plane_t>), g, dim3(256), 0, h->stream, h->L16[h->cur].get(), h->D16[h->cur].get(), n, h->stats2[h->sp].get());
     else if (h->unq_kind == UNQ_F64)
-        hipLaunchKernelGGL((stats_only<double>), g, dim3(256), 0, h->stream, h->L64, h->D64, n, h->stats2[h->sp]);
+        hipLaunchKernelGGL((stats_only<double>), g, dim3(256), 0, h->stream, h->L64.get(), h->D64.get(), n, h->stats2[h->sp].get());
     else
-        hipLaunchKernelGGL((stats_only<float>), g, dim3(256), 0, h->stream, h->U32L, h->U32D, n, h->stats2[h->sp]);
+        hipLaunchKernelGGL((stats_only<float>), g, dim3(256), 0, h->stream, h->U32L.get(), h->U32D.get(), n, h->stats2[h->sp].get());
     HIPCHK(hipGetLastError());
     return DW_OK;
 }
@@ -1072,8 +1072,8 @@ int dw_upload_state_f64(dw_handle* h, const double* light, const double* dark) {
     NEED(h && light && dark, DW_EINVAL, "null argument");
     HIPCHK(hipSetDevice(h->prm.device));
     if (int arc = ensure_f64(h)) return arc;
-    HIPCHK(hipMemcpyAsync(h->L64, light, sizeof(double) * h->cells, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->D64, dark, sizeof(double) * h->cells, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->L64.get(), light, sizeof(double) * h->cells, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->D64.get(), dark, sizeof(double) * h->cells, hipMemcpyHostToDevice, h->stream));
     h->unq_kind = UNQ_F64;
     h->unq = OWN_CUR;
     h->have_state = true;
@@ -1093,21 +1093,21 @@ int dw_upload_state_f32(dw_handle* h, const float* light, const float* dark, int
         // natural-unit floats staged in scratch, rounded to the per-mille integers of the canonical planes
         int rc = ensure_scratch(h, sizeof(float) * 2 * h->cells);
         if (rc) return rc;
-        float* sL = reinterpret_cast<float*>(h->scratch);
+        float* sL = reinterpret_cast<float*>(h->scratch.get());
         float* sD = sL + h->cells;
         HIPCHK(hipMemcpyAsync(sL, light, sizeof(float) * h->cells, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(sD, dark, sizeof(float) * h->cells, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(f32nat_to_plane, dim3(blocks), dim3(256), 0, h->stream, sL, h->L16[h->cur], h->cells);
-        hipLaunchKernelGGL(f32nat_to_plane, dim3(blocks), dim3(256), 0, h->stream, sD, h->D16[h->cur], h->cells);
+        hipLaunchKernelGGL(f32nat_to_plane, dim3(blocks), dim3(256), 0, h->stream, sL, h->L16[h->cur].get(), h->cells);
+        hipLaunchKernelGGL(f32nat_to_plane, dim3(blocks), dim3(256), 0, h->stream, sD, h->D16[h->cur].get(), h->cells);
         HIPCHK(hipGetLastError());
         h->unq = OWN_NONE;
     } else {
         int rc = ensure_u32(h);
         if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(h->U32L, light, sizeof(float) * h->cells, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->U32D, dark, sizeof(float) * h->cells, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(f32nat_to_permille, dim3(blocks), dim3(256), 0, h->stream, h->U32L, h->U32L, h->cells);
-        hipLaunchKernelGGL(f32nat_to_permille, dim3(blocks), dim3(256), 0, h->stream, h->U32D, h->U32D, h->cells);
+        HIPCHK(hipMemcpyAsync(h->U32L.get(), light, sizeof(float) * h->cells, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->U32D.get(), dark, sizeof(float) * h->cells, hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(f32nat_to_permille, dim3(blocks), dim3(256), 0, h->stream, h->U32L.get(), h->U32L.get(), h->cells);
+        hipLaunchKernelGGL(f32nat_to_permille, dim3(blocks), dim3(256), 0, h->stream, h->U32D.get(), h->U32D.get(), h->cells);
         HIPCHK(hipGetLastError());
         h->unq_kind = UNQ_F32;
         h->unq = OWN_CUR;
@@ -1134,8 +1134,8 @@ int dw_upload_agents(dw_handle* h, const int32_t* indices, const double* states)
                  DW_EINVAL, "agent %zu position (%d,%d) outside the %dx%d grid", i, indices[2 * i],
                  indices[2 * i + 1], p.height, p.width);
         }
-        HIPCHK(hipMemcpyAsync(h->idx, indices, sizeof(int) * bn * 2, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->st, states, sizeof(double) * bn, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->idx.get(), indices, sizeof(int) * bn * 2, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->st.get(), states, sizeof(double) * bn, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     h->have_agents = true;
@@ -1149,8 +1149,8 @@ int dw_download_agents(dw_handle* h, int32_t* indices, double* states) {
     const size_t bn = (size_t)p.batch * p.n_agents;
     if (bn) {
         NEED(h->have_agents, DW_ESTATE, "no agents");
-        if (indices) HIPCHK(hipMemcpyAsync(indices, h->idx, sizeof(int) * bn * 2, hipMemcpyDeviceToHost, h->stream));
-        if (states) HIPCHK(hipMemcpyAsync(states, h->st, sizeof(double) * bn, hipMemcpyDeviceToHost, h->stream));
+        if (indices) HIPCHK(hipMemcpyAsync(indices, h->idx.get(), sizeof(int) * bn * 2, hipMemcpyDeviceToHost, h->stream));
+        if (states) HIPCHK(hipMemcpyAsync(states, h->st.get(), sizeof(double) * bn, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return DW_OK;
@@ -1166,13 +1166,13 @@ int dw_init_random(dw_handle* h, uint64_t seed) {
     if (int crc = clear_stats(h)) return crc;
     const int ncell = p.height * p.width;
     const dim3 g((unsigned)((ncell + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
-    hipLaunchKernelGGL((init_random_cells<float>), g, dim3(256), 0, h->stream, h->U32L, h->U32D, ncell,
+    hipLaunchKernelGGL((init_random_cells<float>), g, dim3(256), 0, h->stream, h->U32L.get(), h->U32D.get(), ncell,
                        (long long)p.world_offset, (unsigned long long)seed, (float)p.light_proportion,
-                       (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp]);
+                       (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp].get());
     HIPCHK(hipGetLastError());
     if (p.n_agents) {
         const int bn = p.batch * p.n_agents;
-        hipLaunchKernelGGL(init_random_agents, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->idx, h->st,
+        hipLaunchKernelGGL(init_random_agents, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->idx.get(), h->st.get(),
                            p.batch, p.n_agents, p.height, p.width, (long long)p.world_offset,
                            (unsigned long long)seed);
         HIPCHK(hipGetLastError());
@@ -1193,13 +1193,13 @@ int dw_init_random_quantised(dw_handle* h, uint64_t seed) {
     if (int crc = clear_stats(h)) return crc;
     const int ncell = p.height * p.width;
     const dim3 g((unsigned)((ncell + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
-    hipLaunchKernelGGL((init_random_cells<plane_t>), g, dim3(256), 0, h->stream, h->L16[h->cur], h->D16[h->cur], ncell,
+    hipLaunchKernelGGL((init_random_cells<plane_t>), g, dim3(256), 0, h->stream, h->L16[h->cur].get(), h->D16[h->cur].get(), ncell,
                        (long long)p.world_offset, (unsigned long long)seed, (float)p.light_proportion,
-                       (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp]);
+                       (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp].get());
     HIPCHK(hipGetLastError());
     if (p.n_agents) {
         const int bn = p.batch * p.n_agents;
-        hipLaunchKernelGGL(init_random_agents, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->idx, h->st,
+        hipLaunchKernelGGL(init_random_agents, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->idx.get(), h->st.get(),
                            p.batch, p.n_agents, p.height, p.width, (long long)p.world_offset,
                            (unsigned long long)seed);
         HIPCHK(hipGetLastError());
@@ -1223,8 +1223,8 @@ int dw_download_planes(dw_handle* h, int which, double* light, double* dark) {
     const bool unq = (which == DW_STATE_CURRENT && h->unq == OWN_CUR) || (which == DW_STATE_PREVIOUS && h->unq == OWN_PREV);
     const size_t bytes = sizeof(double) * h->cells;
     if (unq && h->unq_kind == UNQ_F64) {
-        if (light) HIPCHK(hipMemcpyAsync(light, h->L64, bytes, hipMemcpyDeviceToHost, h->stream));
-        if (dark) HIPCHK(hipMemcpyAsync(dark, h->D64, bytes, hipMemcpyDeviceToHost, h->stream));
+        if (light) HIPCHK(hipMemcpyAsync(light, h->L64.get(), bytes, hipMemcpyDeviceToHost, h->stream));
+        if (dark) HIPCHK(hipMemcpyAsync(dark, h->D64.get(), bytes, hipMemcpyDeviceToHost, h->stream));
     } else {
         int rc = ensure_scratch(h, bytes);
         if (rc) return rc;
@@ -1234,12 +1234,12 @@ int dw_download_planes(dw_handle* h, int which, double* light, double* dark) {
             if (!dst) continue;
             if (unq)
                 hipLaunchKernelGGL((plane_to_f64<float>), dim3(blocks), dim3(256), 0, h->stream,
-                                   pl == 0 ? h->U32L : h->U32D, h->scratch, h->cells);
+                                   pl == 0 ? h->U32L.get() : h->U32D.get(), h->scratch.get(), h->cells);
             else
                 hipLaunchKernelGGL((plane_to_f64<plane_t>), dim3(blocks), dim3(256), 0, h->stream,
-                                   pl == 0 ? h->L16[buf] : h->D16[buf], h->scratch, h->cells);
+                                   pl == 0 ? h->L16[buf].get() : h->D16[buf].get(), h->scratch.get(), h->cells);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(dst, h->scratch, bytes, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(dst, h->scratch.get(), bytes, hipMemcpyDeviceToHost, h->stream));
         }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1254,12 +1254,12 @@ static DerivedFrom derived_from(const dw_handle* h) {
     const int cur = h->cur, prev = 1 - h->cur;
     if (h->stepped) {
         if (h->unq == OWN_PREV)
-            return h->unq_kind == UNQ_F64 ? DerivedFrom{2, h->L64, h->D64, true} : DerivedFrom{1, h->U32L, h->U32D, true};
-        return DerivedFrom{0, h->L16[prev], h->D16[prev], true};
+            return h->unq_kind == UNQ_F64 ? DerivedFrom{2, h->L64.get(), h->D64.get(), true} : DerivedFrom{1, h->U32L.get(), h->U32D.get(), true};
+        return DerivedFrom{0, h->L16[prev].get(), h->D16[prev].get(), true};
     }
     if (h->unq == OWN_CUR)
-        return h->unq_kind == UNQ_F64 ? DerivedFrom{2, h->L64, h->D64, false} : DerivedFrom{1, h->U32L, h->U32D, false};
-    return DerivedFrom{0, h->L16[cur], h->D16[cur], false};
+        return h->unq_kind == UNQ_F64 ? DerivedFrom{2, h->L64.get(), h->D64.get(), false} : DerivedFrom{1, h->U32L.get(), h->U32D.get(), false};
+    return DerivedFrom{0, h->L16[cur].get(), h->D16[cur].get(), false};
 }
 // K<T, POST>(pL, pD, args...) for the format / phase of `src`
 #define DW_DISPATCH_DERIVED(K, src, grid, block, ...)                                                               \
@@ -1283,14 +1283,14 @@ static int run_materialise(dw_handle* h, double L, double* d_grid7, double* d_te
     const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
     const DerivedFrom src = derived_from(h);
     const PhysF64 P = make_f64(p, src.post ? h->L_last : L);
-    const plane_t* cL = h->L16[h->cur];            // read by the POST variants only
-    const plane_t* cD = h->D16[h->cur];
+    const plane_t* cL = h->L16[h->cur].get();            // read by the POST variants only
+    const plane_t* cD = h->D16[h->cur].get();
     DW_DISPATCH_DERIVED(materialise, src, g, dim3(256), cL, cD, p.height, p.width, P, d_grid7, d_temps, d_betas, d_growth,
                         d_teff);
     HIPCHK(hipGetLastError());
     if (src.post && d_grid7 && p.n_agents && h->have_agents) {
-        hipLaunchKernelGGL(agents_stamp, dim3((p.batch + 63) / 64), dim3(64), 0, h->stream, d_grid7, h->idx,
-                           h->st, p.batch, p.n_agents, p.height, p.width);
+        hipLaunchKernelGGL(agents_stamp, dim3((p.batch + 63) / 64), dim3(64), 0, h->stream, d_grid7, h->idx.get(),
+                           h->st.get(), p.batch, p.n_agents, p.height, p.width);
         HIPCHK(hipGetLastError());
     }
     return DW_OK;
@@ -1303,9 +1303,9 @@ int dw_download_grid(dw_handle* h, double L_init, double* grid7) {
     const size_t bytes = sizeof(double) * 7 * h->cells;
     int rc = ensure_scratch(h, bytes);
     if (rc) return rc;
-    rc = run_materialise(h, L_init, h->scratch, nullptr, nullptr, nullptr, nullptr);
+    rc = run_materialise(h, L_init, h->scratch.get(), nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(grid7, h->scratch, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(grid7, h->scratch.get(), bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return DW_OK;
 }
@@ -1318,7 +1318,7 @@ int dw_download_caches(dw_handle* h, double L, double* temps, double* betas, dou
     const size_t n = h->cells;
     int rc = ensure_scratch(h, sizeof(double) * 9 * n);
     if (rc) return rc;
-    double* d_t = h->scratch;
+    double* d_t = h->scratch.get();
     double* d_b = d_t + 3 * n;
     double* d_g = d_b + 3 * n;
     double* d_e = d_g + 2 * n;
@@ -1340,7 +1340,7 @@ int dw_update_agents(dw_handle* h, const int32_t* action, int32_t action_b, int3
     HIPCHK(hipSetDevice(h->prm.device));
     int rc = stage_host_actions(h, action, action_b, action_n);
     if (rc) return rc;
-    return launch_agents(h, h->action_tmp, action_b, action_n, true);
+    return launch_agents(h, h->action_tmp.get(), action_b, action_n, true);
 }
 
 int dw_step(dw_handle* h, const int32_t* action, int32_t action_b, int32_t action_n, double L) {
@@ -1349,7 +1349,7 @@ int dw_step(dw_handle* h, const int32_t* action, int32_t action_b, int32_t actio
     if (action) {
         int rc = stage_host_actions(h, action, action_b, action_n);
         if (rc) return rc;
-        rc = launch_agents(h, h->action_tmp, action_b, action_n);
+        rc = launch_agents(h, h->action_tmp.get(), action_b, action_n);
         if (rc) return rc;
     }
     return launch_forward(h, L);
@@ -1358,7 +1358,7 @@ int dw_step(dw_handle* h, const int32_t* action, int32_t action_b, int32_t actio
 int dw_step_device_actions(dw_handle* h, double L) {
     NEED(h, DW_EINVAL, "null handle");
     HIPCHK(hipSetDevice(h->prm.device));
-    int rc = launch_agents(h, h->action, h->prm.batch, h->prm.n_agents);
+    int rc = launch_agents(h, h->action.get(), h->prm.batch, h->prm.n_agents);
     if (rc) return rc;
     return launch_forward(h, L);
 }
@@ -1368,7 +1368,7 @@ int dw_upload_actions(dw_handle* h, const int32_t* action) {
     HIPCHK(hipSetDevice(h->prm.device));
     const size_t bn = (size_t)h->prm.batch * h->prm.n_agents;
     if (bn) {
-        HIPCHK(hipMemcpyAsync(h->action, action, sizeof(int) * bn, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->action.get(), action, sizeof(int) * bn, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     return DW_OK;
@@ -1378,7 +1378,7 @@ int dw_download_actions(dw_handle* h, int32_t* action) {
     NEED(h && action, DW_EINVAL, "null argument");
     HIPCHK(hipSetDevice(h->prm.device));
     const size_t bn = (size_t)h->prm.batch * h->prm.n_agents;
-    if (bn) HIPCHK(hipMemcpyAsync(action, h->action, sizeof(int) * bn, hipMemcpyDeviceToHost, h->stream));
+    if (bn) HIPCHK(hipMemcpyAsync(action, h->action.get(), sizeof(int) * bn, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return DW_OK;
 }
@@ -1422,7 +1422,7 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
         // so that the retained previous state is the true predecessor.  HIP events around the run of fused
         // launches feed dw_last_step_n_timing (the dominant kernel's duration, measured on its own stream).
         // The first fused launch ends the life of an un-quantised PREVIOUS state (after it the retained state is two
-        // steps back anyway): drop it here, so that release_unquantised's synchronise + hipFree of 128 GiB at the
+        // steps back anyway): drop it here, so that release_unquantised's synchronise + free of 128 GiB at the
         // north-star shape happen in front of the timed window and not inside it.
         if (h->unq == OWN_PREV) { h->unq = OWN_NONE; h->stepped = false; }
         release_unquantised(h);
@@ -1444,7 +1444,7 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
     for (int s = s0; s < nsteps; ++s) {
         int rc;
         if (use_device_actions) {
-            rc = launch_agents(h, h->action, h->prm.batch, h->prm.n_agents);
+            rc = launch_agents(h, h->action.get(), h->prm.batch, h->prm.n_agents);
             if (rc) return rc;
         }
         rc = launch_forward(h, L);
@@ -1477,7 +1477,7 @@ int dw_forward_f64(dw_handle* h, const double* light, const double* dark, double
     // scratch layout: [in light n][in dark n][grid7 7n][caches 9n] doubles, [new light n][new dark n] binary16
     int rc = ensure_scratch(h, sizeof(double) * 18 * n + sizeof(plane_t) * 2 * n + 16);
     if (rc) return rc;
-    double* dL = h->scratch;
+    double* dL = h->scratch.get();
     double* dD = dL + n;
     double* dG = dD + n;
     double* d_t = dG + 7 * n;
@@ -1487,7 +1487,7 @@ int dw_forward_f64(dw_handle* h, const double* light, const double* dark, double
     plane_t* nL = reinterpret_cast<plane_t*>(d_e + n);
     plane_t* nD = nL + n;
     // the reductions of this side computation must not disturb the handle's per-world stats
-    StatsDev* tmp_stats = h->side_stats;
+    StatsDev* tmp_stats = h->side_stats.get();
     HIPCHK(hipMemsetAsync(tmp_stats, 0, sizeof(StatsDev) * (p.batch + 1), h->stream));
     HIPCHK(hipMemcpyAsync(dL, light, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     {
@@ -1508,7 +1508,7 @@ int dw_forward_f64(dw_handle* h, const double* light, const double* dark, double
                        growth ? d_g : (double*)nullptr, temp_effective ? d_e : (double*)nullptr);
     hipError_t le = hipGetLastError();
     if (le == hipSuccess && p.n_agents && h->have_agents) {
-        hipLaunchKernelGGL(agents_stamp, dim3((p.batch + 63) / 64), dim3(64), 0, h->stream, dG, h->idx, h->st,
+        hipLaunchKernelGGL(agents_stamp, dim3((p.batch + 63) / 64), dim3(64), 0, h->stream, dG, h->idx.get(), h->st.get(),
                            p.batch, p.n_agents, p.height, p.width);
         le = hipGetLastError();
     }
@@ -1532,7 +1532,7 @@ int dw_conv3x3_f64(dw_handle* h, const double* plane, const double kernel[9], do
     const size_t n = h->cells;
     int rc = ensure_scratch(h, sizeof(double) * 2 * n);
     if (rc) return rc;
-    double* d_in = h->scratch;
+    double* d_in = h->scratch.get();
     double* d_out = d_in + n;
     Kernel9 K;
     for (int i = 0; i < 9; ++i) K.k[i] = kernel[i];
@@ -1556,7 +1556,7 @@ int dw_stage_f64(dw_handle* h, int stage, const double* in, double* out, double 
     const size_t n = h->cells, nin = (size_t)stage_inputs(stage), nout = (size_t)stage_outputs(stage);
     int rc = ensure_scratch(h, sizeof(double) * (nin + nout) * n);
     if (rc) return rc;
-    double* d_in = h->scratch;
+    double* d_in = h->scratch.get();
     double* d_out = d_in + nin * n;
     Kernel9 K{};
     if (kernel) for (int i = 0; i < 9; ++i) K.k[i] = kernel[i];
@@ -1590,7 +1590,7 @@ int dw_get_obs(dw_handle* h, double L_init, double* obs) {
     NEED(h->have_state && h->have_agents, DW_ESTATE, "no state / agents");
     int rc = observe_into_scratch(h, L_init, 0);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(obs, h->scratch, sizeof(double) * bn * 63, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(obs, h->scratch.get(), sizeof(double) * bn * 63, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return DW_OK;
 }
@@ -1610,21 +1610,16 @@ int dw_env_step(dw_handle* h, const int32_t* action, int32_t action_b, int32_t a
     // observation blocks only reward | done are staged, at o_rew)
     const size_t o_act = 0, o_obs = up(sizeof(int) * bn), o_rew = o_obs + sizeof(double) * bn * 63;
     const size_t total = up(o_rew + sizeof(double) * bn + bn) + 256;
-    if (h->pinned_bytes < total) {
-        if (h->pinned) HIPCHK(hipHostFree(h->pinned));
-        h->pinned = nullptr; h->pinned_bytes = 0;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->pinned), total, hipHostMallocDefault));
-        h->pinned_bytes = total;
-    }
+    if (int rc = reserve(h->pinned, "the page-locked step staging", total)) return rc;
     if (action) {
         NEED(action_b >= 0 && action_n >= 0 && action_b <= p.batch && action_n <= p.n_agents, DW_EINVAL,
              "action block %dx%d exceeds (B,N)=(%d,%d)", action_b, action_n, p.batch, p.n_agents);
         const size_t na = (size_t)action_b * action_n;
         if (na) {
-            std::memcpy(h->pinned + o_act, action, sizeof(int) * na);
-            HIPCHK(hipMemcpyAsync(h->action_tmp, h->pinned + o_act, sizeof(int) * na, hipMemcpyHostToDevice, h->stream));
+            std::memcpy(h->pinned.get() + o_act, action, sizeof(int) * na);
+            HIPCHK(hipMemcpyAsync(h->action_tmp.get(), h->pinned.get() + o_act, sizeof(int) * na, hipMemcpyHostToDevice, h->stream));
         }
-        int rc = launch_agents(h, h->action_tmp, action_b, action_n);
+        int rc = launch_agents(h, h->action_tmp.get(), action_b, action_n);
         if (rc) return rc;
     }
     int rc = launch_forward(h, L);
@@ -1636,15 +1631,15 @@ int dw_env_step(dw_handle* h, const int32_t* action, int32_t action_b, int32_t a
         const size_t d_rew = sizeof(double) * bn * 63, d_done = d_rew + sizeof(double) * bn, d_total = d_done + bn;
         rc = observe_into_scratch(h, L, d_total - d_rew + 64, true);     // reward | done written by the same kernel
         if (rc) return rc;
-        unsigned char* blk = reinterpret_cast<unsigned char*>(h->scratch);
+        unsigned char* blk = reinterpret_cast<unsigned char*>(h->scratch.get());
         if (big_obs) {
             if (obs) HIPCHK(hipMemcpyAsync(obs, blk, d_rew, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(h->pinned + o_rew, blk + d_rew, d_total - d_rew, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(h->pinned.get() + o_rew, blk + d_rew, d_total - d_rew, hipMemcpyDeviceToHost, h->stream));
         } else {
-            HIPCHK(hipMemcpyAsync(h->pinned + o_obs, blk, d_total, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(h->pinned.get() + o_obs, blk, d_total, hipMemcpyDeviceToHost, h->stream));
         }
         HIPCHK(hipStreamSynchronize(h->stream));
-        const unsigned char* src = big_obs ? h->pinned + o_rew - d_rew : h->pinned + o_obs;     // base of the block image
+        const unsigned char* src = big_obs ? h->pinned.get() + o_rew - d_rew : h->pinned.get() + o_obs;     // base of the block image
         if (obs && !big_obs) std::memcpy(obs, src, d_rew);
         if (reward) std::memcpy(reward, src + d_rew, sizeof(double) * bn);
         if (done) std::memcpy(done, src + d_done, bn);
@@ -1659,10 +1654,10 @@ int dw_get_reward_done(dw_handle* h, double* reward, uint8_t* done) {
     const int bn = p.batch * p.n_agents;
     if (bn == 0) return DW_OK;
     NEED(h->have_agents, DW_ESTATE, "no agents");
-    hipLaunchKernelGGL(reward_done, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->st, h->reward_d, h->done_d, bn);
+    hipLaunchKernelGGL(reward_done, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->st.get(), h->reward_d.get(), h->done_d.get(), bn);
     HIPCHK(hipGetLastError());
-    if (reward) HIPCHK(hipMemcpyAsync(reward, h->reward_d, sizeof(double) * bn, hipMemcpyDeviceToHost, h->stream));
-    if (done) HIPCHK(hipMemcpyAsync(done, h->done_d, (size_t)bn, hipMemcpyDeviceToHost, h->stream));
+    if (reward) HIPCHK(hipMemcpyAsync(reward, h->reward_d.get(), sizeof(double) * bn, hipMemcpyDeviceToHost, h->stream));
+    if (done) HIPCHK(hipMemcpyAsync(done, h->done_d.get(), (size_t)bn, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return DW_OK;
 }
@@ -1672,24 +1667,24 @@ int dw_reduce(dw_handle* h, dw_world_stats* per_world) {
     NEED(h->have_state, DW_ESTATE, "no state");
     static_assert(sizeof(dw_world_stats) == sizeof(StatsDev), "stats layout");
     HIPCHK(hipSetDevice(h->prm.device));
-    HIPCHK(hipMemcpyAsync(per_world, h->stats2[h->sp], sizeof(StatsDev) * h->prm.batch, hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(per_world, h->stats2[h->sp].get(), sizeof(StatsDev) * h->prm.batch, hipMemcpyDeviceToHost,
                           h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return DW_OK;
 }
 
 // Greedy / anti-greedy choice of every agent from the CURRENT covers (ref Greedy.__call__, agents/greedy.py:18-30)
-// into h->action; agent_mode / codes as in policy_greedy (dw_agents.hpp).
+// into h->action.get(); agent_mode / codes as in policy_greedy (dw_agents.hpp).
 static int launch_policy_greedy(dw_handle* h, int argmin, const int* agent_mode, int codes) {
     const dw_params& p = h->prm;
     const int bn = p.batch * p.n_agents;
     const dim3 g((unsigned)((bn + 255) / 256));
     if (h->unq == OWN_CUR && h->unq_kind == UNQ_F32)
-        hipLaunchKernelGGL(policy_greedy<float>, g, dim3(256), 0, h->stream, h->U32L, h->U32D, h->idx, p.batch, p.n_agents,
-                           p.height, p.width, p.obs_mask, argmin, agent_mode, h->action, codes);
+        hipLaunchKernelGGL(policy_greedy<float>, g, dim3(256), 0, h->stream, h->U32L.get(), h->U32D.get(), h->idx.get(), p.batch, p.n_agents,
+                           p.height, p.width, p.obs_mask, argmin, agent_mode, h->action.get(), codes);
     else
-        hipLaunchKernelGGL(policy_greedy<plane_t>, g, dim3(256), 0, h->stream, h->L16[h->cur], h->D16[h->cur], h->idx,
-                           p.batch, p.n_agents, p.height, p.width, p.obs_mask, argmin, agent_mode, h->action, codes);
+        hipLaunchKernelGGL(policy_greedy<plane_t>, g, dim3(256), 0, h->stream, h->L16[h->cur].get(), h->D16[h->cur].get(), h->idx.get(),
+                           p.batch, p.n_agents, p.height, p.width, p.obs_mask, argmin, agent_mode, h->action.get(), codes);
     HIPCHK(hipGetLastError());
     return DW_OK;
 }
@@ -1722,29 +1717,29 @@ int dw_policy_per_agent(dw_handle* h, const int32_t* agent_mode) {
     // modes travel in the (otherwise idle) staging buffer of host-supplied actions; 3 -> internal code 2
     std::vector<int> m(p.n_agents);
     for (int n = 0; n < p.n_agents; ++n) m[n] = agent_mode[n] == DW_POLICY_TABLE ? 2 : agent_mode[n];
-    HIPCHK(hipMemcpyAsync(h->action_tmp, m.data(), sizeof(int) * p.n_agents, hipMemcpyHostToDevice, h->stream));
-    const int prc = launch_policy_greedy(h, 0, h->action_tmp, 0);
+    HIPCHK(hipMemcpyAsync(h->action_tmp.get(), m.data(), sizeof(int) * p.n_agents, hipMemcpyHostToDevice, h->stream));
+    const int prc = launch_policy_greedy(h, 0, h->action_tmp.get(), 0);
     HIPCHK(hipStreamSynchronize(h->stream));      // `m` is a local host buffer: also on the error path
     return prc;
 }
 
-// fills h->scratch with the [B][N][63] observations of the current state (device side of dw_get_obs)
+// fills h->scratch.get() with the [B][N][63] observations of the current state (device side of dw_get_obs)
 // reward_tail: the kernel also writes [reward (B,N) float64 | done (B,N) u8] right behind the observations
 static int observe_into_scratch(dw_handle* h, double L_init, size_t extra_bytes, bool reward_tail) {
     const dw_params& p = h->prm;
     const size_t bn = (size_t)p.batch * p.n_agents;
     int rc = ensure_scratch(h, sizeof(double) * bn * 63 + extra_bytes);
     if (rc) return rc;
-    double* d_rew = reward_tail ? h->scratch + bn * 63 : nullptr;
-    unsigned char* d_done = reward_tail ? reinterpret_cast<unsigned char*>(h->scratch + bn * 64) : nullptr;
+    double* d_rew = reward_tail ? h->scratch.get() + bn * 63 : nullptr;
+    unsigned char* d_done = reward_tail ? reinterpret_cast<unsigned char*>(h->scratch.get() + bn * 64) : nullptr;
     const int threads = (int)(bn * 9);
     const dim3 g((threads + 127) / 128);
     const DerivedFrom src = derived_from(h);
     const PhysF64 P = make_f64(p, src.post ? h->L_last : L_init);
-    const plane_t* cL = h->L16[h->cur];            // read by the POST variants only
-    const plane_t* cD = h->D16[h->cur];
-    DW_DISPATCH_DERIVED(observe, src, g, dim3(128), cL, cD, h->idx, h->st, p.batch, p.n_agents, p.height, p.width, P,
-                        p.obs_mask, h->scratch, d_rew, d_done);
+    const plane_t* cL = h->L16[h->cur].get();            // read by the POST variants only
+    const plane_t* cD = h->D16[h->cur].get();
+    DW_DISPATCH_DERIVED(observe, src, g, dim3(128), cL, cD, h->idx.get(), h->st.get(), p.batch, p.n_agents, p.height, p.width, P,
+                        p.obs_mask, h->scratch.get(), d_rew, d_done);
     HIPCHK(hipGetLastError());
     return DW_OK;
 }
@@ -1764,14 +1759,14 @@ static int policy_mlp_impl(dw_handle* h, const double* params, int32_t n_members
     const size_t mbytes = world_member ? sizeof(int) * (size_t)p.batch : 0;
     int rc = observe_into_scratch(h, L_init, wbytes + mbytes + 16);
     if (rc) return rc;
-    double* d_w = h->scratch + bn * 63;
+    double* d_w = h->scratch.get() + bn * 63;
     int* d_m = world_member ? reinterpret_cast<int*>(d_w + 1808 * (size_t)n_members) : nullptr;
     SyncOnExit guard(h->stream);                              // params / world_member are the caller's
     HIPCHK(hipMemcpyAsync(d_w, params, wbytes, hipMemcpyHostToDevice, h->stream));
     if (world_member) HIPCHK(hipMemcpyAsync(d_m, world_member, mbytes, hipMemcpyHostToDevice, h->stream));
     const int n = p.batch * (agent_end - agent_begin);
-    hipLaunchKernelGGL(policy_mlp, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->scratch, d_w, d_m, p.batch,
-                       p.n_agents, agent_begin, agent_end, h->action);
+    hipLaunchKernelGGL(policy_mlp, dim3((n + 3) / 4), dim3(64), 0, h->stream, h->scratch.get(), d_w, d_m, p.batch,
+                       p.n_agents, agent_begin, agent_end, h->action.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     guard.disarm();
@@ -1805,7 +1800,7 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     HIPCHK(hipSetDevice(p.device));
     NEED(nsteps >= 1 && nsteps <= 4096, DW_EINVAL, "nsteps must be in 1..4096");
     NEED(n_members >= 1, DW_EINVAL, "n_members < 1");
-    NEED(params || (h->mlp_w && h->mlp_members == n_members), DW_ESTATE,
+    NEED(params || (h->mlp_w.get() && h->mlp_members == n_members), DW_ESTATE,
          "params == NULL but no parameter sets of %d members are on the device", n_members);
     NEED(p.collision_mode == 0, DW_EINVAL, "collision_mode=1 is not implemented on the device");
     NEED(split >= 0 && split <= p.n_agents, DW_EINVAL, "split outside 0..n_agents");
@@ -1826,21 +1821,21 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     if (int erc = ensure_ep_buf(h, total)) return erc;
     if (params) {                                               // the sets stay on the device for later calls (params == NULL)
         if (h->mlp_members != n_members) {
-            (void)hipFree(h->mlp_w);
-            h->mlp_w = nullptr; h->mlp_members = 0;
-            HIPCHK(hipMalloc(&h->mlp_w, wbytes));
+            h->mlp_w.reset();
+            h->mlp_members = 0;
+            if (int rc = reserve(h->mlp_w, "the parameter sets", wbytes)) return rc;
             h->mlp_members = n_members;
         }
     }
-    const double* d_w = h->mlp_w;
-    const int* d_ma = member_a ? reinterpret_cast<const int*>(h->ep_buf + o_ma) : nullptr;
-    const int* d_mb = member_b ? reinterpret_cast<const int*>(h->ep_buf + o_mb) : nullptr;
-    double* d_r = reinterpret_cast<double*>(h->ep_buf + o_r);
-    unsigned char* d_d = h->ep_buf + o_d;
+    const double* d_w = h->mlp_w.get();
+    const int* d_ma = member_a ? reinterpret_cast<const int*>(h->ep_buf.get() + o_ma) : nullptr;
+    const int* d_mb = member_b ? reinterpret_cast<const int*>(h->ep_buf.get() + o_mb) : nullptr;
+    double* d_r = reinterpret_cast<double*>(h->ep_buf.get() + o_r);
+    unsigned char* d_d = h->ep_buf.get() + o_d;
     SyncOnExit guard(h->stream);                              // params / member maps are the caller's
-    if (params) HIPCHK(hipMemcpyAsync(h->mlp_w, params, wbytes, hipMemcpyHostToDevice, h->stream));
-    if (member_a) HIPCHK(hipMemcpyAsync(h->ep_buf + o_ma, member_a, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    if (member_b) HIPCHK(hipMemcpyAsync(h->ep_buf + o_mb, member_b, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    if (params) HIPCHK(hipMemcpyAsync(h->mlp_w.get(), params, wbytes, hipMemcpyHostToDevice, h->stream));
+    if (member_a) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ma, member_a, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    if (member_b) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_mb, member_b, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
     // Small worlds with a quantised state and a quantised retained previous state: the rest of the chunk in ONE
     // launch, worlds in LDS (episode_mlp).  Until then - the first two steps of an episode, whose current /
     // previous state is the un-quantised upload - and for large worlds: one launch sequence per step.
@@ -1860,32 +1855,30 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
             const size_t Kr = K - t;
             p32.resize(Kr);
             for (size_t i = 0; i < Kr; ++i) p32[i] = derive_f32(p, L_schedule[t + i]);
-            HIPCHK(hipMemcpyAsync(h->ep_buf + o_p32, p32.data(), sizeof(PhysF32) * Kr, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->ep_buf + o_ls, L_schedule + t, sizeof(double) * Kr, hipMemcpyHostToDevice, h->stream));
-            StatsDev* stats = h->stats2[h->sp];
+            HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_p32, p32.data(), sizeof(PhysF32) * Kr, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ls, L_schedule + t, sizeof(double) * Kr, hipMemcpyHostToDevice, h->stream));
+            StatsDev* stats = h->stats2[h->sp].get();
             if (!wave_kernel) HIPCHK(hipMemsetAsync(stats, 0, sizeof(StatsDev) * (B + 1), h->stream));   // (the wave kernel assigns every record)
             EpisodeMlpIO io;
             const int cur = h->cur, prev = 1 - h->cur;
-            io.L = h->L16[cur]; io.D = h->D16[cur]; io.prevL = h->L16[prev]; io.prevD = h->D16[prev];
-            io.idx = h->idx; io.st = h->st;
-            io.P32 = reinterpret_cast<const PhysF32*>(h->ep_buf + o_p32);
-            io.Ls = reinterpret_cast<const double*>(h->ep_buf + o_ls);
+            io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
+            io.idx = h->idx.get(); io.st = h->st.get();
+            io.P32 = reinterpret_cast<const PhysF32*>(h->ep_buf.get() + o_p32);
+            io.Ls = reinterpret_cast<const double*>(h->ep_buf.get() + o_ls);
             io.weights = d_w; io.member_a = d_ma; io.member_b = d_mb;
             io.reward = d_r + t * bn; io.done = d_d + t * bn;
             io.stats = stats; io.fixups = &stats[B].sum_l;
-            io.action = h->action;
+            io.action = h->action.get();
             const bool ex = p.precision == DW_PRECISION_EXACT;
             if (wave_kernel) {
                 auto kern = ex ? episode_mlp_wave<true> : episode_mlp_wave<false>;
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds));
+                if (int rc = set_lds_limit(h, kern, lds)) return rc;
                 const EpisodeMlpWaveArgs A{io, B, N, p.height, p.width, (int)Kr, p.obs_mask, (int)split, p.agent_gamma,
                                            h->L_last, make_f64(p, L_schedule[t])};
                 hipLaunchKernelGGL(kern, dim3((unsigned)((B + 3) / 4)), dim3(256), lds, h->stream, A);
             } else {
                 auto kern = ex ? episode_mlp<true> : episode_mlp<false>;
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds));
+                if (int rc = set_lds_limit(h, kern, lds)) return rc;
                 hipLaunchKernelGGL(kern, dim3((unsigned)((B + wpb - 1) / wpb)), dim3(256), lds, h->stream, io, B, N, p.height,
                                    p.width, wpb, (int)Kr, p.obs_mask, p.agent_gamma, make_f64(p, L_schedule[t]), h->L_last,
                                    (int)split);
@@ -1900,10 +1893,10 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
         if (rc) return rc;
         // both halves in one launch (agents [split, N) read member_b), reward / done written by the grazing
         // kernel: 4 instead of 6 launches per step - the loop is bound by the host thread that issues them
-        hipLaunchKernelGGL(policy_mlp, dim3((unsigned)((bn + 3) / 4)), dim3(64), 0, h->stream, h->scratch, d_w, d_ma, B, N,
-                           0, N, h->action, d_mb, split);
+        hipLaunchKernelGGL(policy_mlp, dim3((unsigned)((bn + 3) / 4)), dim3(64), 0, h->stream, h->scratch.get(), d_w, d_ma, B, N,
+                           0, N, h->action.get(), d_mb, split);
         HIPCHK(hipGetLastError());
-        rc = launch_agents(h, h->action, B, N, false, d_r + t * bn, d_d + t * bn);
+        rc = launch_agents(h, h->action.get(), B, N, false, d_r + t * bn, d_d + t * bn);
         if (rc) return rc;
         rc = launch_forward(h, L_schedule[t]);
         if (rc) return rc;
@@ -1922,9 +1915,9 @@ int dw_lifespan_reset(dw_handle* h) {
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
     const size_t bn = (size_t)p.batch * (p.n_agents > 0 ? p.n_agents : 1);
-    HIPCHK(hipMemsetAsync(h->done_at, 0, sizeof(int) * p.batch, h->stream));
-    HIPCHK(hipMemsetAsync(h->agents_done_at, 0, sizeof(int) * bn, h->stream));
-    HIPCHK(hipMemsetAsync(h->n_alive, 0, sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->done_at.get(), 0, sizeof(int) * p.batch, h->stream));
+    HIPCHK(hipMemsetAsync(h->agents_done_at.get(), 0, sizeof(int) * bn, h->stream));
+    HIPCHK(hipMemsetAsync(h->n_alive.get(), 0, sizeof(int), h->stream));
     return DW_OK;
 }
 
@@ -1932,10 +1925,10 @@ int dw_lifespan_accumulate(dw_handle* h, uint32_t threshold_k) {
     NEED(h, DW_EINVAL, "null handle");
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
-    HIPCHK(hipMemsetAsync(h->n_alive, 0, sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->n_alive.get(), 0, sizeof(int), h->stream));
     const int n = p.batch * (p.n_agents > 0 ? p.n_agents : 1);
-    hipLaunchKernelGGL(lifespan_accumulate, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->stats2[h->sp], h->st, p.batch,
-                       p.n_agents, threshold_k, h->done_at, h->agents_done_at, h->n_alive);
+    hipLaunchKernelGGL(lifespan_accumulate, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->stats2[h->sp].get(), h->st.get(), p.batch,
+                       p.n_agents, threshold_k, h->done_at.get(), h->agents_done_at.get(), h->n_alive.get());
     HIPCHK(hipGetLastError());
     return DW_OK;
 }
@@ -1944,11 +1937,11 @@ int dw_lifespan_download(dw_handle* h, int32_t* done_at, int32_t* agents_done_at
     NEED(h, DW_EINVAL, "null handle");
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
-    if (done_at) HIPCHK(hipMemcpyAsync(done_at, h->done_at, sizeof(int) * p.batch, hipMemcpyDeviceToHost, h->stream));
+    if (done_at) HIPCHK(hipMemcpyAsync(done_at, h->done_at.get(), sizeof(int) * p.batch, hipMemcpyDeviceToHost, h->stream));
     if (agents_done_at && p.n_agents)
-        HIPCHK(hipMemcpyAsync(agents_done_at, h->agents_done_at, sizeof(int) * (size_t)p.batch * p.n_agents,
+        HIPCHK(hipMemcpyAsync(agents_done_at, h->agents_done_at.get(), sizeof(int) * (size_t)p.batch * p.n_agents,
                               hipMemcpyDeviceToHost, h->stream));
-    if (n_worlds_alive) HIPCHK(hipMemcpyAsync(n_worlds_alive, h->n_alive, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (n_worlds_alive) HIPCHK(hipMemcpyAsync(n_worlds_alive, h->n_alive.get(), sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return DW_OK;
 }
@@ -1981,7 +1974,7 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
     const size_t o_ps = up(o_code + bn), total = up(o_ps + sizeof(unsigned int) * 2 * B) + 256;
     if (int erc = ensure_ep_buf(h, total)) return erc;
     SyncOnExit guard(h->stream);                              // `table` is the caller's
-    if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
+    if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
     const int nflag = B > (int)bn ? B : (int)bn;
     // Step pairs on wide grids (dw_agents_fused.hpp): policy_t, graze_t, ONE fused launch for forward_t and
     // forward_{t+1}, then the agents' step t+1 recomputed around the agents and patched into the result.
@@ -1992,13 +1985,13 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
                           !h->sw.no_agent_fuse;
     // With per-step world flags the fused launch also reduces what the flags of both steps need (STATS
     // variants: exact step-1 maximum, count of certain step-2 values above the threshold).
-    unsigned int* pstats = world_alive ? reinterpret_cast<unsigned int*>(h->ep_buf + o_ps) : nullptr;
+    unsigned int* pstats = world_alive ? reinterpret_cast<unsigned int*>(h->ep_buf.get() + o_ps) : nullptr;
     // zeroed once: every agents_lookahead_patch launch leaves its world's words cleared for the next pair
     if (pstats && may_pair) HIPCHK(hipMemsetAsync(pstats, 0, sizeof(unsigned int) * 2 * B, h->stream));
     // action codes of a pair's second step when they come from no table: one byte value for the whole episode
     const int uniform_code = policy_mode == DW_POLICY_ZEROS ? 0 : (policy_mode == DW_POLICY_ARGMIN ? 0xFE : 0xFF);
     if (may_pair && policy_mode != DW_POLICY_TABLE)
-        HIPCHK(hipMemsetAsync(h->ep_buf + o_code, uniform_code, bn, h->stream));
+        HIPCHK(hipMemsetAsync(h->ep_buf.get() + o_code, uniform_code, bn, h->stream));
     auto greedy = [&](int argmin, int codes) { return launch_policy_greedy(h, argmin, nullptr, codes); };
     // policy + update_agents of the step after a pair run inside that pair's patch kernel (phase E) while the chunk
     // continues: two launches per pair instead of four (DW_NO_AGENT_PREAPPLY: experiments)
@@ -2012,16 +2005,16 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
             const bool from_table = policy_mode == DW_POLICY_TABLE || (use_table && use_table[t]);
             if (from_table) {
                 hipLaunchKernelGGL(actions_from_table, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, h->stream,
-                                   reinterpret_cast<const signed char*>(h->ep_buf + o_tab + t * bn), (int)bn, h->action);
+                                   reinterpret_cast<const signed char*>(h->ep_buf.get() + o_tab + t * bn), (int)bn, h->action.get());
                 if (int prc = greedy(0, 1)) return prc;                      // codes -1 / -2: greedy / anti-greedy
             } else if (policy_mode == DW_POLICY_ZEROS) {
-                HIPCHK(hipMemsetAsync(h->action, 0, sizeof(int) * bn, h->stream));
+                HIPCHK(hipMemsetAsync(h->action.get(), 0, sizeof(int) * bn, h->stream));
             } else {
                 if (int prc = greedy(policy_mode == DW_POLICY_ARGMIN ? 1 : 0, 0)) return prc;
             }
             HIPCHK(hipGetLastError());
             // a pair's first step: the agents' ok flags straight from the grazing kernel
-            int rc = launch_agents(h, h->action, B, N, false, nullptr, nullptr, pair ? h->ep_buf + o_ok + t * bn : nullptr);
+            int rc = launch_agents(h, h->action.get(), B, N, false, nullptr, nullptr, pair ? h->ep_buf.get() + o_ok + t * bn : nullptr);
             if (rc) return rc;
         }
         if (pair) {
@@ -2030,24 +2023,24 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
             if (rc) return rc;
             // codes of step t+1: the caller's table slice, or one byte value for the whole ensemble
             const bool tab2 = policy_mode == DW_POLICY_TABLE || (use_table && use_table[t + 1]);
-            unsigned char* codes = tab2 ? h->ep_buf + o_tab + (t + 1) * bn : h->ep_buf + o_code;
+            unsigned char* codes = tab2 ? h->ep_buf.get() + o_tab + (t + 1) * bn : h->ep_buf.get() + o_code;
             LookaheadArgs A;
-            A.inL = h->L16[1 - h->cur]; A.inD = h->D16[1 - h->cur];
-            A.outL = h->L16[h->cur]; A.outD = h->D16[h->cur];
-            A.idx = h->idx; A.st = h->st;
+            A.inL = h->L16[1 - h->cur].get(); A.inD = h->D16[1 - h->cur].get();
+            A.outL = h->L16[h->cur].get(); A.outD = h->D16[h->cur].get();
+            A.idx = h->idx.get(); A.st = h->st.get();
             A.code = reinterpret_cast<const signed char*>(codes);
-            A.agent_ok = h->ep_buf + o_ok + (t + 1) * bn;
+            A.agent_ok = h->ep_buf.get() + o_ok + (t + 1) * bn;
             A.code_next = nullptr;
             A.agent_ok_next = nullptr;
-            A.action_out = h->action;
+            A.action_out = h->action.get();
             if (t + 2 < K && !no_preapply) {                   // the chunk continues with step t+2
                 const bool tab3 = policy_mode == DW_POLICY_TABLE || (use_table && use_table[t + 2]);
-                A.code_next = reinterpret_cast<const signed char*>(tab3 ? h->ep_buf + o_tab + (t + 2) * bn : h->ep_buf + o_code);
-                A.agent_ok_next = h->ep_buf + o_ok + (t + 2) * bn;
+                A.code_next = reinterpret_cast<const signed char*>(tab3 ? h->ep_buf.get() + o_tab + (t + 2) * bn : h->ep_buf.get() + o_code);
+                A.agent_ok_next = h->ep_buf.get() + o_ok + (t + 2) * bn;
                 pre_applied = true;
             }
-            A.alive_t = pstats ? h->ep_buf + o_wa + t * B : nullptr;
-            A.alive_t1 = pstats ? h->ep_buf + o_wa + (t + 1) * B : nullptr;
+            A.alive_t = pstats ? h->ep_buf.get() + o_wa + t * B : nullptr;
+            A.alive_t1 = pstats ? h->ep_buf.get() + o_wa + (t + 1) * B : nullptr;
             A.pstats = pstats; A.thr = threshold_k;
             A.B = B; A.N = N; A.H = p.height; A.W = p.width; A.mask = p.obs_mask;
             A.agent_gamma = p.agent_gamma;
@@ -2064,11 +2057,11 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
         int rc = launch_forward(h, L_schedule[t]);
         if (rc) return rc;
         hipLaunchKernelGGL(episode_flags, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, h->stream,
-                           h->stats2[h->sp], h->st, B, N, threshold_k, h->ep_buf + o_wa + t * B, h->ep_buf + o_ok + t * bn);
+                           h->stats2[h->sp].get(), h->st.get(), B, N, threshold_k, h->ep_buf.get() + o_wa + t * B, h->ep_buf.get() + o_ok + t * bn);
         HIPCHK(hipGetLastError());
     }
-    if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf + o_wa, K * B, hipMemcpyDeviceToHost, h->stream));
-    if (agent_ok && bn) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
+    if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * B, hipMemcpyDeviceToHost, h->stream));
+    if (agent_ok && bn) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     guard.disarm();
     return DW_OK;
@@ -2108,21 +2101,15 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     // in ONE copy (round 3: four pageable uploads, a memset and two pageable downloads per chunk - 88 us of host time
     // per 64-step chunk of 1000 8x8 worlds against 116 us of kernel).  Beyond 64 MiB: straight from / to the caller's arrays.
     const bool staged = total <= ((size_t)64 << 20);
-    if (staged && h->ep_pinned_bytes < total) {
-        if (h->ep_pinned) HIPCHK(hipHostFree(h->ep_pinned));
-        h->ep_pinned = nullptr; h->ep_pinned_bytes = 0;
-        size_t want = h->ep_pinned_bytes ? h->ep_pinned_bytes * 2 : ((size_t)1 << 20);
-        if (want < total) want = total;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->ep_pinned), want, hipHostMallocDefault));
-        h->ep_pinned_bytes = want;
-    }
+    if (staged)
+        if (int rc = reserve(h->ep_pinned, "the page-locked episode staging", total, (size_t)1 << 20)) return rc;
     std::vector<PhysF32> p32_own;
     std::vector<unsigned char> ut_own;
     PhysF32* p32 = nullptr;
     unsigned char* ut = nullptr;
     if (staged) {
-        p32 = reinterpret_cast<PhysF32*>(h->ep_pinned + o_p32);
-        ut = h->ep_pinned + o_ut;
+        p32 = reinterpret_cast<PhysF32*>(h->ep_pinned.get() + o_p32);
+        ut = h->ep_pinned.get() + o_ut;
     } else {
         p32_own.resize(K); ut_own.resize(K);
         p32 = p32_own.data(); ut = ut_own.data();
@@ -2131,49 +2118,45 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     if (use_table) std::memcpy(ut, use_table, K); else std::memset(ut, 0, K);
     SyncOnExit guard(h->stream);                              // the images above and the caller's arrays
     if (staged) {
-        std::memcpy(h->ep_pinned + o_ls, L_schedule, sizeof(double) * K);
-        if (table && bn) std::memcpy(h->ep_pinned + o_tab, table, K * bn);
-        HIPCHK(hipMemcpyAsync(h->ep_buf, h->ep_pinned, (table && bn) ? o_tab + K * bn : o_ut + K, hipMemcpyHostToDevice, h->stream));
+        std::memcpy(h->ep_pinned.get() + o_ls, L_schedule, sizeof(double) * K);
+        if (table && bn) std::memcpy(h->ep_pinned.get() + o_tab, table, K * bn);
+        HIPCHK(hipMemcpyAsync(h->ep_buf.get(), h->ep_pinned.get(), (table && bn) ? o_tab + K * bn : o_ut + K, hipMemcpyHostToDevice, h->stream));
     } else {
-        HIPCHK(hipMemcpyAsync(h->ep_buf + o_p32, p32, sizeof(PhysF32) * K, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->ep_buf + o_ls, L_schedule, sizeof(double) * K, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->ep_buf + o_ut, ut, K, hipMemcpyHostToDevice, h->stream));
-        if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_p32, p32, sizeof(PhysF32) * K, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ls, L_schedule, sizeof(double) * K, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ut, ut, K, hipMemcpyHostToDevice, h->stream));
+        if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
     }
-    StatsDev* stats = h->stats2[h->sp];
+    StatsDev* stats = h->stats2[h->sp].get();
     // episode_wave ASSIGNS every world's whole record (its float64 count in `reserved`) and the counter record behind them:
     // nothing to clear; episode_small accumulates: cleared as before
     if (!wave_kernel) HIPCHK(hipMemsetAsync(stats, 0, sizeof(StatsDev) * (B + 1), h->stream));
     EpisodeIO io;
     const int cur = h->cur, prev = 1 - h->cur;
-    io.L = h->L16[cur]; io.D = h->D16[cur]; io.prevL = h->L16[prev]; io.prevD = h->D16[prev];
-    io.idx = h->idx; io.st = h->st;
-    io.P32 = reinterpret_cast<const PhysF32*>(h->ep_buf + o_p32);
-    io.Ls = reinterpret_cast<const double*>(h->ep_buf + o_ls);
-    io.use_table = h->ep_buf + o_ut;
-    io.table = reinterpret_cast<const signed char*>(h->ep_buf + o_tab);
-    io.world_alive = h->ep_buf + o_wa;
-    io.agent_ok = h->ep_buf + o_ok;
+    io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
+    io.idx = h->idx.get(); io.st = h->st.get();
+    io.P32 = reinterpret_cast<const PhysF32*>(h->ep_buf.get() + o_p32);
+    io.Ls = reinterpret_cast<const double*>(h->ep_buf.get() + o_ls);
+    io.use_table = h->ep_buf.get() + o_ut;
+    io.table = reinterpret_cast<const signed char*>(h->ep_buf.get() + o_tab);
+    io.world_alive = h->ep_buf.get() + o_wa;
+    io.agent_ok = h->ep_buf.get() + o_ok;
     io.stats = stats;
     io.fixups = &stats[B].sum_l;
-    io.action = (N > 0 && policy_mode != kPolicySkipAgents) ? h->action : nullptr;
+    io.action = (N > 0 && policy_mode != kPolicySkipAgents) ? h->action.get() : nullptr;
     const PhysF64 P64 = make_f64(p, L_schedule[0]);
     const dim3 grid((unsigned)((B + wpb - 1) / wpb));
     const bool ex = p.precision == DW_PRECISION_EXACT;
     if (wave_kernel) {
-        io.use_table = use_table ? h->ep_buf + o_ut : nullptr;
+        io.use_table = use_table ? h->ep_buf.get() + o_ut : nullptr;
         io.table = (table && bn) ? io.table : nullptr;
         auto kern = ex ? episode_wave<true> : episode_wave<false>;
-        static size_t lds_set[2] = {0, 0};                      // the attribute only ever has to grow
-        if (lds_set[ex] < lds) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_set[ex] = lds;
-        }
+        if (int rc = set_lds_limit(h, kern, lds)) return rc;
         const EpisodeWaveArgs A{io, B, N, p.height, p.width, nsteps, policy_mode, p.obs_mask, threshold_k, p.agent_gamma, P64};
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, h->stream, A);
     } else {
         auto kern = ex ? episode_small<true> : episode_small<false>;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (int rc = set_lds_limit(h, kern, lds)) return rc;
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, h->stream, io, B, N, p.height, p.width, wpb, nsteps, policy_mode,
                            p.obs_mask, p.agent_gamma, threshold_k, P64);
     }
@@ -2182,11 +2165,11 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     if (staged) {
         if (world_alive || want_ok) {
             const size_t lo = world_alive ? o_wa : o_ok, hi = want_ok ? o_ok + K * bn : o_wa + K * B;
-            HIPCHK(hipMemcpyAsync(h->ep_pinned + lo, h->ep_buf + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(h->ep_pinned.get() + lo, h->ep_buf.get() + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
         }
     } else {
-        if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf + o_wa, K * B, hipMemcpyDeviceToHost, h->stream));
-        if (want_ok) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
+        if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * B, hipMemcpyDeviceToHost, h->stream));
+        if (want_ok) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
     }
     h->unq = OWN_NONE;
     h->stepped = true;
@@ -2195,8 +2178,8 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     HIPCHK(hipStreamSynchronize(h->stream));      // flags are returned
     guard.disarm();
     if (staged) {
-        if (world_alive) std::memcpy(world_alive, h->ep_pinned + o_wa, K * B);
-        if (want_ok) std::memcpy(agent_ok, h->ep_pinned + o_ok, K * bn);
+        if (world_alive) std::memcpy(world_alive, h->ep_pinned.get() + o_wa, K * B);
+        if (want_ok) std::memcpy(agent_ok, h->ep_pinned.get() + o_ok, K * bn);
     }
     return DW_OK;
 }
@@ -2214,7 +2197,7 @@ __global__ __launch_bounds__(256) void copy_regions(CopyJobs J) {
     const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     for (int j = 0; j < J.n; ++j) {
         const size_t nb = J.bytes[j];
-        // (every region starts at a hipMalloc'ed address: 256-byte aligned)
+        // (every region starts at the start of a device allocation: 256-byte aligned)
         const uint4* s16 = static_cast<const uint4*>(J.src[j]);
         uint4* d16 = static_cast<uint4*>(J.dst[j]);
         for (size_t i = t0; i < nb / 16; i += stride) d16[i] = s16[i];
@@ -2226,6 +2209,7 @@ __global__ __launch_bounds__(256) void copy_regions(CopyJobs J) {
 static int launch_copy_regions(dw_handle* h, const CopyJobs& J) {
     size_t most = 0;
     for (int j = 0; j < J.n; ++j) {
+        NEED(J.src[j] && J.dst[j], DW_EINVAL, "snapshot region not allocated");
         NEED(((reinterpret_cast<uintptr_t>(J.src[j]) | reinterpret_cast<uintptr_t>(J.dst[j])) & 15) == 0, DW_EINVAL,
              "snapshot region not 16-byte aligned");
         most = J.bytes[j] > most ? J.bytes[j] : most;
@@ -2246,44 +2230,39 @@ int dw_snapshot_save_slot(dw_handle* h, int32_t slot) {
     NEED(h->have_state, DW_ESTATE, "no state uploaded");
     NEED(cur_quantised(h), DW_ESTATE, "the current state is an un-quantised upload; take a step first");
     dw_handle::Snapshot& sn = h->snap[slot];
+    sn.valid = false;                           // until the copy below is queued
     const size_t bn = (size_t)p.batch * p.n_agents;
     const size_t pb = sizeof(plane_t) * h->cells;
-    if (!sn.L) {
-        HIPCHK(hipMalloc(&sn.L, pb));
-        HIPCHK(hipMalloc(&sn.D, pb));
-        HIPCHK(hipMalloc(&sn.stats, h->stats_bytes));
-        if (bn) {
-            HIPCHK(hipMalloc(&sn.idx, sizeof(int) * 2 * bn));
-            HIPCHK(hipMalloc(&sn.st, sizeof(double) * bn));
-        }
-    }
-    CopyJobs J;
-    J.n = 0;
-    auto job = [&J](void* dst, const void* src, size_t bytes) { J.dst[J.n] = dst; J.src[J.n] = src; J.bytes[J.n] = bytes; ++J.n; };
-    job(sn.L, h->L16[h->cur], pb);
-    job(sn.D, h->D16[h->cur], pb);
-    job(sn.stats, h->stats2[h->sp], h->stats_bytes);
+    const int rc = bn ? alloc_group(h, "a snapshot", {{sn.L, pb}, {sn.D, pb}, {sn.stats, h->stats_bytes},
+                                                      {sn.idx, sizeof(int) * 2 * bn}, {sn.st, sizeof(double) * bn}})
+                      : alloc_group(h, "a snapshot", {{sn.L, pb}, {sn.D, pb}, {sn.stats, h->stats_bytes}});
+    if (rc) return rc;
     // the previous state too: observations (temperature channels) and the temp / beta / growth caches are
     // derived from it, so a replay from the snapshot must see the same one.  An un-quantised previous state
     // (the step after an upload) stays where it is: its buffers are not reused before the next upload, which
     // invalidates the snapshot.
+    const bool keep_prev = h->stepped && h->unq != OWN_PREV;
+    if (keep_prev)
+        if (int prc = alloc_group(h, "a snapshot's previous state", {{sn.PL, pb}, {sn.PD, pb}})) return prc;
+    CopyJobs J;
+    J.n = 0;
+    auto job = [&J](void* dst, const void* src, size_t bytes) { J.dst[J.n] = dst; J.src[J.n] = src; J.bytes[J.n] = bytes; ++J.n; };
+    job(sn.L.get(), h->L16[h->cur].get(), pb);
+    job(sn.D.get(), h->D16[h->cur].get(), pb);
+    job(sn.stats.get(), h->stats2[h->sp].get(), h->stats_bytes);
+    if (keep_prev) {
+        job(sn.PL.get(), h->L16[1 - h->cur].get(), pb);
+        job(sn.PD.get(), h->D16[1 - h->cur].get(), pb);
+    }
     sn.stepped = h->stepped;
     sn.L_last = h->L_last;
     sn.unq = h->unq;
-    if (h->stepped && h->unq != OWN_PREV) {
-        if (!sn.PL) {
-            HIPCHK(hipMalloc(&sn.PL, pb));
-            HIPCHK(hipMalloc(&sn.PD, pb));
-        }
-        job(sn.PL, h->L16[1 - h->cur], pb);
-        job(sn.PD, h->D16[1 - h->cur], pb);
-    }
     sn.agents = bn && h->have_agents;
     if (sn.agents) {
-        job(sn.idx, h->idx, sizeof(int) * 2 * bn);
-        job(sn.st, h->st, sizeof(double) * bn);
+        job(sn.idx.get(), h->idx.get(), sizeof(int) * 2 * bn);
+        job(sn.st.get(), h->st.get(), sizeof(double) * bn);
     }
-    if (int rc = launch_copy_regions(h, J)) return rc;
+    if (int crc = launch_copy_regions(h, J)) return crc;
     sn.valid = true;
     return DW_OK;
 }
@@ -2300,19 +2279,19 @@ int dw_snapshot_restore_slot(dw_handle* h, int32_t slot) {
     CopyJobs J;
     J.n = 0;
     auto job = [&J](void* dst, const void* src, size_t bytes) { J.dst[J.n] = dst; J.src[J.n] = src; J.bytes[J.n] = bytes; ++J.n; };
-    job(h->L16[h->cur], sn.L, pb);
-    job(h->D16[h->cur], sn.D, pb);
-    job(h->stats2[h->sp], sn.stats, h->stats_bytes);
+    job(h->L16[h->cur].get(), sn.L.get(), pb);
+    job(h->D16[h->cur].get(), sn.D.get(), pb);
+    job(h->stats2[h->sp].get(), sn.stats.get(), h->stats_bytes);
     if (sn.agents) {
-        job(h->idx, sn.idx, sizeof(int) * 2 * bn);
-        job(h->st, sn.st, sizeof(double) * bn);
+        job(h->idx.get(), sn.idx.get(), sizeof(int) * 2 * bn);
+        job(h->st.get(), sn.st.get(), sizeof(double) * bn);
     }
     if (sn.stepped && sn.unq != OWN_PREV) {
-        job(h->L16[1 - h->cur], sn.PL, pb);
-        job(h->D16[1 - h->cur], sn.PD, pb);
+        job(h->L16[1 - h->cur].get(), sn.PL.get(), pb);
+        job(h->D16[1 - h->cur].get(), sn.PD.get(), pb);
     }
     if (int rc = launch_copy_regions(h, J)) return rc;
-    HIPCHK(hipMemsetAsync(h->stats2[1 - h->sp], 0, h->stats_bytes, h->stream));
+    HIPCHK(hipMemsetAsync(h->stats2[1 - h->sp].get(), 0, h->stats_bytes, h->stream));
     h->unq = sn.unq;                            // OWN_PREV: the un-quantised initial state is still in its buffers
     h->stepped = sn.stepped;
     h->L_last = sn.L_last;
@@ -2363,8 +2342,8 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark) {
     const int buf = which == DW_STATE_CURRENT ? h->cur : 1 - h->cur;
     NEED(which != DW_STATE_CURRENT || cur_quantised(h), DW_ESTATE,
          "the current state is an un-quantised upload: it has no binary16 planes before the first step");
-    *light = h->L16[buf];
-    *dark = h->D16[buf];
+    *light = h->L16[buf].get();
+    *dark = h->D16[buf].get();
     return DW_OK;
 }
 
@@ -2411,10 +2390,10 @@ int dw_audit_tie_bound(dw_handle* h, double L, double out[4]) {
     NEED(h->have_state && cur_quantised(h), DW_ESTATE, "the audit needs a quantised current state");
     int rc = ensure_scratch(h, 4 * sizeof(unsigned long long));
     if (rc) return rc;
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(h->scratch);
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(h->scratch.get());
     HIPCHK(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), h->stream));
     const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
-    hipLaunchKernelGGL(tie_audit, g, dim3(256), 0, h->stream, h->L16[h->cur], h->D16[h->cur], p.height, p.width,
+    hipLaunchKernelGGL(tie_audit, g, dim3(256), 0, h->stream, h->L16[h->cur].get(), h->D16[h->cur].get(), p.height, p.width,
                        derive_f32(p, L), make_f64(p, L), d, h->sym_albedo && h->use_stream ? 1 : 0);
     HIPCHK(hipGetLastError());
     unsigned long long r[4];
@@ -2433,7 +2412,7 @@ int dw_last_fixup_count(dw_handle* h, uint64_t* count) {
     // the counter behind the per-world records + the per-world counts of the one-wave-per-world episode kernels (`reserved`:
     // zero after every other kernel - the step kernels clear the whole buffer for the step after them)
     std::vector<StatsDev> st((size_t)h->prm.batch + 1);
-    HIPCHK(hipMemcpyAsync(st.data(), h->stats2[h->sp], sizeof(StatsDev) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(st.data(), h->stats2[h->sp].get(), sizeof(StatsDev) * st.size(), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     unsigned long long v = st[h->prm.batch].sum_l;
     for (int b = 0; b < h->prm.batch; ++b) v += st[b].reserved;

@@ -177,15 +177,17 @@ class RLDaisyWorld:
             return self._engine                              # nothing changed since the last push
         shape = (int(self.batch_size), int(self.dim), int(self.n_agents), int(self.device))
         p = self._params()
-        self._pushed_key = key
+        # the key and shape are recorded only once the handle took them: after a failure the next call tries again
         if self._engine is None or shape != self._shape:
             if self._engine is not None:
                 self._engine.close()
+                self._engine = None
             self._engine = Engine(p)
             self._shape = shape
             self._agents_on_device = False
         else:
             self._engine.set_params(p)
+        self._pushed_key = key
         return self._engine
 
     def _sync_to_device(self):
