@@ -14,6 +14,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/daisyworld_hip.h"
@@ -100,6 +101,29 @@ static Switches read_switches() {
     return w;
 }
 
+// Which kernels take the steps, and their launch geometry: a pure function of the parameters and the switches
+// (plan_steps), computed when a handle is created or its parameters change and committed together with them.
+enum StepKind { STEP_GENERIC, STEP_TILED, STEP_STREAM };
+struct StepPlan {
+    StepKind kind = STEP_GENERIC;     // the step from a quantised state (DW_PRECISION_F64: always generic)
+    int halo = 0;                     // wave-strip halo form of the single-step kernels, first step included (halo_form)
+    bool packed = false;              // STEP_STREAM with W < 256: several worlds side by side in a wave row
+    bool allow_fuse = false;          // STEP_STREAM only: dw_step_n / dw_run_episode fuse pairs of steps ...
+    int fused_mode = kFusedOvl;       // ... with this strip layout (packed worlds: kFusedRot)
+    bool sym_albedo = false;          // a_dark - a_bare == -(a_light - a_bare) exactly: the exact wave-strip kernels use
+                                      // the two-term coefficient chain (growth_t<.., SYM>)
+    int tcq = 0, rpt = 0;             // STEP_TILED: tile columns (quads) and rows per thread
+    Geom geom{};
+    size_t tile_lds = 0;
+    StripGeom sgeom{};                // STEP_STREAM
+    FusedGeom fgeom{};
+    int first_prec = 2;               // the first step from an un-quantised state: PREC of step_generic /
+                                      // step_first_stream (1 float32, 2 float64, 3 float32 with the tie bound) ...
+    bool first_stream = false;        // ... in the wave-strip form (step_first_stream)
+    FirstGeom first_geom{};
+    bool need_fixq = false;           // exact tiled steps: the global near-tie queues
+};
+
 // The handle owns its buffers (dw_host_util.hpp): device memory, and page-locked host memory for the staging images.
 // DW_TEST_FAIL_GROUP_ALLOC=<n> (tests, under DW_TEST_HOOKS; process-wide countdown, read when a group is first allocated
 // while it is set): the last allocation of each of the next n groups (alloc_group) fails with out-of-memory.  Groups
@@ -151,15 +175,8 @@ struct dw_handle {
     DevBuf<uint4> fixq;               // exact mode: global near-tie queues [kNumQueues][qcap][3]
     unsigned int qcap = 0;
     DevBuf<int> redo_tiles;           // exact mode: tiles to recompute whole (queue overflow)
-    // streaming kernel (W >= 256)
-    bool use_stream = false;
     Switches sw{};                    // experiment / test switches as they were when the handle was created
-    StripGeom sgeom{};
-    bool allow_fuse = false;          // wide grids: dw_step_n / dw_run_episode fuse pairs of steps
-    bool fused_ring = false;          // W == 1024: the four waves of a workgroup form a ring over the torus row
-    bool sym_albedo = false;          // a_dark - a_bare == -(a_light - a_bare) exactly: the exact wave-strip kernels use
-                                      // the two-term coefficient chain (growth_t<.., SYM>)
-    FusedGeom fgeom{};
+    StepPlan plan{};                  // kernel selection for `prm`
     DevBuf<int> done_at;              // [B]
     DevBuf<int> agents_done_at;       // [B][N]
     DevBuf<int> n_alive;
@@ -190,15 +207,55 @@ struct dw_handle {
         DevBuf<unsigned char> stats;
         bool valid = false, agents = false;
     } snap[DW_SNAPSHOT_SLOTS];
-    // kernel selection
-    int tcq = 0, rpt = 0;             // 0 => generic
-    Geom geom{};
-    size_t tile_lds = 0;
     std::vector<std::pair<const void*, size_t>> lds_limit;   // set_lds_limit: kernel -> dynamic LDS limit set
     bool created = false;             // dw_create has returned it (DW_TEST_FAIL_GROUP_ALLOC counts from then on)
 };
 
 static inline bool cur_quantised(const dw_handle* h) { return h->unq != OWN_CUR; }
+
+// ------------------------------------------------------------------------------------------------
+// runtime values -> template arguments.  Each helper instantiates `f` for every value it lists, so it is used only
+// where every one of those kernel instantiations is meant to exist.  The helpers, and the launch templates and
+// lambdas that use them, deduce their return types: they are instantiated where they are called, so the kernels are
+// instantiated - and laid out in the code object - in the order the launch code names them.
+// ------------------------------------------------------------------------------------------------
+template <int V> using int_c = std::integral_constant<int, V>;
+
+// f(int_c<v>{}) for v among the listed values (the last one takes any other value: the callers pass listed ones only)
+template <int V, int... Vs, class F>
+static decltype(auto) with_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(int_c<V>{});
+    else return v == V ? f(int_c<V>{}) : with_int<Vs...>(v, f);
+}
+
+template <class F>
+static decltype(auto) with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// element type of a plane pointer handed out by with_planes
+template <class P> using elem_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+
+// f(light, dark) with the un-quantised state's typed pointers: float64 natural units or float32 per-mille
+template <class F>
+static decltype(auto) with_unq_planes(const dw_handle* h, F&& f) {
+    return h->unq_kind == UNQ_F64 ? f(h->L64.get(), h->D64.get()) : f(h->U32L.get(), h->U32D.get());
+}
+
+// ... or, unless `unq`, with the binary16 planes of buffer `buf`
+template <class F>
+static decltype(auto) with_planes(const dw_handle* h, bool unq, int buf, F&& f) {
+    return unq ? with_unq_planes(h, f) : f(h->L16[buf].get(), h->D16[buf].get());
+}
+
+// The state observations and the materialised grid derive their temperature channels from: after a step the
+// PRE-step state (POST = true), before any step the current one (POST = false).  f(light, dark, POST) with the planes in
+// that state's format and POST a bool constant.
+template <class F>
+static auto with_derived_from(const dw_handle* h, F&& f) {
+    const bool post = h->stepped;
+    return with_planes(h, h->unq == (post ? OWN_PREV : OWN_CUR), post ? 1 - h->cur : h->cur, [&](auto* L, auto* D) {
+        return with_bool(post, [&](auto POST) { return f(L, D, POST); });
+    });
+}
 
 // Asynchronous copies FROM host memory (the caller's arrays, local vectors) must have finished before that
 // memory can go away: a function that issues them declares one of these right after the host buffers, so that
@@ -514,118 +571,122 @@ static FirstStepBound derive_first_bound(const dw_params& p, double L, const Phy
 // ------------------------------------------------------------------------------------------------
 // kernel selection
 // ------------------------------------------------------------------------------------------------
-// strip counts / grid sizes of the wave-strip kernels for strips of `sr` rows
-static void set_strip_rows(dw_handle* h, int sr) {
-    const dw_params& p = h->prm;
-    StripGeom& g = h->sgeom;
-    FusedGeom& f = h->fgeom;
-    const bool packed = g.wpr > 1 || p.width < 256;
-    const long groups = packed ? (p.batch + g.wpr - 1) / g.wpr : p.batch;
-    g.SR = f.SR = p.height < sr ? p.height : sr;
-    g.nrs = f.nrs = (p.height + g.SR - 1) / g.SR;
-    g.nstrips = (int)(groups * g.nrs * g.ncs);
-    g.nwg = (g.nstrips + 3) / 4;
-    g.chunk = (g.nwg + 7) / 8;
-    f.nstrips = (int)(groups * f.nrs * f.ncs);
-    f.nwg = h->fused_ring ? f.nstrips : (f.nstrips + 3) / 4;
-    f.chunk = (f.nwg + 7) / 8;
+// Halo form of the wave-strip single-step kernels (HALO of step_stream_* and step_first_stream): 0 W == 256 (rotate),
+// 1 another multiple of 256, 2 any other W >= 256, 3 packed worlds (W < 256)
+static int halo_form(int W) { return W < 256 ? 3 : (W == 256 ? 0 : (W % 256 == 0 ? 1 : 2)); }
+
+// Rows per wave-strip: 64 (3 % halo re-reads) when `groups` columns of strips then make at least `target` strips; shorter
+// strips for smaller jobs - a strip is a serial march of ~0.8 us per row, so with few strips the launch takes as long as
+// ONE strip and most SIMDs idle.  Never more than the grid's height.
+static int strip_rows(long groups, int H, long target) {
+    int sr = 64;
+    while (sr > 8 && groups * ((H + sr - 1) / sr) < target) sr >>= 1;
+    return H < sr ? H : sr;
 }
 
-// Packed mode of the wave-strip kernels: narrow worlds whose width divides 256 sit side by side in one 256-column wave
-// row (256/W worlds per wave) - only for ensembles with enough wave-strips to occupy the GPU: a lone strip is a serial
-// march down 64 rows, ~50 us, where the tiled kernel answers in ~9 us; DW_PACK_MIN_STRIPS overrides for tests.
-// Any width below 256 that is a multiple of 4, provided at least 70 % of the 64 lanes get columns (W = 96: 2 worlds on
-// 48 lanes; W = 132: one world on 33 lanes - left to the tiled kernel).  Returns the worlds per wave row, 0 if unpacked.
-static int packed_worlds_per_row(const dw_handle* h, const dw_params& p) {
-    const int pack_min_strips = h->sw.pack_min_strips >= 0 ? h->sw.pack_min_strips : 512;
-    const int pk_lpw = p.width / 4, pk_wpr = pk_lpw ? 64 / pk_lpw : 0;
-    const bool pack_shape = p.width >= 8 && p.width < 256 && pk_wpr >= 1 && pk_wpr * pk_lpw * 10 >= 64 * 7 &&
-                            !h->sw.no_pack;
-    const long pack_strips = pack_shape ? (long)((p.batch + pk_wpr - 1) / pk_wpr) * ((p.height + 63) / 64) : 0;
-    return pack_shape && pack_strips >= pack_min_strips ? pk_wpr : 0;
-}
-
-// the wave-strip (streaming) kernels take the step: W >= 256 or a packed ensemble, unless DW_KERNEL=tiled (A/B experiments)
-static bool picks_stream(const dw_handle* h, const dw_params& p) {
-    if (p.precision == DW_PRECISION_F64 || p.width % 4 != 0) return false;
-    const bool force_tiled = std::strcmp(h->sw.kernel, "tiled") == 0;
-    return (p.width >= 256 || packed_worlds_per_row(h, p) > 0) && !force_tiled;
-}
-
-static void select_kernel(dw_handle* h) {
-    const dw_params& p = h->prm;
-    h->tcq = 0;
-    h->rpt = 0;
-    h->use_stream = false;
-    h->allow_fuse = false;
-    h->sym_albedo = (p.albedo_dark - p.albedo_bare) == -(p.albedo_light - p.albedo_bare) && !h->sw.no_sym;
-    if (p.precision == DW_PRECISION_F64) return;
-    if (p.width % 4 != 0) return;
-    const int Wq = p.width / 4;
-    const int pk_wpr = packed_worlds_per_row(h, p);
-    const bool packable = pk_wpr > 0;
-    if (picks_stream(h, p)) {
-        h->use_stream = true;
-        StripGeom& g = h->sgeom;
+static StepPlan plan_steps(const dw_params& p, const Switches& sw) {
+    StepPlan s;
+    s.sym_albedo = (p.albedo_dark - p.albedo_bare) == -(p.albedo_light - p.albedo_bare) && !sw.no_sym;
+    s.halo = halo_form(p.width);
+    // Packed mode of the wave-strip kernels: narrow worlds whose width divides 256 sit side by side in one 256-column wave
+    // row (256/W worlds per wave) - only for ensembles with enough wave-strips to occupy the GPU: a lone strip is a serial
+    // march down 64 rows, ~50 us, where the tiled kernel answers in ~9 us; DW_PACK_MIN_STRIPS overrides for tests.
+    // Any width below 256 that is a multiple of 4, provided at least 70 % of the 64 lanes get columns (W = 96: 2 worlds on
+    // 48 lanes; W = 132: one world on 33 lanes - left to the tiled kernel).
+    const int lpw = p.width / 4, wpr = lpw ? 64 / lpw : 0;
+    const bool pack_shape = p.width >= 8 && p.width < 256 && wpr >= 1 && wpr * lpw * 10 >= 64 * 7 && !sw.no_pack;
+    const long pack_strips = pack_shape ? (long)((p.batch + wpr - 1) / wpr) * ((p.height + 63) / 64) : 0;
+    const bool packable = pack_shape && pack_strips >= (sw.pack_min_strips >= 0 ? sw.pack_min_strips : 512);
+    const bool quads = p.precision != DW_PRECISION_F64 && p.width % 4 == 0;
+    // the wave-strip kernels take the step: W >= 256 or a packed ensemble, unless DW_KERNEL=tiled (A/B experiments)
+    if (quads && (p.width >= 256 || packable) && std::strcmp(sw.kernel, "tiled") != 0) {
+        s.kind = STEP_STREAM;
+        s.packed = p.width < 256;
+        StripGeom& g = s.sgeom;
         g.B = p.batch; g.H = p.height; g.W = p.width;
         g.ncs = (p.width + 255) / 256;
-        g.lpw = packable ? p.width / 4 : 64;
-        g.wpr = packable ? pk_wpr : 1;
-        // Strip height: 64 rows (3 % halo re-reads) when that already gives every SIMD two strips; shorter
-        // strips for smaller jobs - a strip is a serial march of ~0.8 us per row, so with few strips the
-        // launch takes as long as ONE strip and most SIMDs idle.  DW_STRIP_ROWS overrides (experiments).
-        {
-            const long groups = (long)(packable ? (p.batch + g.wpr - 1) / g.wpr : p.batch) * g.ncs;
-            int sr = 64;
-            while (sr > 8 && groups * ((p.height + sr - 1) / sr) < 2048) sr >>= 1;    // two strips per SIMD
-            if (h->sw.strip_rows >= 1) sr = h->sw.strip_rows;
-            g.SR = p.height < sr ? p.height : sr;
-        }
+        g.lpw = s.packed ? lpw : 64;
+        g.wpr = s.packed ? wpr : 1;
+        const long groups = s.packed ? (p.batch + wpr - 1) / wpr : p.batch;
+        // two strips per SIMD; DW_STRIP_ROWS overrides (experiments)
+        g.SR = sw.strip_rows >= 1 ? (p.height < sw.strip_rows ? p.height : sw.strip_rows)
+                                  : strip_rows(groups * g.ncs, p.height, 2048);
+        g.nrs = (p.height + g.SR - 1) / g.SR;
+        g.nstrips = (int)(groups * g.nrs * g.ncs);
+        g.nwg = (g.nstrips + 3) / 4;
+        g.chunk = (g.nwg + 7) / 8;
         g.qcap = kWaveQueueCap;
         int mcap = kMismatchCap;
-        if (h->sw.queue_cap >= 0 && h->sw.queue_cap < kWaveQueueCap) g.qcap = h->sw.queue_cap;   // tests: force the overflow fallbacks
-        if (h->sw.mismatch_cap >= 0 && h->sw.mismatch_cap < kMismatchCap) mcap = h->sw.mismatch_cap;
-        g.force_rescan = h->sw.force_rescan ? 1 : 0;            // tests: the strip maximum's re-scan path
-        h->allow_fuse = !h->sw.no_fuse;
-        FusedGeom& f = h->fgeom;
-        f.B = p.batch; f.H = p.height; f.W = p.width;
-        f.SR = g.SR;
-        f.lpw = g.lpw; f.wpr = g.wpr;
+        if (sw.queue_cap >= 0 && sw.queue_cap < kWaveQueueCap) g.qcap = sw.queue_cap;   // tests: force the overflow fallbacks
+        if (sw.mismatch_cap >= 0 && sw.mismatch_cap < kMismatchCap) mcap = sw.mismatch_cap;
+        g.force_rescan = sw.force_rescan ? 1 : 0;               // tests: the strip maximum's re-scan path
+        s.allow_fuse = !sw.no_fuse;
         // W == 1024: one WORKGROUP per row strip, its four waves side by side (edge columns through LDS) instead of
         // five overlapped 248-column strips (DW_NO_RING: experiments)
-        h->fused_ring = p.width == 1024 && !h->sw.no_ring;
-        f.cols_per_strip = p.width <= 256 ? 256 : (h->fused_ring ? 1024 : 248);
-        f.ncs = packable ? 1 : (p.width + f.cols_per_strip - 1) / f.cols_per_strip;
+        const bool ring = p.width == 1024 && !sw.no_ring;
+        s.fused_mode = p.width <= 256 ? kFusedRot : (ring ? kFusedRing : kFusedOvl);
+        FusedGeom& f = s.fgeom;
+        f.B = p.batch; f.H = p.height; f.W = p.width;
+        f.SR = g.SR;
+        f.nrs = g.nrs;
+        f.lpw = g.lpw; f.wpr = g.wpr;
+        f.cols_per_strip = p.width <= 256 ? 256 : (ring ? 1024 : 248);
+        f.ncs = s.packed ? 1 : (p.width + f.cols_per_strip - 1) / f.cols_per_strip;
+        f.nstrips = (int)(groups * f.nrs * f.ncs);
+        f.nwg = ring ? f.nstrips : (f.nstrips + 3) / 4;
+        f.chunk = (f.nwg + 7) / 8;
         f.qcap = g.qcap;
         f.mcap = mcap;
         f.sure_need = 9 * p.n_agents + 9 * mcap + 1;            // (dw_step_fused.hpp, STATS)
-        set_strip_rows(h, g.SR);
-        return;
+    } else if (quads && p.width >= 64) {
+        s.kind = STEP_TILED;
+        const int Wq = p.width / 4;
+        if (Wq >= 64) {
+            s.tcq = 64; s.rpt = 4;
+            if (sw.tile_rpt == 2 || sw.tile_rpt == 4 || sw.tile_rpt == 8) s.rpt = sw.tile_rpt;   // tuning experiments only
+        }
+        else if (Wq >= 32) { s.tcq = 32; s.rpt = 4; }
+        else { s.tcq = 16; s.rpt = 2; }
+        const int TR = (256 / s.tcq) * s.rpt;
+        Geom& g = s.geom;
+        g.B = p.batch; g.H = p.height; g.W = p.width; g.Wq = Wq;
+        g.tiles_r = (p.height + TR - 1) / TR;
+        g.tiles_c = (Wq + s.tcq - 1) / s.tcq;
+        g.ntiles = p.batch * g.tiles_r * g.tiles_c;
+        g.chunk = (g.ntiles + 7) / 8;
+        g.qcap = kMaxFix;
+        if (sw.queue_cap >= 0 && sw.queue_cap < kMaxFix) g.qcap = sw.queue_cap;   // tests: force the overflow fallbacks
+        s.tile_lds = (size_t)2 * (TR + 2) * (s.tcq + 2) * 4 * sizeof(float);
+    }                                                           // narrow grids and DW_PRECISION_F64: generic kernel
+    s.need_fixq = p.precision == DW_PRECISION_EXACT && s.kind == STEP_TILED;
+    // The first step from an un-quantised state reads it in its upload format: float32 (fast mode); exact mode: float32
+    // with the tie bound for non-integer inputs, float64 only for the flagged cells (DW_FIRST_STEP_F64=1: every cell in
+    // float64, as in round 2 - experiments); f64 mode: float64 (bit-identical to the reference's first step).
+    s.first_prec = p.precision == DW_PRECISION_FAST ? 1 : (p.precision == DW_PRECISION_EXACT && !sw.first_f64 ? 3 : 2);
+    // Every shape the steady-state wave-strip kernels take, and any multiple of 256: the wave-strip form of the same
+    // arithmetic (dw_step_first.hpp; ~4x fewer vector instructions per cell).  DW_FIRST_GENERIC=1: the one-thread-per-cell
+    // kernel (experiments, tests)
+    s.first_stream = (p.width % 256 == 0 || s.kind == STEP_STREAM) && s.first_prec != 2 && !sw.first_generic;
+    if (s.first_stream) {
+        FirstGeom& fg = s.first_geom;
+        fg.B = p.batch; fg.H = p.height; fg.W = p.width;
+        fg.lpw = s.packed ? lpw : 64;
+        fg.wpr = s.packed ? wpr : 1;
+        fg.ncs = s.packed ? 1 : (p.width + 255) / 256;
+        const long groups = s.packed ? (p.batch + fg.wpr - 1) / fg.wpr : p.batch;
+        fg.SR = strip_rows(groups * fg.ncs, p.height, 4096);   // four strips per SIMD
+        fg.nrs = (p.height + fg.SR - 1) / fg.SR;
+        fg.nstrips = (int)(groups * fg.nrs * fg.ncs);
     }
-    if (Wq >= 64) {
-        h->tcq = 64; h->rpt = 4;
-        if (h->sw.tile_rpt == 2 || h->sw.tile_rpt == 4 || h->sw.tile_rpt == 8) h->rpt = h->sw.tile_rpt;   // tuning experiments only
-    }
-    else if (Wq >= 32) { h->tcq = 32; h->rpt = 4; }
-    else if (Wq >= 16) { h->tcq = 16; h->rpt = 2; }
-    else return;   // narrow grids: generic kernel
-    const int TR = (256 / h->tcq) * h->rpt;
-    Geom& g = h->geom;
-    g.B = p.batch; g.H = p.height; g.W = p.width; g.Wq = Wq;
-    g.tiles_r = (p.height + TR - 1) / TR;
-    g.tiles_c = (Wq + h->tcq - 1) / h->tcq;
-    g.ntiles = p.batch * g.tiles_r * g.tiles_c;
-    g.chunk = (g.ntiles + 7) / 8;
-    g.qcap = kMaxFix;
-    if (h->sw.queue_cap >= 0 && h->sw.queue_cap < kMaxFix) g.qcap = h->sw.queue_cap;   // tests: force the overflow fallbacks
-    h->tile_lds = (size_t)2 * (TR + 2) * (h->tcq + 2) * 4 * sizeof(float);
+    return s;
 }
 
-// near-tie queues of the tiled exact kernel (the streaming kernel keeps them in LDS) for the parameters `p`: room for 1/64
+// near-tie queues of the tiled exact kernel (the streaming kernel keeps them in LDS) when `plan` needs them: room for 1/64
 // of all cells (the bound flags ~0.3-0.5 %), at least 2048 entries per queue; 48 bytes per entry, i.e. 0.75 B per cell
 // on top of the 16 B of state
-static int ensure_fixq(dw_handle* h, const dw_params& p) {
-    if (p.precision != DW_PRECISION_EXACT || p.width % 4 != 0 || p.width < 64 || picks_stream(h, p)) return DW_OK;
+static int ensure_fixq(dw_handle* h, const StepPlan& plan) {
+    if (!plan.need_fixq) return DW_OK;
+    const dw_params& p = h->prm;                                // (the shape: the same for every plan of a handle)
     size_t per_q = (h->cells / 64 + kNumQueues - 1) / kNumQueues;
     if (per_q < 2048) per_q = 2048;
     per_q = (per_q + 255) / 256 * 256;
@@ -637,53 +698,136 @@ static int ensure_fixq(dw_handle* h, const dw_params& p) {
     return DW_OK;
 }
 
+// What every single-step launch passes besides its input planes
+struct StepOut {
+    plane_t* L; plane_t* D;                   // the binary16 planes of the other buffer
+    PhysF32 P;
+    PhysF64 P64;
+    StatsDev* stats;                          // the new state's reductions (all zero before the step) ...
+    unsigned long long* fixups;               // ... and the float64 fix-up counter behind them
+    unsigned long long* zero_me;              // the old state's reductions: cleared for the step after this one
+    int zero_n;
+};
+
 template <int TCQ, int RPT, bool EXACT>
-static int launch_tiled(dw_handle* h, const plane_t* iL, const plane_t* iD, plane_t* oL, plane_t* oD,
-                        const PhysF32& P, const PhysF64& P64, StatsDev* stats,
-                        unsigned long long* fixups, unsigned long long* zero_me, int zero_n, const FixQ& fq) {
+static int launch_tiled(dw_handle* h, const plane_t* iL, const plane_t* iD, const StepOut& o, const FixQ& fq) {
     auto kern = step_tiled<TCQ, RPT, EXACT>;
     // only the 32-row tuning tiles exceed the 64 KB a launch may ask for without opting in
     if constexpr (TileCfg<TCQ, RPT>::LDS_BYTES > 64 * 1024)
         if (int rc = set_lds_limit(h, kern, TileCfg<TCQ, RPT>::LDS_BYTES)) return rc;
-    const unsigned grid = (unsigned)h->geom.chunk * 8u;
+    const Geom& g = h->plan.geom;
     constexpr size_t lds_bytes = TileCfg<TCQ, RPT>::LDS_BYTES;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, h->stream, iL, iD, oL, oD, h->geom, P, stats,
-                       fixups, zero_me, zero_n, fq);
+    hipLaunchKernelGGL(kern, dim3((unsigned)g.chunk * 8u), dim3(256), lds_bytes, h->stream, iL, iD, o.L, o.D, g, o.P, o.stats,
+                       o.fixups, o.zero_me, o.zero_n, fq);
     HIPCHK(hipGetLastError());
     if (EXACT) {
         // second kernel of the step: dense float64 re-evaluation of the queued near-tie cells
-        const dim3 g((fq.qcap + 255) / 256, kNumQueues);
-        hipLaunchKernelGGL(fixup_cells, g, dim3(256), 0, h->stream, oL, oD, h->prm.height, h->prm.width, P64, stats, fq);
+        const dim3 qg((fq.qcap + 255) / 256, kNumQueues);
+        hipLaunchKernelGGL(fixup_cells, qg, dim3(256), 0, h->stream, o.L, o.D, h->prm.height, h->prm.width, o.P64, o.stats, fq);
         // third: whole tiles whose queue overflowed (normally none: exits immediately)
-        hipLaunchKernelGGL(redo_tiles_f64, dim3(256), dim3(256), 0, h->stream, iL, iD, oL, oD, h->geom,
-                           TileCfg<TCQ, RPT>::TR, TCQ, P64, stats, fq);
+        hipLaunchKernelGGL(redo_tiles_f64, dim3(256), dim3(256), 0, h->stream, iL, iD, o.L, o.D, g, TileCfg<TCQ, RPT>::TR, TCQ,
+                           o.P64, o.stats, fq);
         HIPCHK(hipGetLastError());
     }
     return DW_OK;
+}
+
+// one thread per cell (several for big jobs), any input format
+template <class T, int PREC>
+static auto launch_generic(dw_handle* h, const T* iL, const T* iD, const StepOut& o, const FirstStepBound& fb = {}) {
+    const dw_params& p = h->prm;
+    const int cpt = generic_cells_per_thread(p.batch, (long long)p.height * p.width);
+    const dim3 grid((unsigned)(((long long)p.height * p.width + 256LL * cpt - 1) / (256LL * cpt)), (unsigned)p.batch);
+    hipLaunchKernelGGL((step_generic<T, PREC>), grid, dim3(256), 0, h->stream, iL, iD, o.L, o.D, p.height, p.width, o.P, o.P64,
+                       o.stats, o.fixups, o.zero_me, o.zero_n, cpt, fb);
+}
+
+// the first step from the un-quantised state, read in its upload format (StepPlan::first_prec, first_stream)
+static int launch_first_step(dw_handle* h, double L, const StepOut& o) {
+    const StepPlan& pl = h->plan;
+    const FirstStepBound fb = pl.first_prec == 3 ? derive_first_bound(h->prm, L, o.P, h->unq_kind == UNQ_F64, h->sw.first_slack)
+                                                 : FirstStepBound{};
+    if (pl.first_stream) {
+        const dim3 grid((unsigned)((pl.first_geom.nstrips + 3) / 4));
+        with_unq_planes(h, [&](auto* iL, auto* iD) {
+            with_int<1, 3>(pl.first_prec, [&](auto PR) {
+                with_int<0, 1, 2, 3>(pl.halo, [&](auto HL) {
+                    hipLaunchKernelGGL((step_first_stream<elem_t<decltype(iL)>, PR, HL>), grid, dim3(256), 0, h->stream, iL, iD,
+                                       o.L, o.D, pl.first_geom, o.P, o.P64, o.stats, o.fixups, o.zero_me, o.zero_n, fb);
+                });
+            });
+        });
+    } else {
+        with_unq_planes(h, [&](auto* iL, auto* iD) {
+            with_int<1, 3, 2>(pl.first_prec, [&](auto PR) { launch_generic<elem_t<decltype(iL)>, PR>(h, iL, iD, o, fb); });
+        });
+    }
+    HIPCHK(hipGetLastError());
+    return DW_OK;
+}
+
+// a step from the binary16 planes of `cur` by the plan's kernel
+static int launch_step(dw_handle* h, const StepOut& o) {
+    const dw_params& p = h->prm;
+    const StepPlan& pl = h->plan;
+    const plane_t* iL = h->L16[h->cur].get();
+    const plane_t* iD = h->D16[h->cur].get();
+    const bool ex = p.precision == DW_PRECISION_EXACT;
+    if (pl.kind == STEP_GENERIC) {                              // PREC 0 exact, 1 fast, 2 f64
+        const int prec = p.precision == DW_PRECISION_F64 ? 2 : (ex ? 0 : 1);
+        with_int<2, 0, 1>(prec, [&](auto PR) { launch_generic<plane_t, PR>(h, iL, iD, o); });
+    } else if (pl.kind == STEP_STREAM && ex) {
+        const StreamExactArgs A{iL, iD, o.L, o.D, pl.sgeom, o.P, o.stats, o.fixups, o.zero_me, o.zero_n, o.P64};
+        with_int<0, 1, 2, 3>(pl.halo, [&](auto HL) {
+            with_bool(pl.sym_albedo, [&](auto SYM) {
+                hipLaunchKernelGGL((step_stream_exact<HL, SYM>), dim3((unsigned)pl.sgeom.chunk * 8u), dim3(256), 0, h->stream, A);
+            });
+        });
+    } else if (pl.kind == STEP_STREAM) {
+        with_int<0, 1, 2, 3>(pl.halo, [&](auto HL) {
+            hipLaunchKernelGGL((step_stream_fast<HL>), dim3((unsigned)pl.sgeom.chunk * 8u), dim3(256), 0, h->stream, iL, iD, o.L,
+                               o.D, pl.sgeom, o.P, o.P64, o.stats, o.fixups, o.zero_me, o.zero_n);
+        });
+    } else {
+        FixQ fq;
+        fq.entries = h->fixq.get();
+        fq.counts = reinterpret_cast<unsigned int*>(o.stats + p.batch + 1);
+        fq.qcap = h->qcap;
+        fq.redo_tiles = h->redo_tiles.get();
+        auto tiled = [&](auto TCQ, auto RPT) {
+            return with_bool(ex, [&](auto EX) { return launch_tiled<TCQ, RPT, EX>(h, iL, iD, o, fq); });
+        };
+        // the tile shapes plan_steps picks: TCQ 64 with RPT 4 (8 or 2 under DW_TILE_RPT), 32 x 4, 16 x 2
+        if (pl.tcq == 64) return with_int<8, 4, 2>(pl.rpt, [&](auto RPT) { return tiled(int_c<64>{}, RPT); });
+        return pl.tcq == 32 ? tiled(int_c<32>{}, int_c<4>{}) : tiled(int_c<16>{}, int_c<2>{});
+    }
+    HIPCHK(hipGetLastError());
+    return DW_OK;
+}
+
+// A step wrote the other buffer: it holds the current state now, and the reductions swap with it.
+static void step_done(dw_handle* h, double L, bool stepped) {
+    h->cur = 1 - h->cur;
+    h->sp = 1 - h->sp;
+    h->unq = h->unq == OWN_CUR ? OWN_PREV : OWN_NONE;
+    h->stepped = stepped;
+    h->L_last = L;
+    release_unquantised(h);
 }
 
 // forward(): cur -> other buffer, swap.  Assumes agents were already updated.
 static int launch_forward(dw_handle* h, double L) {
     const dw_params& p = h->prm;
     NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
-    const int in = h->cur, out = 1 - h->cur;
-    const PhysF32 P = derive_f32(p, L);
-    const PhysF64 P64 = make_f64(p, L);
+    const int out = 1 - h->cur;
     StatsDev* stats = h->stats2[1 - h->sp].get();                       // invariant: all zero
-    unsigned long long* fixups = &stats[p.batch].sum_l;
-    unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get());
-    const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
-    FixQ fq;
-    fq.entries = h->fixq.get();
-    fq.counts = reinterpret_cast<unsigned int*>(stats + p.batch + 1);
-    fq.qcap = h->qcap;
-    fq.redo_tiles = h->redo_tiles.get();
-    const int gcpt = generic_cells_per_thread(p.batch, (long long)p.height * p.width);
-    const dim3 ggrid((unsigned)(((long long)p.height * p.width + 256LL * gcpt - 1) / (256LL * gcpt)), (unsigned)p.batch);
-    int prec = p.precision;
+    const StepOut o{h->L16[out].get(), h->D16[out].get(), derive_f32(p, L), make_f64(p, L), stats, &stats[p.batch].sum_l,
+                    reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get()),
+                    (int)(h->stats_bytes / sizeof(unsigned long long))};
 #ifdef DW_TUNING
     if (const char* e = std::getenv("DW_ABLATE")) {
         if (std::strcmp(e, "copy") == 0) {
+            const int in = h->cur;
             const size_t n4 = h->cells * sizeof(plane_t) / 16;
             hipLaunchKernelGGL(copy_planes, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, h->stream,
                                reinterpret_cast<const float4*>(h->L16[in].get()), reinterpret_cast<const float4*>(h->D16[in].get()),
@@ -696,122 +840,17 @@ static int launch_forward(dw_handle* h, double L) {
         HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ablate), &v, sizeof(int), 0, hipMemcpyHostToDevice, h->stream));
     }
 #endif
-    if (h->unq == OWN_CUR) {
-        // first step from an un-quantised state: one thread per cell straight from the upload format, in
-        // float64 (exact and f64 modes: bit-identical to the reference's first step) or float32 (fast mode)
-#define DW_GEN(T, PR, IL, ID)                                                                                     \
-    hipLaunchKernelGGL((step_generic<T, PR>), ggrid, dim3(256), 0, h->stream, IL, ID, h->L16[out].get(), h->D16[out].get(),   \
-                       p.height, p.width, P, P64, stats, fixups, zero_me, zero_n, gcpt)
-        // exact mode: float32 with the tie bound for non-integer inputs, float64 only for the flagged cells
-        // (DW_FIRST_STEP_F64=1: every cell in float64, as in round 2 - experiments)
-        const bool first_f64 = h->sw.first_f64;
-        const bool f32arith = prec == DW_PRECISION_FAST;
-        const bool bounded = prec == DW_PRECISION_EXACT && !first_f64;
-#define DW_GEN3(T, IL, ID, FB)                                                                                    \
-    hipLaunchKernelGGL((step_generic<T, 3>), ggrid, dim3(256), 0, h->stream, IL, ID, h->L16[out].get(), h->D16[out].get(),    \
-                       p.height, p.width, P, P64, stats, fixups, zero_me, zero_n, gcpt, FB)
-        // every shape the steady-state wave-strip kernels take (select_kernel: W >= 256 a multiple of 4, or the packed
-        // mode of narrower worlds; and any multiple of 256): the wave-strip form of the same arithmetic (dw_step_first.hpp;
-        // ~4x fewer vector instructions per cell).  DW_FIRST_GENERIC=1: the one-thread-per-cell kernel (experiments, tests)
-        const bool first_stream = (p.width % 256 == 0 || h->use_stream) && (f32arith || bounded) && !h->sw.first_generic;
-        if (first_stream) {
-            const bool packed = h->use_stream && p.width < 256;
-            FirstGeom fg;
-            fg.B = p.batch; fg.H = p.height; fg.W = p.width;
-            fg.lpw = packed ? h->sgeom.lpw : 64;
-            fg.wpr = packed ? h->sgeom.wpr : 1;
-            fg.ncs = packed ? 1 : (p.width + 255) / 256;
-            const long groups = packed ? (p.batch + fg.wpr - 1) / fg.wpr : p.batch;
-            int sr = 64;                                         // shorter strips until every SIMD has four
-            while (sr > 8 && groups * fg.ncs * ((p.height + sr - 1) / sr) < 4096) sr >>= 1;
-            fg.SR = p.height < sr ? p.height : sr;
-            fg.nrs = (p.height + fg.SR - 1) / fg.SR;
-            fg.nstrips = (int)(groups * fg.nrs * fg.ncs);
-            const int fhalo = packed ? 3 : (p.width == 256 ? 0 : (p.width % 256 == 0 ? 1 : 2));
-            const dim3 fgrid((unsigned)((fg.nstrips + 3) / 4));
-            const FirstStepBound fb = bounded ? derive_first_bound(p, L, P, h->unq_kind == UNQ_F64, h->sw.first_slack) : FirstStepBound{};
-#define DW_FIRST(T, PR, HL, IL, ID)                                                                               \
-    hipLaunchKernelGGL((step_first_stream<T, PR, HL>), fgrid, dim3(256), 0, h->stream, IL, ID, h->L16[out].get(),       \
-                       h->D16[out].get(), fg, P, P64, stats, fixups, zero_me, zero_n, fb)
-#define DW_FIRST_HL(T, PR, IL, ID)                                                                                \
-    do { if (fhalo == 0) DW_FIRST(T, PR, 0, IL, ID); else if (fhalo == 1) DW_FIRST(T, PR, 1, IL, ID);           \
-         else if (fhalo == 2) DW_FIRST(T, PR, 2, IL, ID); else DW_FIRST(T, PR, 3, IL, ID); } while (0)
-            if (h->unq_kind == UNQ_F64) {
-                if (f32arith) DW_FIRST_HL(double, 1, h->L64.get(), h->D64.get());
-                else DW_FIRST_HL(double, 3, h->L64.get(), h->D64.get());
-            } else {
-                if (f32arith) DW_FIRST_HL(float, 1, h->U32L.get(), h->U32D.get());
-                else DW_FIRST_HL(float, 3, h->U32L.get(), h->U32D.get());
-            }
-#undef DW_FIRST_HL
-#undef DW_FIRST
-        } else if (h->unq_kind == UNQ_F64) {
-            if (f32arith) DW_GEN(double, 1, h->L64.get(), h->D64.get());
-            else if (bounded) DW_GEN3(double, h->L64.get(), h->D64.get(), derive_first_bound(p, L, P, true, h->sw.first_slack));
-            else DW_GEN(double, 2, h->L64.get(), h->D64.get());
-        } else {
-            if (f32arith) DW_GEN(float, 1, h->U32L.get(), h->U32D.get());
-            else if (bounded) DW_GEN3(float, h->U32L.get(), h->U32D.get(), derive_first_bound(p, L, P, false, h->sw.first_slack));
-            else DW_GEN(float, 2, h->U32L.get(), h->U32D.get());
-        }
-#undef DW_GEN3
-        HIPCHK(hipGetLastError());
-    } else if (prec == DW_PRECISION_F64 || (h->tcq == 0 && !h->use_stream)) {
-        if (prec == DW_PRECISION_F64) DW_GEN(plane_t, 2, h->L16[in].get(), h->D16[in].get());
-        else if (prec == DW_PRECISION_EXACT) DW_GEN(plane_t, 0, h->L16[in].get(), h->D16[in].get());
-        else DW_GEN(plane_t, 1, h->L16[in].get(), h->D16[in].get());
-#undef DW_GEN
-        HIPCHK(hipGetLastError());
-    } else if (h->use_stream) {
-        const bool ex = prec == DW_PRECISION_EXACT;
-        const StripGeom& g = h->sgeom;
-        const dim3 grid((unsigned)g.chunk * 8u);
-        const int halo = p.width < 256 ? 3 : (p.width == 256 ? 0 : (p.width % 256 == 0 ? 1 : 2));
-#define DW_STREAM(K, HL)                                                                                \
-    hipLaunchKernelGGL((K<HL>), grid, dim3(256), 0, h->stream, h->L16[in].get(), h->D16[in].get(), h->L16[out].get(),     \
-                       h->D16[out].get(), g, P, P64, stats, fixups, zero_me, zero_n)
-        if (ex) {
-            const StreamExactArgs A{h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P, stats, fixups, zero_me,
-                                    zero_n, P64};
-#define DW_SX(HL)                                                                                     \
-    do {                                                                                              \
-        if (h->sym_albedo) hipLaunchKernelGGL((step_stream_exact<HL, true>), grid, dim3(256), 0, h->stream, A); \
-        else hipLaunchKernelGGL((step_stream_exact<HL, false>), grid, dim3(256), 0, h->stream, A);     \
-    } while (0)
-            if (halo == 0) DW_SX(0); else if (halo == 1) DW_SX(1); else if (halo == 2) DW_SX(2); else DW_SX(3);
-#undef DW_SX
-
-        } else {
-            if (halo == 0) DW_STREAM(step_stream_fast, 0);
-            else if (halo == 1) DW_STREAM(step_stream_fast, 1);
-            else if (halo == 2) DW_STREAM(step_stream_fast, 2);
-            else DW_STREAM(step_stream_fast, 3);
-        }
-#undef DW_STREAM
-        HIPCHK(hipGetLastError());
-    } else {
-        const bool ex = prec == DW_PRECISION_EXACT;
-        int rc;
-#define DW_TILED(T, R)                                                                              \
-    rc = ex ? launch_tiled<T, R, true>(h, h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), P, P64,  \
-                                       stats, fixups, zero_me, zero_n, fq)                           \
-            : launch_tiled<T, R, false>(h, h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), P, P64, \
-                                        stats, fixups, zero_me, zero_n, fq)
-        if (h->tcq == 64 && h->rpt == 8) { DW_TILED(64, 8); }
-        else if (h->tcq == 64 && h->rpt == 4) { DW_TILED(64, 4); }
-        else if (h->tcq == 64) { DW_TILED(64, 2); }
-        else if (h->tcq == 32) { DW_TILED(32, 4); }
-        else { DW_TILED(16, 2); }
-#undef DW_TILED
-        if (rc != DW_OK) return rc;
-    }
-    h->cur = out;
-    h->sp = 1 - h->sp;
-    h->unq = (h->unq == OWN_CUR) ? OWN_PREV : OWN_NONE;
-    h->stepped = true;
-    h->L_last = L;
-    release_unquantised(h);
+    if (int rc = h->unq == OWN_CUR ? launch_first_step(h, L, o) : launch_step(h, o)) return rc;
+    step_done(h, L, true);
     return DW_OK;
+}
+
+// f(MODE, PACK) for the strip layout of the fused kernels: packed worlds in rotating 256-column strips, the others by
+// the plan's mode
+template <class F>
+static auto with_fused_layout(const StepPlan& pl, F&& f) {
+    if (pl.packed) return f(int_c<kFusedRot>{}, std::true_type{});
+    return with_int<kFusedRot, kFusedRing, kFusedOvl>(pl.fused_mode, [&](auto MODE) { return f(MODE, std::false_type{}); });
 }
 
 // Two steps (luminosities L1 then L2) in one launch on wide grids, no agent update in between.  The buffer
@@ -820,51 +859,36 @@ static int launch_forward(dw_handle* h, double L) {
 static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned int* pstats = nullptr,
                                  float thr_hi = 0.f) {
     const dw_params& p = h->prm;
+    const StepPlan& pl = h->plan;
     const int in = h->cur, out = 1 - h->cur;
     PhysF32 P1, P2;
     if (p.precision == DW_PRECISION_EXACT) derive_f32_pair(p, L1, L2, &P1, &P2);
     else { P1 = derive_f32(p, L1); P2 = derive_f32(p, L2); }
     unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get());
     const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
-    const FusedGeom& g = h->fgeom;
+    const FusedGeom& g = pl.fgeom;
     const dim3 grid((unsigned)g.chunk * 8u);
-    const bool rot = p.width == 256, pack = p.width < 256, ring = h->fused_ring;
     if (p.precision == DW_PRECISION_EXACT) {
         const FusedExactArgs A{h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P1, lum_part(P2), zero_me, zero_n,
                                pstats, thr_hi, make_f64(p, L1), L1, L2};
-#define DW_FX(R, P, S)                                                                                            \
-    do {                                                                                                          \
-        if (h->sym_albedo) hipLaunchKernelGGL((step_stream_fused2_exact<R, P, S, true>), grid, dim3(256), 0, h->stream, A); \
-        else hipLaunchKernelGGL((step_stream_fused2_exact<R, P, S, false>), grid, dim3(256), 0, h->stream, A);     \
-    } while (0)
-        if (pstats) {
-            if (pack) DW_FX(kFusedRot, true, true); else if (rot) DW_FX(kFusedRot, false, true);
-            else if (ring) DW_FX(kFusedRing, false, true); else DW_FX(kFusedOvl, false, true);
-        } else {
-            if (pack) DW_FX(kFusedRot, true, false); else if (rot) DW_FX(kFusedRot, false, false);
-            else if (ring) DW_FX(kFusedRing, false, false); else DW_FX(kFusedOvl, false, false);
-        }
-#undef DW_FX
+        with_bool(pstats != nullptr, [&](auto STATS) {
+            with_fused_layout(pl, [&](auto MODE, auto PACK) {
+                with_bool(pl.sym_albedo, [&](auto SYM) {
+                    hipLaunchKernelGGL((step_stream_fused2_exact<MODE, PACK, STATS, SYM>), grid, dim3(256), 0, h->stream, A);
+                });
+            });
+        });
     } else {
-#define DW_FF(R, P, S)                                                                                           \
-    hipLaunchKernelGGL((step_stream_fused2<R, P, S>), grid, dim3(256), 0, h->stream, h->L16[in].get(), h->D16[in].get(),      \
-                       h->L16[out].get(), h->D16[out].get(), g, P1, P2, zero_me, zero_n, pstats, thr_hi)
-        if (pstats) {
-            if (pack) DW_FF(kFusedRot, true, true); else if (rot) DW_FF(kFusedRot, false, true);
-            else if (ring) DW_FF(kFusedRing, false, true); else DW_FF(kFusedOvl, false, true);
-        } else {
-            if (pack) DW_FF(kFusedRot, true, false); else if (rot) DW_FF(kFusedRot, false, false);
-            else if (ring) DW_FF(kFusedRing, false, false); else DW_FF(kFusedOvl, false, false);
-        }
-#undef DW_FF
+        with_bool(pstats != nullptr, [&](auto STATS) {
+            with_fused_layout(pl, [&](auto MODE, auto PACK) {
+                hipLaunchKernelGGL((step_stream_fused2<MODE, PACK, STATS>), grid, dim3(256), 0, h->stream, h->L16[in].get(),
+                                   h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P1, P2, zero_me, zero_n, pstats,
+                                   thr_hi);
+            });
+        });
     }
     HIPCHK(hipGetLastError());
-    h->cur = out;
-    h->sp = 1 - h->sp;            // the kernel cleared the old buffer; the (untouched, zero) other one is "current"
-    h->unq = OWN_NONE;
-    h->stepped = false;
-    h->L_last = L2;
-    release_unquantised(h);
+    step_done(h, L2, false);      // the kernel cleared the old reductions; the (untouched, zero) other buffer is "current"
     return DW_OK;
 }
 
@@ -878,16 +902,13 @@ static int launch_agents(dw_handle* h, const int* d_action, int act_b, int act_n
          "collision_mode=1: call dw_update_agents, apply the collision pass (it consumes the caller's RNG) to the "
          "downloaded agent states, upload them, then dw_step without actions");
     const int blocks = (p.batch + 63) / 64;
-#define DW_AG(T, PL, PD)                                                                                          \
-    hipLaunchKernelGGL(agents_update<T>, dim3(blocks), dim3(64), 0, h->stream, PL, PD, h->idx.get(), h->st.get(), d_action,    \
-                       act_b, act_n, p.batch, p.n_agents, p.height, p.width, p.agent_gamma,                        \
-                       p.collision_mode == 0 ? 1 : 0, d_reward, d_done, d_ok)
-    if (h->unq == OWN_CUR) {                       // grazing on the un-quantised state, in its own format
-        if (h->unq_kind == UNQ_F64) DW_AG(double, h->L64.get(), h->D64.get()); else DW_AG(float, h->U32L.get(), h->U32D.get());
-    } else {
-        DW_AG(plane_t, h->L16[h->cur].get(), h->D16[h->cur].get());
-    }
-#undef DW_AG
+    // grazing on the current state, in its own format (an un-quantised one included)
+    with_planes(h, h->unq == OWN_CUR, h->cur, [&](auto* L, auto* D) {
+        using T = elem_t<decltype(L)>;
+        hipLaunchKernelGGL(agents_update<T>, dim3(blocks), dim3(64), 0, h->stream, L, D, h->idx.get(), h->st.get(), d_action,
+                           act_b, act_n, p.batch, p.n_agents, p.height, p.width, p.agent_gamma,
+                           p.collision_mode == 0 ? 1 : 0, d_reward, d_done, d_ok);
+    });
     HIPCHK(hipGetLastError());
     return DW_OK;
 }
@@ -997,7 +1018,8 @@ int dw_create(const dw_params* p, dw_handle** out) {
         return rc;
     for (int i = 0; i < 2; ++i) HIPCHK(hipMemsetAsync(h->stats2[i].get(), 0, h->stats_bytes, h->stream));
     h->sw = read_switches();                                    // the environment is read here and nowhere else
-    if (int rc = ensure_fixq(h.get(), *p)) return rc;
+    h->plan = plan_steps(*p, h->sw);
+    if (int rc = ensure_fixq(h.get(), h->plan)) return rc;
     HIPCHK(hipMemsetAsync(h->action.get(), 0, sizeof(int) * bn, h->stream));
     HIPCHK(hipMemsetAsync(h->done_at.get(), 0, sizeof(int) * p->batch, h->stream));
     HIPCHK(hipMemsetAsync(h->agents_done_at.get(), 0, sizeof(int) * bn, h->stream));
@@ -1006,7 +1028,6 @@ int dw_create(const dw_params* p, dw_handle** out) {
     HIPCHK(hipEventCreate(&h->ev1));
     HIPCHK(hipEventCreate(&h->evf0));
     HIPCHK(hipEventCreate(&h->evf1));
-    select_kernel(h.get());
     h->created = true;
     *out = h.release();
     return DW_OK;
@@ -1034,9 +1055,10 @@ int dw_set_params(dw_handle* h, const dw_params* p) {
              p->device == o.device,
          DW_EINVAL, "dw_set_params cannot change shape or device; create a new handle");
     HIPCHK(hipSetDevice(p->device));
-    if ((rc = ensure_fixq(h, *p))) return rc;                   // a failure leaves the handle as it was
+    const StepPlan plan = plan_steps(*p, h->sw);
+    if ((rc = ensure_fixq(h, plan))) return rc;                 // a failure leaves the handle as it was
     h->prm = *p;
-    select_kernel(h);
+    h->plan = plan;
     return DW_OK;
 }
 
@@ -1058,12 +1080,11 @@ static int refresh_stats(dw_handle* h) {
     if (int rc = clear_stats(h)) return rc;
     const int n = p.height * p.width;
     const dim3 g((unsigned)((n + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
-    if (h->unq != OWN_CUR)
-        hipLaunchKernelGGL((stats_only<plane_t>), g, dim3(256), 0, h->stream, h->L16[h->cur].get(), h->D16[h->cur].get(), n, h->stats2[h->sp].get());
-    else if (h->unq_kind == UNQ_F64)
-        hipLaunchKernelGGL((stats_only<double>), g, dim3(256), 0, h->stream, h->L64.get(), h->D64.get(), n, h->stats2[h->sp].get());
-    else
-        hipLaunchKernelGGL((stats_only<float>), g, dim3(256), 0, h->stream, h->U32L.get(), h->U32D.get(), n, h->stats2[h->sp].get());
+    auto reduce = [&](auto* L, auto* D) {
+        hipLaunchKernelGGL((stats_only<elem_t<decltype(L)>>), g, dim3(256), 0, h->stream, L, D, n, h->stats2[h->sp].get());
+    };
+    if (cur_quantised(h)) reduce(h->L16[h->cur].get(), h->D16[h->cur].get());
+    else with_unq_planes(h, reduce);
     HIPCHK(hipGetLastError());
     return DW_OK;
 }
@@ -1246,49 +1267,20 @@ int dw_download_planes(dw_handle* h, int which, double* light, double* dark) {
     return DW_OK;
 }
 
-// The state observations and the materialised grid derive their temperature channels from: after a step the
-// PRE-step state (post = true), before any step the current one (post = false); fmt 0 binary16, 1 float32
-// per-mille, 2 float64 natural.
-struct DerivedFrom { int fmt; const void* L; const void* D; bool post; };
-static DerivedFrom derived_from(const dw_handle* h) {
-    const int cur = h->cur, prev = 1 - h->cur;
-    if (h->stepped) {
-        if (h->unq == OWN_PREV)
-            return h->unq_kind == UNQ_F64 ? DerivedFrom{2, h->L64.get(), h->D64.get(), true} : DerivedFrom{1, h->U32L.get(), h->U32D.get(), true};
-        return DerivedFrom{0, h->L16[prev].get(), h->D16[prev].get(), true};
-    }
-    if (h->unq == OWN_CUR)
-        return h->unq_kind == UNQ_F64 ? DerivedFrom{2, h->L64.get(), h->D64.get(), false} : DerivedFrom{1, h->U32L.get(), h->U32D.get(), false};
-    return DerivedFrom{0, h->L16[cur].get(), h->D16[cur].get(), false};
-}
-// K<T, POST>(pL, pD, args...) for the format / phase of `src`
-#define DW_DISPATCH_DERIVED(K, src, grid, block, ...)                                                               \
-    do {                                                                                                            \
-        if ((src).fmt == 2) {                                                                                       \
-            if ((src).post) hipLaunchKernelGGL((K<double, true>), grid, block, 0, h->stream, (const double*)(src).L, (const double*)(src).D, __VA_ARGS__); \
-            else hipLaunchKernelGGL((K<double, false>), grid, block, 0, h->stream, (const double*)(src).L, (const double*)(src).D, __VA_ARGS__); \
-        } else if ((src).fmt == 1) {                                                                                \
-            if ((src).post) hipLaunchKernelGGL((K<float, true>), grid, block, 0, h->stream, (const float*)(src).L, (const float*)(src).D, __VA_ARGS__); \
-            else hipLaunchKernelGGL((K<float, false>), grid, block, 0, h->stream, (const float*)(src).L, (const float*)(src).D, __VA_ARGS__); \
-        } else {                                                                                                    \
-            if ((src).post) hipLaunchKernelGGL((K<plane_t, true>), grid, block, 0, h->stream, (const plane_t*)(src).L, (const plane_t*)(src).D, __VA_ARGS__); \
-            else hipLaunchKernelGGL((K<plane_t, false>), grid, block, 0, h->stream, (const plane_t*)(src).L, (const plane_t*)(src).D, __VA_ARGS__); \
-        }                                                                                                           \
-    } while (0)
-
 // materialise into device scratch: grid7 and/or caches
 static int run_materialise(dw_handle* h, double L, double* d_grid7, double* d_temps, double* d_betas,
                            double* d_growth, double* d_teff) {
     const dw_params& p = h->prm;
     const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
-    const DerivedFrom src = derived_from(h);
-    const PhysF64 P = make_f64(p, src.post ? h->L_last : L);
+    const PhysF64 P = make_f64(p, h->stepped ? h->L_last : L);
     const plane_t* cL = h->L16[h->cur].get();            // read by the POST variants only
     const plane_t* cD = h->D16[h->cur].get();
-    DW_DISPATCH_DERIVED(materialise, src, g, dim3(256), cL, cD, p.height, p.width, P, d_grid7, d_temps, d_betas, d_growth,
-                        d_teff);
+    with_derived_from(h, [&](auto* pL, auto* pD, auto POST) {
+        hipLaunchKernelGGL((materialise<elem_t<decltype(pL)>, POST>), g, dim3(256), 0, h->stream, pL, pD, cL, cD, p.height,
+                           p.width, P, d_grid7, d_temps, d_betas, d_growth, d_teff);
+    });
     HIPCHK(hipGetLastError());
-    if (src.post && d_grid7 && p.n_agents && h->have_agents) {
+    if (h->stepped && d_grid7 && p.n_agents && h->have_agents) {
         hipLaunchKernelGGL(agents_stamp, dim3((p.batch + 63) / 64), dim3(64), 0, h->stream, d_grid7, h->idx.get(),
                            h->st.get(), p.batch, p.n_agents, p.height, p.width);
         HIPCHK(hipGetLastError());
@@ -1401,7 +1393,7 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
     // Small worlds: keep the whole run of steps on the chip (worlds in LDS, one launch per 4096 steps) -
     // unless the ensemble is big enough to fill the GPU with wave-strips, where the packed fused kernel is
     // 1.5-1.8x faster (measured crossover between 2 M and 16 M cells: tools/kbench.py 512 64 / 4096 64).
-    const bool big_packed = h->use_stream && h->allow_fuse && h->prm.width < 256 && h->cells >= ((size_t)1 << 23);
+    const bool big_packed = h->plan.allow_fuse && h->plan.packed && h->cells >= ((size_t)1 << 23);
     if (!use_device_actions && nsteps - s0 > 1 && h->have_state && h->prm.height * h->prm.width <= 4096 && !big_packed &&
         episode_kernel_applies(h)) {
         std::vector<double> Ls;
@@ -1416,8 +1408,7 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
         *L_io = L;
         return DW_OK;
     }
-    if (!use_device_actions && h->allow_fuse && h->use_stream && h->have_state &&
-        (h->prm.precision == DW_PRECISION_FAST || h->prm.precision == DW_PRECISION_EXACT) && nsteps - s0 >= 3) {
+    if (!use_device_actions && h->plan.allow_fuse && h->have_state && nsteps - s0 >= 3) {
         // wide grids: pairs of steps share one HBM round trip; the last one or two steps are ordinary launches
         // so that the retained previous state is the true predecessor.  HIP events around the run of fused
         // launches feed dw_last_step_n_timing (the dominant kernel's duration, measured on its own stream).
@@ -1564,15 +1555,9 @@ int dw_stage_f64(dw_handle* h, int stage, const double* in, double* out, double 
     SyncOnExit guard(h->stream);                              // `in` / `out` are the caller's
     HIPCHK(hipMemcpyAsync(d_in, in, sizeof(double) * nin * n, hipMemcpyHostToDevice, h->stream));
     const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
-#define DW_STAGE(S) hipLaunchKernelGGL((stage_f64<S>), g, dim3(256), 0, h->stream, d_in, d_out, p.batch, p.height, p.width, P, K)
-    switch (stage) {
-        case kStageAlbedo: DW_STAGE(kStageAlbedo); break;
-        case kStageDensity: DW_STAGE(kStageDensity); break;
-        case kStageTemperature: DW_STAGE(kStageTemperature); break;
-        case kStageGrowthRate: DW_STAGE(kStageGrowthRate); break;
-        default: DW_STAGE(kStageGrowth); break;
-    }
-#undef DW_STAGE
+    with_int<kStageAlbedo, kStageDensity, kStageTemperature, kStageGrowthRate, kStageGrowth>(stage, [&](auto S) {
+        hipLaunchKernelGGL((stage_f64<S>), g, dim3(256), 0, h->stream, d_in, d_out, p.batch, p.height, p.width, P, K);
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nout * n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1734,12 +1719,13 @@ static int observe_into_scratch(dw_handle* h, double L_init, size_t extra_bytes,
     unsigned char* d_done = reward_tail ? reinterpret_cast<unsigned char*>(h->scratch.get() + bn * 64) : nullptr;
     const int threads = (int)(bn * 9);
     const dim3 g((threads + 127) / 128);
-    const DerivedFrom src = derived_from(h);
-    const PhysF64 P = make_f64(p, src.post ? h->L_last : L_init);
+    const PhysF64 P = make_f64(p, h->stepped ? h->L_last : L_init);
     const plane_t* cL = h->L16[h->cur].get();            // read by the POST variants only
     const plane_t* cD = h->D16[h->cur].get();
-    DW_DISPATCH_DERIVED(observe, src, g, dim3(128), cL, cD, h->idx.get(), h->st.get(), p.batch, p.n_agents, p.height, p.width, P,
-                        p.obs_mask, h->scratch.get(), d_rew, d_done);
+    with_derived_from(h, [&](auto* pL, auto* pD, auto POST) {
+        hipLaunchKernelGGL((observe<elem_t<decltype(pL)>, POST>), g, dim3(128), 0, h->stream, pL, pD, cL, cD, h->idx.get(),
+                           h->st.get(), p.batch, p.n_agents, p.height, p.width, P, p.obs_mask, h->scratch.get(), d_rew, d_done);
+    });
     HIPCHK(hipGetLastError());
     return DW_OK;
 }
@@ -1980,8 +1966,7 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
     // forward_{t+1}, then the agents' step t+1 recomputed around the agents and patched into the result.
     // Needs no per-step world reductions (the caller passed world_alive == NULL); the last step of the
     // call stays an ordinary step, so the handle ends exactly as after K calls of dw_step.
-    const bool may_pair = h->allow_fuse && h->use_stream && bn && N <= kLookaheadMaxAgents &&
-                          policy_mode != kPolicySkipAgents && p.precision != DW_PRECISION_F64 &&
+    const bool may_pair = h->plan.allow_fuse && bn && N <= kLookaheadMaxAgents && policy_mode != kPolicySkipAgents &&
                           !h->sw.no_agent_fuse;
     // With per-step world flags the fused launch also reduces what the flags of both steps need (STATS
     // variants: exact step-1 maximum, count of certain step-2 values above the threshold).
@@ -2350,28 +2335,29 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark) {
 int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     NEED(h && buf && buflen, DW_EINVAL, "null argument");
     const dw_params& p = h->prm;
+    const StepPlan& pl = h->plan;
     const char* prec = p.precision == DW_PRECISION_EXACT ? "exact" : (p.precision == DW_PRECISION_FAST ? "fast" : "f64");
-    if (h->use_stream && p.precision != DW_PRECISION_F64) {
-        const StripGeom& g = h->sgeom;
+    static const char* const halo_name[] = {"rotate", "dpp-old", "general", "packed"};     // by halo_form
+    if (pl.kind == STEP_STREAM) {
+        const StripGeom& g = pl.sgeom;
         snprintf(buf, buflen,
                  "step_stream_%s<halo=%s> wave-strip=%dx256 cells, register window + DPP neighbours, %d-row blocks in "
                  "flight%s, %d strips, grid=%d x 256 threads (4 strips each), XCD-chunked",
-                 prec, p.width < 256 ? "packed" : (p.width == 256 ? "rotate" : (p.width % 256 == 0 ? "dpp-old" : "general")),
-                 g.SR,
+                 prec, halo_name[pl.halo], g.SR,
                  p.precision == DW_PRECISION_EXACT ? DW_STREAM_RB_EXACT : DW_STREAM_RB_FAST,
                  p.precision == DW_PRECISION_EXACT ? ", in-wave float64 fix-up from an LDS queue" : "", g.nstrips,
                  g.chunk * 8);
-        if (h->allow_fuse) {
+        if (pl.allow_fuse) {
             const size_t n = std::strlen(buf);
             snprintf(buf + n, buflen - n, "; dw_step_n fuses step pairs (step_stream_fused2%s)",
                      p.precision == DW_PRECISION_EXACT ? "_exact" : "");
         }
-    } else if (h->tcq) {
-        const int TR = (256 / h->tcq) * h->rpt;
+    } else if (pl.kind == STEP_TILED) {
+        const int TR = (256 / pl.tcq) * pl.rpt;
         snprintf(buf, buflen,
                  "step_tiled<TCQ=%d,RPT=%d,%s> tile=%dx%d cells, %zu B LDS/workgroup, %d tiles, grid=%d x 256 threads, "
                  "XCD-chunked",
-                 h->tcq, h->rpt, prec, TR, h->tcq * 4, h->tile_lds, h->geom.ntiles, h->geom.chunk * 8);
+                 pl.tcq, pl.rpt, prec, TR, pl.tcq * 4, pl.tile_lds, pl.geom.ntiles, pl.geom.chunk * 8);
     } else {
         snprintf(buf, buflen, "step_generic<%s> one thread per cell, grid=(%d,%d) x 256 threads", prec,
                  (p.height * p.width + 255) / 256, p.batch);
@@ -2388,13 +2374,14 @@ int dw_audit_tie_bound(dw_handle* h, double L, double out[4]) {
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
     NEED(h->have_state && cur_quantised(h), DW_ESTATE, "the audit needs a quantised current state");
+    const StepPlan& pl = h->plan;
     int rc = ensure_scratch(h, 4 * sizeof(unsigned long long));
     if (rc) return rc;
     unsigned long long* d = reinterpret_cast<unsigned long long*>(h->scratch.get());
     HIPCHK(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), h->stream));
     const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
     hipLaunchKernelGGL(tie_audit, g, dim3(256), 0, h->stream, h->L16[h->cur].get(), h->D16[h->cur].get(), p.height, p.width,
-                       derive_f32(p, L), make_f64(p, L), d, h->sym_albedo && h->use_stream ? 1 : 0);
+                       derive_f32(p, L), make_f64(p, L), d, pl.sym_albedo && pl.kind == STEP_STREAM ? 1 : 0);
     HIPCHK(hipGetLastError());
     unsigned long long r[4];
     HIPCHK(hipMemcpyAsync(r, d, sizeof(r), hipMemcpyDeviceToHost, h->stream));
