@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define DW_ABI_VERSION 5
+#define DW_ABI_VERSION 6
 
 /* ---- error codes ---------------------------------------------------------------------------- */
 enum {
@@ -233,6 +233,15 @@ int dw_download_actions(dw_handle* h, int32_t* action /* [B][N] */);
  * (on wide grids two steps share one launch: step-1 values live only in registers). */
 int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_L, double max_L,
               int use_device_actions);
+
+/* The time series of an agent-free run (the notebook's population curves, ref daisy/notebook_helpers.py:50-54): nsteps
+ * steps (as dw_step_n with use_device_actions = 0) with luminosity L_schedule[t] for step t.
+ * trace[t*B + b] = what dw_reduce would report for world b after step t (max_k, sum_light_k, sum_dark_k; `reserved` is
+ * unspecified).  State, retained previous state, dw_reduce and observations after the call are those of nsteps calls of
+ * dw_step(h, NULL, 0, 0, L_schedule[t]), bit for bit.  The series is recorded on the device (on wide grids by the step-pair
+ * kernels themselves, see dw_kernel_info: "trace: step pairs" / "trace: single steps") and downloaded once per 32 MiB of
+ * records.  nsteps == 0 is a no-op.  Synchronises (it fills a host buffer). */
+int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace /* [nsteps][B] */);
 
 /* Measurement aid (bench.py): duration of the run of fused step-pair launches issued by the LAST
  * dw_step_n call, from HIP events recorded on the handle's stream immediately before the first and after the

@@ -110,6 +110,8 @@ struct StepPlan {
     bool packed = false;              // STEP_STREAM with W < 256: several worlds side by side in a wave row
     bool allow_fuse = false;          // STEP_STREAM only: dw_step_n / dw_run_episode fuse pairs of steps ...
     int fused_mode = kFusedOvl;       // ... with this strip layout (packed worlds: kFusedRot)
+    bool trace_pairs = false;         // dw_step_n_trace records step pairs (trace_pair_fast / trace_pair_exact: un-packed
+                                      // overlapped or rotating strips); otherwise single steps, a copy of B records each
     bool sym_albedo = false;          // a_dark - a_bare == -(a_light - a_bare) exactly: the exact wave-strip kernels use
                                       // the two-term coefficient chain (growth_t<.., SYM>)
     int tcq = 0, rpt = 0;             // STEP_TILED: tile columns (quads) and rows per thread
@@ -193,6 +195,7 @@ struct dw_handle {
     int fused_launches = 0;           // ... and how many there were (dw_last_step_n_timing); 0 unless BOTH events
                                       // of that call were recorded (an error return in between leaves 0)
     DevBuf<StatsDev> side_stats;      // reductions of dw_forward_f64's side computation (not the handle's)
+    DevBuf<StatsDev> trace_d;         // dw_step_n_trace: [rows][B] records of the chunk of steps in flight (grown on demand)
     PinnedBuf<unsigned char> pinned;  // page-locked host staging of dw_env_step (actions in, obs/reward/done out)
     // dw_snapshot_save[_slot] / dw_snapshot_restore[_slot]: device copies of the current state (two slots: a harness
     // that runs chunk c + 1 while it still accounts for chunk c keeps the starts of both)
@@ -638,6 +641,7 @@ static StepPlan plan_steps(const dw_params& p, const Switches& sw) {
         f.qcap = g.qcap;
         f.mcap = mcap;
         f.sure_need = 9 * p.n_agents + 9 * mcap + 1;            // (dw_step_fused.hpp, STATS)
+        s.trace_pairs = s.allow_fuse && !s.packed && s.fused_mode != kFusedRing;
     } else if (quads && p.width >= 64) {
         s.kind = STEP_TILED;
         const int Wq = p.width / 4;
@@ -856,8 +860,10 @@ static auto with_fused_layout(const StepPlan& pl, F&& f) {
 // Two steps (luminosities L1 then L2) in one launch on wide grids, no agent update in between.  The buffer
 // that held the input now holds the state TWO steps back, so the retained "previous state" is not valid
 // afterwards; dw_step_n always ends with an ordinary single step.
+// `trace` (dw_step_n_trace, plans with trace_pairs): the TRACE kernels, which add the reductions of both steps into rows
+// trace[0 .. B) and trace[B .. 2B).
 static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned int* pstats = nullptr,
-                                 float thr_hi = 0.f) {
+                                 float thr_hi = 0.f, StatsDev* trace = nullptr) {
     const dw_params& p = h->prm;
     const StepPlan& pl = h->plan;
     const int in = h->cur, out = 1 - h->cur;
@@ -868,7 +874,21 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
     const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
     const FusedGeom& g = pl.fgeom;
     const dim3 grid((unsigned)g.chunk * 8u);
-    if (p.precision == DW_PRECISION_EXACT) {
+    if (trace && p.precision == DW_PRECISION_EXACT) {
+        const TraceExactArgs A{{h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P1, lum_part(P2), zero_me,
+                                zero_n, nullptr, 0.f, make_f64(p, L1), L1, L2},
+                               trace, h->sw.force_rescan ? 1 : 0};
+        with_int<kFusedRot, kFusedOvl>(pl.fused_mode, [&](auto MODE) {
+            with_bool(pl.sym_albedo, [&](auto SYM) {
+                hipLaunchKernelGGL((trace_pair_exact<MODE, SYM>), grid, dim3(256), 0, h->stream, A);
+            });
+        });
+    } else if (trace) {
+        with_int<kFusedRot, kFusedOvl>(pl.fused_mode, [&](auto MODE) {
+            hipLaunchKernelGGL((trace_pair_fast<MODE>), grid, dim3(256), 0, h->stream, h->L16[in].get(), h->D16[in].get(),
+                               h->L16[out].get(), h->D16[out].get(), g, P1, P2, zero_me, zero_n, trace);
+        });
+    } else if (p.precision == DW_PRECISION_EXACT) {
         const FusedExactArgs A{h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P1, lum_part(P2), zero_me, zero_n,
                                pstats, thr_hi, make_f64(p, L1), L1, L2};
         with_bool(pstats != nullptr, [&](auto STATS) {
@@ -1443,6 +1463,52 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
         advance();
     }
     *L_io = L;
+    return DW_OK;
+}
+
+int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace) {
+    NEED(h && L_schedule && trace, DW_EINVAL, "null argument");
+    NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
+    if (nsteps == 0) return DW_OK;
+    NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
+    static_assert(sizeof(dw_world_stats) == sizeof(StatsDev), "stats layout");
+    HIPCHK(hipSetDevice(h->prm.device));
+    const size_t B = (size_t)h->prm.batch, row_bytes = sizeof(StatsDev) * B;
+    // rows of the series held on the device at a time: the whole run up to 32 MiB (512 steps of 1024 worlds: 12 MiB),
+    // longer runs in chunks of that size (an even number of rows, at least two: a step pair fills two)
+    size_t rows = ((size_t)32 << 20) / row_bytes & ~(size_t)1;
+    rows = rows < 2 ? 2 : rows;
+    rows = rows > (size_t)nsteps ? (size_t)nsteps : rows;
+    if (int rc = alloc_group(h, "the trace buffer", {{h->trace_d, rows * row_bytes}})) return rc;
+    SyncOnExit sync(h->stream);                                 // the downloads below fill the caller's array
+    h->fused_launches = 0;
+    bool first_pair = true;
+    for (int c0 = 0; c0 < nsteps; c0 += (int)rows) {
+        const int cn = nsteps - c0 < (int)rows ? nsteps - c0 : (int)rows;
+        HIPCHK(hipMemsetAsync(h->trace_d.get(), 0, (size_t)cn * row_bytes, h->stream));
+        for (int t = c0; t < c0 + cn;) {
+            StatsDev* row = h->trace_d.get() + (size_t)(t - c0) * B;
+            // a pair where dw_step_n would issue one (the closing one or two steps stay ordinary launches: the retained
+            // previous state is the true predecessor) and both rows lie in this chunk
+            if (h->plan.trace_pairs && cur_quantised(h) && nsteps - t >= 3 && t + 2 <= c0 + cn) {
+                if (first_pair) {                               // (as dw_step_n: an un-quantised previous state ends here)
+                    if (h->unq == OWN_PREV) { h->unq = OWN_NONE; h->stepped = false; }
+                    release_unquantised(h);
+                    first_pair = false;
+                }
+                if (int rc = launch_forward_fused2(h, L_schedule[t], L_schedule[t + 1], nullptr, 0.f, row)) return rc;
+                t += 2;
+            } else {
+                if (int rc = launch_forward(h, L_schedule[t])) return rc;
+                HIPCHK(hipMemcpyAsync(row, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
+                t += 1;
+            }
+        }
+        HIPCHK(hipMemcpyAsync(trace + (size_t)c0 * B, h->trace_d.get(), (size_t)cn * row_bytes, hipMemcpyDeviceToHost,
+                              h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    sync.disarm();
     return DW_OK;
 }
 
@@ -2361,6 +2427,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     } else {
         snprintf(buf, buflen, "step_generic<%s> one thread per cell, grid=(%d,%d) x 256 threads", prec,
                  (p.height * p.width + 255) / 256, p.batch);
+    }
+    {                                                           // the form dw_step_n_trace takes (StepPlan::trace_pairs)
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, pl.trace_pairs ? "; trace: step pairs" : "; trace: single steps");
     }
     if (h->sw.text[0]) {                                        // the switches this handle was created under
         const size_t n = std::strlen(buf);

@@ -116,14 +116,27 @@ constexpr int kMismatchCap = 64;            // float32 step-1 mismatches per wav
 //                       value above `thr_hi` that cannot be an artefact of float32 or be undone by the few
 //                       cells patched afterwards - a sound lower bound, see agents_lookahead_patch.
 enum { kFusedOvl = 0, kFusedRot = 1, kFusedRing = 2 };
+// TRACE (trace_pair_fast / trace_pair_exact below, dw_step_n_trace): the wave also leaves the strip with the three
+// per-world reductions of BOTH steps - row `trace` (step 1) and row `trace + G.B` (step 2) of the caller's series.
+//   ownership   a step-1 cell counts in the strip whose OUTPUT cell it is: lanes with `writes`, step-1 rows 2 .. nr+1
+//   sums        float32 pair accumulators per lane (integers, < 2^24 per strip), as in the single-step kernels
+//   exact sums  every later change of a cell reaches them as a difference: F1 (float64 - float32 value of a queued
+//               step-1 cell), F2 (float64 - float32 value of a queued output cell), F3 (new - STORED value, read back);
+//               a strip that falls back is summed from scratch
+//   exact max   step 1: near-tie cells stay out of the running maximum and F1 adds their float64 values (every near-tie
+//               cell of the strip is queued, or the strip falls back) - step 1 is in no memory to re-read.  Step 2: the
+//               running maximum A takes every float32 value; the repairs keep N = max of the values they wrote and
+//               LW = max of the values they LOWERED.  M = max(A, N) is the largest value any cell ever held, so it is
+//               a current value unless a cell that held it was lowered: only if LW >= M the finished strip is re-read.
 template <int MODE, bool EXACT, bool PACK = false, bool STATS = false, bool SYM = false, typename TI = plane_t,
-          typename TO = plane_t>
+          typename TO = plane_t, bool TRACE = false>
 __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI* __restrict__ inD,
                                             TO* __restrict__ outL, TO* __restrict__ outD, const FusedGeom& G,
                                             const PhysF32& P1_, const PhysF32& P2_, const PhysF64& P64,
                                             const double& La, const double& Lb,
                                             unsigned long long* __restrict__ zero_me, int zero_n,
-                                            unsigned int* __restrict__ pstats = nullptr, float thr_hi = 0.f) {
+                                            unsigned int* __restrict__ pstats = nullptr, float thr_hi = 0.f,
+                                            StatsDev* __restrict__ trace = nullptr, int trace_rescan = 0) {
     // LAG: step 2 runs one row further behind step 1, on results of earlier iterations only (see below).
     // Measured: exact kernels -5...-11 %, packed float32 -6 %, W = 256 float32 -4 %,
     // overlapped strips -1.5 %.  (-DDW_FUSED_LAG=0 builds the dependent order for comparison.)
@@ -133,6 +146,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     constexpr bool LAG = DW_FUSED_LAG != 0;
     constexpr bool ROT = MODE == kFusedRot, RING = MODE == kFusedRing;
     static_assert(!RING || (LAG && !PACK), "the ring exchange is written for the lagged loop of un-packed worlds");
+    static_assert(!TRACE || (LAG && !PACK && !STATS && !RING), "the trace form exists for un-packed overlapped / rotating strips");
     __shared__ float s_edge[RING ? 2 * 4 * 8 : 1];               // RING: [parity][wave][.w of lane 63 x4 | .x of lane 0 x4]
     __shared__ uint4 s_queue[EXACT ? 4 * kWaveQueueCap * 3 : 1];
     __shared__ unsigned int s_mm[EXACT ? 4 * kMismatchCap : 1];
@@ -283,6 +297,35 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     bool st_sure1 = false;
     const unsigned long long writes_mask = CHEAP ? lane_mask(writes) : 0ull;
     const float thr_c2 = EXACT ? thr_hi + 1.0f : thr_hi;
+    // TRACE accumulators (see the comment above fused2_body); tr_fix*: what the repairs change in the sums (their
+    // entries are not the sweeping lane's own cells: kept apart from the lane's accumulators)
+    dw_f32x2 tr_l1 = dw_f32x2(0.f), tr_d1 = dw_f32x2(0.f), tr_l2 = dw_f32x2(0.f), tr_d2 = dw_f32x2(0.f);
+    int tr_m1 = 0, tr_m2 = 0;                                   // maxima as bit patterns (non-negative float32 integers)
+    float tr_fix_l1 = 0.f, tr_fix_d1 = 0.f, tr_fix_l2 = 0.f, tr_fix_d2 = 0.f;
+    float tr_x1 = 0.f, tr_new2 = 0.f, tr_low2 = 0.f;
+    auto trace_patch2 = [&](float o, float n) {                 // a repair replaces the step-2 value o by n
+        tr_new2 = fmaxf(tr_new2, n);
+        if (n < o) tr_low2 = fmaxf(tr_low2, o);
+    };
+    auto trace_step1 = [&](const float* ol, const float* od, const TieT* tie) {
+        tr_l1 += dw_f32x2{ol[0], ol[1]} + dw_f32x2{ol[2], ol[3]};
+        tr_d1 += dw_f32x2{od[0], od[1]} + dw_f32x2{od[2], od[3]};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if constexpr (EXACT) {
+                const float m = fmaxf(ol[i], od[i]);
+                tr_m1 = max(tr_m1, __float_as_int(tie_lane(tie[i]) ? 0.f : m));
+            } else {
+                asm("v_max3_i32 %0, %0, %1, %2" : "+v"(tr_m1) : "v"(ol[i]), "v"(od[i]));
+            }
+        }
+    };
+    auto trace_step2 = [&](const float* ol, const float* od) {
+        tr_l2 += dw_f32x2{ol[0], ol[1]} + dw_f32x2{ol[2], ol[3]};
+        tr_d2 += dw_f32x2{od[0], od[1]} + dw_f32x2{od[2], od[3]};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm("v_max3_i32 %0, %0, %1, %2" : "+v"(tr_m2) : "v"(ol[i]), "v"(od[i]));
+    };
     // one row of the map with coefficient set P: (up, mid, down) -> new values; exact mode also queues
     // the near-tie cells (kind 1 = step 1, 2 = step 2; lrow = row index relative to grid row r0-2)
     auto row_map = [&](const PhysF32& P, const Row4& upL, const Row4& miL, const Row4& dnL, const Row4& upD,
@@ -428,6 +471,20 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
                     const NewCoverF64 o = cell_f64_lean(Pe, w);
                     const unsigned int kl = (unsigned)dw_round3_k(o.nl), kd = (unsigned)dw_round3_k(o.nd);
                     where = e0.y;
+                    if (TRACE && (e0.x != 1u || is_output((int)(where >> 16), (int)(where & 0xffffu)))) {
+                        const unsigned int f32v = unpack_ld(e2.w);
+                        const float pl = (float)(f32v & 0xffffu), pd = (float)(f32v >> 16);
+                        if (e0.x == 1u) {                            // F1: an owned step-1 cell's exact value
+                            tr_fix_l1 += (float)kl - pl;
+                            tr_fix_d1 += (float)kd - pd;
+                            tr_x1 = fmaxf(tr_x1, (float)(kl > kd ? kl : kd));
+                        } else {                                     // F2: the float32 value was the stored one
+                            tr_fix_l2 += (float)kl - pl;
+                            tr_fix_d2 += (float)kd - pd;
+                            trace_patch2(pl, (float)kl);
+                            trace_patch2(pd, (float)kd);
+                        }
+                    }
                     if (e0.x == 1u) {
                         mism = (kl | (kd << 16)) != unpack_ld(e2.w);
                         if (STATS && is_output((int)(where >> 16), (int)(where & 0xffffu))) {   // exact value of a tie cell
@@ -485,7 +542,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
         // which are all results of EARLIER iterations: the two row maps of an iteration are independent, so
         // their transcendental chains overlap instead of waiting for each other.  Step-1 row j then replaces
         // step-1 row j-3 in the window.
-        auto iter = [&](auto U, auto D1, auto D2, int j, auto ST) {
+        auto iter = [&](auto U, auto D1, auto D2, int j, auto ST, auto MINE) {   // MINE: step-1 row j is known to be an output row
             constexpr int u = decltype(U)::value;                  // u == j % 3
             constexpr bool do1 = decltype(D1)::value, do2 = decltype(D2)::value;
             constexpr bool st_on = STATS && decltype(ST)::value;   // (the quiet copy of the loop: statistics off)
@@ -505,6 +562,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
                 row_queue(SL[u], SL[(u + 1) % 3], SL[(u + 2) % 3], SD[u], SD[(u + 1) % 3], SD[(u + 2) % 3], l2, d2, tie2, 2,
                           j - 2);
                 if (st_on) stats_step2(sm2);
+                if constexpr (TRACE) trace_step2(l2, d2);
                 if (writes) {
                     const size_t off = woff + (size_t)(r0 + j - 4) * G.W + col;
                     stream_store4(outL + off, make_float4(l2[0], l2[1], l2[2], l2[3]));
@@ -514,6 +572,9 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
             if (do1) {
                 row_queue(IL[(u + 2) % 3], IL[u], IL[(u + 1) % 3], ID[(u + 2) % 3], ID[u], ID[(u + 1) % 3], l1, d1, tie1, 1, j);
                 if (st_on) stats_step1(sm1, l1, d1, tie1, j >= 2 && j <= nr + 1);
+                if constexpr (TRACE) {                              // step-1 rows of MY output cells only (wave-uniform)
+                    if (decltype(MINE)::value || (j >= 2 && j <= nr + 1)) trace_step1(l1, d1, tie1);
+                }
                 if constexpr (RING) {                               // both new rows in ONE exchange (one barrier per iteration)
                     const float4 v[4] = {make_float4(l1[0], l1[1], l1[2], l1[3]), make_float4(d1[0], d1[1], d1[2], d1[3]),
                                          widen4(nx.l), widen4(nx.d)};
@@ -529,15 +590,18 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
         };
         using Yes = std::true_type;
         using No = std::false_type;
-        iter(U1{}, Yes{}, No{}, 1, Yes{});                          // nr >= 1: rows 1..3 always exist
-        iter(U2{}, Yes{}, No{}, 2, Yes{});
-        iter(U0{}, Yes{}, No{}, 3, Yes{});
+        iter(U1{}, Yes{}, No{}, 1, Yes{}, No{});                    // nr >= 1: rows 1..3 always exist
+        iter(U2{}, Yes{}, No{}, 2, Yes{}, No{});
+        iter(U0{}, Yes{}, No{}, 3, Yes{}, No{});
         const int jend = nr + 2;
+        // TRACE: the loop stops one row earlier, so that every step-1 row it computes (j + 2 <= nr + 1) is an output row
+        // and the ownership test stays out of it; the tail then has up to three rows
+        const int jloop = TRACE ? jend - 1 : jend;
         int j = 4;
-        for (; j + 2 <= jend; j += 3) {                             // j % 3 == 1 at the top
-            iter(U1{}, Yes{}, Yes{}, j, Yes{});
-            iter(U2{}, Yes{}, Yes{}, j + 1, Yes{});
-            iter(U0{}, Yes{}, Yes{}, j + 2, Yes{});
+        for (; j + 2 <= jloop; j += 3) {                            // j % 3 == 1 at the top
+            iter(U1{}, Yes{}, Yes{}, j, Yes{}, Yes{});
+            iter(U2{}, Yes{}, Yes{}, j + 1, Yes{}, Yes{});
+            iter(U0{}, Yes{}, Yes{}, j + 2, Yes{}, Yes{});
             // wave-uniform and rare (see sweep_queue); not in the STATS variants, which are at their register budget: their
             // live values would spill on the main path (they keep one sweep at the end of the strip)
             if (EXACT && !STATS && __builtin_expect(nq >= (unsigned)flush_at, 0)) sweep_queue();
@@ -547,17 +611,20 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
             // the rest of the strip with the statistics switched off: a second copy of the row loop rather than a
             // branch around the statistics in the first (that one costs the exact kernels registers they do not have)
             for (; j + 2 <= jend; j += 3) {
-                iter(U1{}, Yes{}, Yes{}, j, No{});
-                iter(U2{}, Yes{}, Yes{}, j + 1, No{});
-                iter(U0{}, Yes{}, Yes{}, j + 2, No{});
+                iter(U1{}, Yes{}, Yes{}, j, No{}, No{});
+                iter(U2{}, Yes{}, Yes{}, j + 1, No{}, No{});
+                iter(U0{}, Yes{}, Yes{}, j + 2, No{}, No{});
             }
         }
-        if (j <= jend) { iter(U1{}, Yes{}, Yes{}, j, Yes{}); ++j; }   // (the last rows: statistics on again - they only grow)
-        if (j <= jend) { iter(U2{}, Yes{}, Yes{}, j, Yes{}); ++j; }
+        if (j <= jend) { iter(U1{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }   // (the last rows: statistics on again - they only grow)
+        if (j <= jend) { iter(U2{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }
+        if constexpr (TRACE) {
+            if (j <= jend) { iter(U0{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }
+        }
         // j == nr + 3: the last output row
-        if (j % 3 == 1) iter(U1{}, No{}, Yes{}, j, Yes{});
-        else if (j % 3 == 2) iter(U2{}, No{}, Yes{}, j, Yes{});
-        else iter(U0{}, No{}, Yes{}, j, Yes{});
+        if (j % 3 == 1) iter(U1{}, No{}, Yes{}, j, Yes{}, No{});
+        else if (j % 3 == 2) iter(U2{}, No{}, Yes{}, j, Yes{}, No{});
+        else iter(U0{}, No{}, Yes{}, j, Yes{}, No{});
     } else {
         // iteration j = 1 .. nr+2: step-1 row j (grid row r0-2+j) from input rows j-1, j, j+1; then, from j = 3
         // on, output row k = j-3 (local row j-1) from step-1 rows j-2, j-1, j
@@ -622,6 +689,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
             // ten in a row on nine lanes.
             unsigned int* s1 = reinterpret_cast<unsigned int*>(q);
             for (unsigned int m0 = 0; m0 < nmm; m0 += 2) {
+                if constexpr (TRACE) wait_row_stores_before_patching();   // the patches so far, before they are read back
                 __builtin_amdgcn_wave_barrier();
                 {
                     const unsigned int mi = lane / 25u, t = lane - mi * 25u;
@@ -665,6 +733,31 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
                             size_t wo;
                             locate(lrow, lc, wo, gr, gc);
                             const size_t off = wo + (size_t)gr * G.W + gc;
+                            if constexpr (TRACE) {
+                                // the stored values (row store or an earlier patch of this wave, all acknowledged or in
+                                // order behind each other), read past the vector cache.  Two mismatches share a pass: a
+                                // cell that depends on both is counted by the first one's lane only.
+                                const float ol_ = (float)__builtin_bit_cast(TO, __hip_atomic_load(reinterpret_cast<const unsigned short*>(outL + off),
+                                                                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                                const float od_ = (float)__builtin_bit_cast(TO, __hip_atomic_load(reinterpret_cast<const unsigned short*>(outD + off),
+                                                                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                                const float nl_ = (float)dw_round3_k(o.nl), nd_ = (float)dw_round3_k(o.nd);
+                                bool dup = false;
+                                if (mi == 1u) {
+                                    const unsigned int w0 = mm[m0];
+                                    const int dr = lrow - (int)(w0 >> 16);
+                                    int dc = lc - (int)(w0 & 0xffffu);
+                                    dc = dc < 0 ? -dc : dc;
+                                    if (ROT) dc = min(dc, 256 - dc);
+                                    dup = dr >= -1 && dr <= 1 && dc <= 1;
+                                }
+                                if (!dup) {
+                                    tr_fix_l2 += nl_ - ol_;
+                                    tr_fix_d2 += nd_ - od_;
+                                }
+                                trace_patch2(ol_, nl_);
+                                trace_patch2(od_, nd_);
+                            }
                             outL[off] = (TO)(float)dw_round3_k(o.nl);
                             outD[off] = (TO)(float)dw_round3_k(o.nd);
                         }
@@ -675,6 +768,12 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
             // overflow fallback: every output cell of the strip, two float64 steps from the inputs
             // (RING: plus the column on either side, whose step-2 values depend on this wave's - unverified - step-1 edge)
             const int ncol = ROT ? 256 : (RING ? 258 : 248);
+            if constexpr (TRACE) {                               // both steps' reductions from scratch
+                tr_l1 = tr_d1 = tr_l2 = tr_d2 = dw_f32x2(0.f);
+                tr_m1 = tr_m2 = 0;
+                tr_fix_l1 = tr_fix_d1 = tr_fix_l2 = tr_fix_d2 = 0.f;
+                tr_x1 = tr_new2 = tr_low2 = 0.f;
+            }
             for (int i = lane; i < nr * ncol; i += 64) {
                 const int lrow = 2 + i / ncol, lc = (ROT ? 0 : (RING ? -1 : 4)) + i % ncol;
                 if (!is_output(lrow, lc)) continue;
@@ -686,6 +785,16 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
                 const size_t off = wo + (size_t)gr * G.W + gc;
                 outL[off] = (TO)kl;
                 outD[off] = (TO)kd;
+                if constexpr (TRACE) {
+                    const unsigned int w1 = exact1_word(inL + wo, inD + wo, G.H, G.W, gr, gc, Pa);
+                    const float l1 = (float)(w1 & 0xffffu), d1 = (float)(w1 >> 16);
+                    tr_fix_l1 += l1;
+                    tr_fix_d1 += d1;
+                    tr_x1 = fmaxf(tr_x1, fmaxf(l1, d1));
+                    tr_fix_l2 += kl;
+                    tr_fix_d2 += kd;
+                    tr_new2 = fmaxf(tr_new2, fmaxf(kl, kd));
+                }
                 if (STATS) {                                     // step-1 maximum from scratch; no step-2 count
                     const unsigned int w1 = exact1_word(inL + wo, inD + wo, G.H, G.W, gr, gc, Pa);
                     atomicMax(&pstats[2 * world_of(lc)], (w1 & 0xffffu) > (w1 >> 16) ? (w1 & 0xffffu) : (w1 >> 16));
@@ -697,6 +806,59 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
             st_c2w = 0;
         }
         st_nmm = nmm;
+    }
+    if constexpr (TRACE) {
+        // This wave's contribution to rows t and t + 1 (six atomics per strip).  A strip that fell back holds everything
+        // in the repairs' accumulators (the lanes' own ones were cleared).
+        const bool own = writes && !redo;
+        float l1 = own ? tr_l1.x + tr_l1.y : 0.f, d1 = own ? tr_d1.x + tr_d1.y : 0.f;
+        float l2 = own ? tr_l2.x + tr_l2.y : 0.f, d2 = own ? tr_d2.x + tr_d2.y : 0.f;
+        float m1 = own ? __int_as_float(tr_m1) : 0.f, m2 = own ? __int_as_float(tr_m2) : 0.f;
+        if (EXACT) {
+            l1 += tr_fix_l1; d1 += tr_fix_d1; l2 += tr_fix_l2; d2 += tr_fix_d2;
+            m1 = fmaxf(m1, tr_x1);
+        }
+        m1 = wave_max(m1);
+        m2 = wave_max(m2);
+        if (EXACT) {
+            m2 = fmaxf(m2, wave_max(tr_new2));
+            const float lw = wave_max(tr_low2);
+            if (__builtin_expect(!redo && (lw >= m2 || trace_rescan), 0)) {
+                // a cell that held the largest value was lowered: the finished, patched strip is re-read (every row
+                // store and patch of this wave has reached L2; agent-scope loads read past the vector cache)
+                wait_row_stores_before_patching();
+                float m = 0.f;
+                for (int k0 = 0; k0 < nr; k0 += 8) {
+                    unsigned long long wl[8], wd[8];
+#pragma unroll
+                    for (int jj = 0; jj < 8; ++jj) {
+                        const int kk = min(k0 + jj, nr - 1);
+                        const size_t off = woff + (size_t)(r0 + kk) * G.W + col;
+                        wl[jj] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(outL + off), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+                        wd[jj] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(outD + off), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+                    }
+#pragma unroll
+                    for (int jj = 0; jj < 8; ++jj) {
+                        const float4 fl = widen4(__builtin_bit_cast(dw_f16x4, wl[jj])), fd = widen4(__builtin_bit_cast(dw_f16x4, wd[jj]));
+                        m = fmaxf(m, fmaxf(fmaxf(fmaxf(fl.x, fl.y), fmaxf(fl.z, fl.w)), fmaxf(fmaxf(fd.x, fd.y), fmaxf(fd.z, fd.w))));
+                    }
+                }
+                m2 = wave_max(writes ? m : 0.f);
+            }
+        }
+        l1 = wave_sum(l1); d1 = wave_sum(d1); l2 = wave_sum(l2); d2 = wave_sum(d2);
+        if (lane == 0) {
+            StatsDev* const t1 = trace + b;
+            StatsDev* const t2 = t1 + G.B;
+            atomicMax(&t1->max_k, (unsigned int)m1);
+            atomicAdd(&t1->sum_l, (unsigned long long)l1);
+            atomicAdd(&t1->sum_d, (unsigned long long)d1);
+            atomicMax(&t2->max_k, (unsigned int)m2);
+            atomicAdd(&t2->sum_l, (unsigned long long)l2);
+            atomicAdd(&t2->sum_d, (unsigned long long)d2);
+        }
     }
     if (STATS) {
         // This wave's contribution.  The counted row groups hold a non-tie step-2 value > thr_hi, i.e. a
@@ -788,6 +950,44 @@ void step_stream_fused2_exact(FusedExactArgs A) {
     const PhysF32 P2 = with_lum(A.P1, A.lum2);
     fused2_body<MODE, true, PACK, STATS, SYM>(A.inL, A.inD, A.outL, A.outD, A.G, A.P1, P2, cold.P64, cold.La, cold.Lb, A.zero_me,
                                              A.zero_n, A.pstats, A.thr_hi);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The TRACE form of the step pairs (dw_step_n_trace): entry points of their own, so that the kernels above keep
+// their code and their register budgets.  The trace accumulators do not fit those budgets: the float32-only kernels
+// are planned for 3 waves per SIMD, the exact ones for 2 (no scratch on the row loop's main path in either).
+// ---------------------------------------------------------------------------------------------
+#ifndef DW_TRACE_FAST_WAVES
+#define DW_TRACE_FAST_WAVES 3
+#endif
+#ifndef DW_TRACE_EXACT_WAVES
+#define DW_TRACE_EXACT_WAVES 2
+#endif
+template <int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DW_TRACE_FAST_WAVES, DW_TRACE_FAST_WAVES)))
+void trace_pair_fast(const plane_t* __restrict__ inL, const plane_t* __restrict__ inD, plane_t* __restrict__ outL,
+                     plane_t* __restrict__ outD, FusedGeom G, PhysF32 P1, PhysF32 P2,
+                     unsigned long long* __restrict__ zero_me, int zero_n, StatsDev* __restrict__ trace) {
+    const PhysF64 dummy{};
+    const double zero = 0.0;
+    fused2_body<MODE, false, false, false, false, plane_t, plane_t, true>(inL, inD, outL, outD, G, P1, P2, dummy, zero, zero,
+                                                                           zero_me, zero_n, nullptr, 0.f, trace, 0);
+}
+
+struct TraceExactArgs {
+    FusedExactArgs F;                                             // (pstats / thr_hi unused)
+    StatsDev* trace;                                              // row t of the series; row t + 1 is G.B records further
+    int rescan;                                                   // tests: every strip re-reads its step-2 maximum
+};
+
+template <int MODE, bool SYM = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DW_TRACE_EXACT_WAVES, DW_TRACE_EXACT_WAVES)))
+void trace_pair_exact(TraceExactArgs A) {
+    const FusedExactArgs& cold = kernarg_struct<TraceExactArgs>().F;
+    const PhysF32 P2 = with_lum(A.F.P1, A.F.lum2);
+    fused2_body<MODE, true, false, false, SYM, plane_t, plane_t, true>(A.F.inL, A.F.inD, A.F.outL, A.F.outD, A.F.G, A.F.P1, P2,
+                                                                       cold.P64, cold.La, cold.Lb, A.F.zero_me, A.F.zero_n,
+                                                                       nullptr, 0.f, A.trace, A.rescan);
 }
 
 }  // namespace dw

@@ -168,6 +168,16 @@ class Engine:
                                   int(bool(use_device_actions))))
         return Lc.value
 
+    def step_n_trace(self, L_schedule):
+        """`len(L_schedule)` agent-free steps, step t with luminosity `L_schedule[t]`, and the per-step, per-world
+        reductions of the whole run: an array of shape (n, B), dtype `_ffi.STATS_DTYPE`, whose row t is what `reduce()`
+        would return after step t (`reserved` unspecified).  Recorded on the device, one download at the end."""
+        Ls = np.ascontiguousarray(L_schedule, dtype=np.float64).reshape(-1)
+        out = np.zeros((Ls.size, self.B), dtype=_ffi.STATS_DTYPE)
+        self._check(self._lib.dw_step_n_trace(self._h, int(Ls.size), _ffi.ptr_d(Ls),
+                                        out.ctypes.data_as(C.POINTER(DwWorldStats))))
+        return out
+
     def last_step_n_timing(self):
         """(ms spent in the fused step-pair launches of the last step_n call, their number, plane element bytes)."""
         ms, n, eb = C.c_float(0), C.c_int32(0), C.c_int32(0)

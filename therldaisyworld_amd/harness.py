@@ -223,6 +223,50 @@ def _advance_host_scalars(env, executed):
     env._invalidate()
 
 
+RAMP_ALIVE_THRESHOLD = 0.005      # the notebook's test for a living biosphere: max cover > 0.005
+
+
+def _ramp_series(env, nsteps, run_trace):
+    """The host side of `simulate_ramp`: the schedule of the next `nsteps` steps, ONE call `run_trace(L_schedule)` ->
+    (n, B) records of dtype `_ffi.STATS_DTYPE` (the engine's `step_n_trace`), then the environment's scalars advanced as
+    `nsteps` calls of `env.step()` would have."""
+    if env.n_agents:
+        raise ValueError("simulate_ramp is for agent-free ensembles (n_agents == 0): with agents the reference's step(None) "
+                         "still grazes with action 0 - use simulate_lifespan")
+    n = int(nsteps)
+    L = np.asarray(_luminosity_schedule(env, n), dtype=np.float64)
+    stats = run_trace(L)
+    _advance_host_scalars(env, n)
+    cells = float(env.dim) * float(env.dim)
+    max_cover = stats["max_k"] / 1000.0
+    return {"L": L,
+            "mean_light": stats["sum_light_k"] / 1000.0 / cells,
+            "mean_dark": stats["sum_dark_k"] / 1000.0 / cells,
+            "max_cover": max_cover,
+            "alive": max_cover > RAMP_ALIVE_THRESHOLD,
+            "stats": stats}
+
+
+def simulate_ramp(env, nsteps, obs=None):
+    """The time series of an agent-free ensemble over the next `nsteps` steps of its luminosity ramp - the curves of
+    the reference's notebooks (daisy/notebook_helpers.py:50-54 appends `env.grid[:, 1].mean()` per step) without a host
+    round trip per step: the per-step, per-world reductions are recorded on the device (`dw_step_n_trace`) and come
+    down once.  `obs=None`: reset the environment first, as `simulate_lifespan` does.
+
+    Returns a dict: `L` (n,) the luminosity each step used; `mean_light`, `mean_dark` (n, B) float64; `max_cover`
+    (n, B); `alive` (n, B) bool, the notebook's `max > 0.005`; `stats` the raw (n, B) records (exact per-mille
+    integers).  Afterwards `env.grid`, `env.step()`, `env.L`, `env.step_count` ... continue as if the steps had been
+    taken one by one."""
+    if env.n_agents:
+        raise ValueError("simulate_ramp is for agent-free ensembles (n_agents == 0): with agents the reference's step(None) "
+                         "still grazes with action 0 - use simulate_lifespan")
+    if obs is None:
+        env.reset()
+    eng = env._ensure_engine()
+    env._sync_to_device()
+    return _ramp_series(env, nsteps, eng.step_n_trace)
+
+
 def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_chunk):
     """The step loop shared by the two fitness harnesses: chunks of steps device-resident
     (``dw_run_episode_mlp``), the reference's per-step float64 bookkeeping done by `after_chunk(rewards,

@@ -9,6 +9,7 @@ For every kernel whose (demangled) name contains SUBSTR: VGPRs, AGPRs, SGPRs, sp
 LDS bytes, occupancy, code length; with --loop also the instruction-class histogram of the largest
 loop body (the block between the last backward branch target and its branch) and the lines that touch
 scratch memory.  Runs in the build container (no GPU).
+The step-pair kernels and their TRACE forms side by side:  --build --loop --kernel fused2 ;  --loop --kernel trace_pair
 """
 from __future__ import annotations
 
