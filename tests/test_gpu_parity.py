@@ -591,14 +591,16 @@ def test_lifespan_harness_random_configurations_vs_notebook_loop_on_oracle(amd, 
     assert ok, log
 
 
-@pytest.mark.parametrize("seed,case", [(603, 26), (603, 3), (601, 17), (602, 44), (605, 120), (607, 9)])
+@pytest.mark.parametrize("seed,case", [(603, 26), (603, 3), (601, 17), (602, 44), (605, 120), (607, 9),
+                                       (611, 50), (611, 61), (611, 10), (611, 90)])
 def test_exact_mode_random_configurations_vs_c_oracle(amd, monkeypatch, seed, case):
     """A slice of tools/fuzz_exact.py: random shape / constants / upload format / luminosity schedule, planes AND
     reductions against the float64 C oracle.  (603, 26) is the case that found a round-3 regression: packed strips
     (W = 128) with the repair queue cut to one entry - a strip swept its queue inside the row loop, sent the sweep's
     sum corrections to the world's counters, overflowed later, was recomputed whole and counted those corrections
     twice (sum of light cover off by one); the corrections of packed strips now wait in LDS until the strip is known
-    to finish without an overflow."""
+    to finish without an overflow.  The (611, .) cases draw a forced strip height (the fuzz's side generator): rotating strips
+    at 32 rows, overlapped W = 512 at 64, packed W = 64 at 64 and the W = 1024 ring at 64; the six older pairs draw none."""
     import importlib.util
     import os
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "fuzz_exact.py")

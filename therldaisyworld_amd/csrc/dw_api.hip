@@ -65,11 +65,15 @@ enum UnqOwner { OWN_NONE = 0, OWN_CUR = 1, OWN_PREV = 2 };
 // its whole life whatever the environment does afterwards - and reported by dw_kernel_info when any is set.  None changes
 // results.  The DW_TEST_* hooks (shrunk queues, injected allocation failures, forced fallbacks) are honoured only when
 // DW_TEST_HOOKS is set as well: a stray variable in a user's environment cannot inject failures.
+//   DW_STRIP_ROWS=n        rows per wave-strip of the steady-state, step-pair AND first-step kernels instead of strip_rows()'s
+//                          choice (the first-step kernel: at most 64, the height its float32 partial sums stay exact at)
+//   DW_TEST_TRACE_ROWS=n   (test hook) dw_step_n_trace holds n rows of the series on the device at a time (rounded down to
+//                          even, at least 2) instead of 32 MiB of them: multi-chunk runs with a handful of worlds
 struct Switches {
     bool no_sym = false, no_pack = false, no_fuse = false, no_ring = false, no_episode_kernel = false,
          no_episode_wave = false, no_agent_fuse = false, no_agent_preapply = false, first_f64 = false,
          first_generic = false, force_rescan = false, test_hooks = false;
-    int pack_min_strips = -1, strip_rows = 0, tile_rpt = 0, queue_cap = -1, mismatch_cap = -1;
+    int pack_min_strips = -1, strip_rows = 0, tile_rpt = 0, queue_cap = -1, mismatch_cap = -1, trace_rows = 0;
     double first_slack = -1.0;
     char kernel[16] = {0};           // DW_KERNEL: "tiled" | "stream"
     char text[256] = {0};            // what was set, for dw_kernel_info
@@ -95,6 +99,7 @@ static Switches read_switches() {
     num("DW_PACK_MIN_STRIPS", w.pack_min_strips, false); num("DW_STRIP_ROWS", w.strip_rows, false);
     num("DW_TILE_RPT", w.tile_rpt, false);
     num("DW_TEST_QUEUE_CAP", w.queue_cap, true); num("DW_TEST_MISMATCH_CAP", w.mismatch_cap, true);
+    num("DW_TEST_TRACE_ROWS", w.trace_rows, true);
     if (test_hook("DW_TEST_FORCE_RESCAN")) { w.force_rescan = true; note("DW_TEST_FORCE_RESCAN", nullptr); }
     if (const char* e = test_hook("DW_TEST_FIRST_SLACK")) { w.first_slack = std::atof(e); note("DW_TEST_FIRST_SLACK", e); }
     if (const char* e = std::getenv("DW_KERNEL")) { snprintf(w.kernel, sizeof(w.kernel), "%s", e); note("DW_KERNEL", e); }
@@ -678,7 +683,9 @@ static StepPlan plan_steps(const dw_params& p, const Switches& sw) {
         fg.wpr = s.packed ? wpr : 1;
         fg.ncs = s.packed ? 1 : (p.width + 255) / 256;
         const long groups = s.packed ? (p.batch + fg.wpr - 1) / fg.wpr : p.batch;
-        fg.SR = strip_rows(groups * fg.ncs, p.height, 4096);   // four strips per SIMD
+        // four strips per SIMD; DW_STRIP_ROWS overrides (experiments, tests), never above the 64 rows FirstGeom::SR allows
+        const int want = sw.strip_rows < 64 ? sw.strip_rows : 64;
+        fg.SR = sw.strip_rows >= 1 ? (p.height < want ? p.height : want) : strip_rows(groups * fg.ncs, p.height, 4096);
         fg.nrs = (p.height + fg.SR - 1) / fg.SR;
         fg.nstrips = (int)(groups * fg.nrs * fg.ncs);
     }
@@ -1475,8 +1482,9 @@ int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_w
     HIPCHK(hipSetDevice(h->prm.device));
     const size_t B = (size_t)h->prm.batch, row_bytes = sizeof(StatsDev) * B;
     // rows of the series held on the device at a time: the whole run up to 32 MiB (512 steps of 1024 worlds: 12 MiB),
-    // longer runs in chunks of that size (an even number of rows, at least two: a step pair fills two)
-    size_t rows = ((size_t)32 << 20) / row_bytes & ~(size_t)1;
+    // longer runs in chunks of that size (an even number of rows, at least two: a step pair fills two);
+    // DW_TEST_TRACE_ROWS: that many rows instead (tests: runs of several chunks with a handful of worlds)
+    size_t rows = (h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / row_bytes) & ~(size_t)1;
     rows = rows < 2 ? 2 : rows;
     rows = rows > (size_t)nsteps ? (size_t)nsteps : rows;
     if (int rc = alloc_group(h, "the trace buffer", {{h->trace_d, rows * row_bytes}})) return rc;
@@ -2431,6 +2439,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_step_n_trace takes (StepPlan::trace_pairs)
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, pl.trace_pairs ? "; trace: step pairs" : "; trace: single steps");
+    }
+    if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; first step: wave-strip=%dx256", pl.first_geom.SR);
     }
     if (h->sw.text[0]) {                                        // the switches this handle was created under
         const size_t n = std::strlen(buf);

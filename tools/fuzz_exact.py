@@ -3,7 +3,8 @@
 tiled, wave-strip rotate / halo / general / packed, fused pairs), random physics constants in the ranges
 callers use, random un-quantised initial states in all three upload formats (the first step: step_first_stream /
 step_generic), random luminosity schedules, in a fifth of the cases with the LDS queue / mismatch list shrunk so that
-the overflow fallbacks run; planes and reductions compared bit for bit after every run.
+the overflow fallbacks run, in half of them with the strip height forced to 16, 32 or 64 rows; planes and reductions
+compared bit for bit after every run.
 The audit of the tie bound (dw_audit_tie_bound) is evaluated along the way.
 
 usage: fuzz_exact.py [cases=100] [seed=1] [only=<case index>]"""
@@ -53,7 +54,14 @@ def run_case(seed, i, log=None, explain=False):
     # i.e. small batches of narrow worlds take the tiled / generic kernels instead of the packed wave-strips
     if np.random.RandomState((seed * 7919 + i * 104729 + 1) % (2 ** 32)).rand() < 0.33:
         caps = dict(caps, DW_PACK_MIN_STRIPS="512")
-    saved = {k: os.environ.pop(k, None) for k in ("DW_TEST_QUEUE_CAP", "DW_TEST_MISMATCH_CAP")}
+    # another side generator: the strip height of the wave-strip kernels (first step, single steps, step pairs) - the
+    # library's own choice for these small batches is always 8 rows; half of the cases force 16, 32 or 64 (DW_STRIP_ROWS).
+    # (The salt 112 is the first for which the six pairs that tests/test_gpu_parity.py pinned before this generator
+    # existed draw "the library's own choice", i.e. run exactly as they always did.)
+    rows = int(np.random.RandomState((seed * 15485863 + i * 32452843 + 112) % (2 ** 32)).choice([0, 0, 0, 16, 32, 64]))
+    if rows:
+        caps = dict(caps, DW_STRIP_ROWS=str(rows))
+    saved = {k: os.environ.pop(k, None) for k in ("DW_TEST_QUEUE_CAP", "DW_TEST_MISMATCH_CAP", "DW_STRIP_ROWS")}
     saved["DW_PACK_MIN_STRIPS"] = os.environ.get("DW_PACK_MIN_STRIPS")
     os.environ.update(caps)
     try:
