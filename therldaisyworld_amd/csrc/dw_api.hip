@@ -318,6 +318,14 @@ static void release_unquantised(dw_handle* h) {
     h->U32D.reset();
 }
 
+// The first fused launch of a run ends the life of an un-quantised PREVIOUS state (after it the retained state is two
+// steps back anyway): drop it in front of the run, so that release_unquantised's synchronise + free of 128 GiB at the
+// north-star shape happen in front of dw_step_n's timed window and not inside it.
+static void drop_unquantised_previous(dw_handle* h) {
+    if (h->unq == OWN_PREV) { h->unq = OWN_NONE; h->stepped = false; }
+    release_unquantised(h);
+}
+
 static int ensure_u32(dw_handle* h) {
     const size_t n = sizeof(float) * h->cells;
     return alloc_group(h, "two float32 planes", {{h->U32L, n}, {h->U32D, n}});
@@ -372,9 +380,6 @@ static PhysF64 make_f64(const dw_params& p, double L) {
     return P;
 }
 
-#ifndef DW_TIE_BOUND
-#define DW_TIE_BOUND 3
-#endif
 // kbeta = 1 / sqrt(g To^2) in float64 (g = 0: a denominator so large that w^2 vanishes)
 static double cbeta_host(const dw_params& p) {
     const double cbeta = p.g * p.temp_optimal * p.temp_optimal;
@@ -446,15 +451,6 @@ static PhysF32 derive_f32(const dw_params& p, double L, int hb_cap = 40) {
     const double pos = (std::fmax(a1, 0.0) + std::fmax(a2, 0.0)) * 8 * kmax + (std::fmax(a3, 0.0) + std::fmax(a4, 0.0)) * kmax;
     const double neg = (std::fmin(a1, 0.0) + std::fmin(a2, 0.0)) * 8 * kmax + (std::fmin(a3, 0.0) + std::fmin(a4, 0.0)) * kmax;
     const double emax = std::fmax(c0l, c0d) + pos, emin = std::fmin(c0l, c0d) + neg;
-#if DW_TIE_BOUND == 2
-    // round-2 constants (kept for A/B runs: -DDW_TIE_BOUND=2)
-    const double dabs = std::fmax(std::fabs(std::pow(std::fmax(1.0 + emax, 1e-6), 0.25) - 1.0),
-                                  std::fabs(std::pow(std::fmax(1.0 + emin, 1e-6), 0.25) - 1.0));
-    const double cb = p.g * p.temp_optimal * p.temp_optimal;
-    const double safety = 1.25;
-    const double A0 = safety * (0.25 * kmax * std::fabs(p.dt) * cb * dabs * de_abs + 4.0 * u * kmax * 0.25 + 2e-5);
-    const double eA = safety * 9.0 * u, eK0d = safety * 5.0 * u, eK1d = safety * 28.0 * u;
-#else
     // Round-3 derivation (every step numbered there).  With v = 1 + e, s = sqrt(v), y = sqrt(s),
     // D = kbeta (y+1)(s+1), w = e/D, om = w^2, the hardware's sqrt / rcp at 1 ulp (relative 2u) and every other
     // operation correctly rounded (relative u):
@@ -493,7 +489,6 @@ static PhysF32 derive_f32(const dw_params& p, double L, int hb_cap = 40) {
     const double eA = safety * 13.0 * u;
     const double eK0d = safety * (6.0 * std::fabs(p.p) + pu + kbmax + 8.0 * std::fabs(p.gamma)) * u;
     const double eK1d = safety * ((6.0 * std::fabs(p.p) + pu) * u + kbmax * (u + 2.0 * ew));
-#endif
     auto up = [](double v) { float f = (float)v; return (double)f < v ? std::nextafterf(f, INFINITY) : f; };   // never round a bound DOWN
     P.tie_lo = (float)(0.5 - A0);
     if ((double)P.tie_lo > 0.5 - A0) P.tie_lo = std::nextafterf(P.tie_lo, -INFINITY);
@@ -874,17 +869,21 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
     const dw_params& p = h->prm;
     const StepPlan& pl = h->plan;
     const int in = h->cur, out = 1 - h->cur;
+    const bool exact = p.precision == DW_PRECISION_EXACT;
     PhysF32 P1, P2;
-    if (p.precision == DW_PRECISION_EXACT) derive_f32_pair(p, L1, L2, &P1, &P2);
+    if (exact) derive_f32_pair(p, L1, L2, &P1, &P2);
     else { P1 = derive_f32(p, L1); P2 = derive_f32(p, L2); }
     unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get());
     const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
     const FusedGeom& g = pl.fgeom;
     const dim3 grid((unsigned)g.chunk * 8u);
-    if (trace && p.precision == DW_PRECISION_EXACT) {
-        const TraceExactArgs A{{h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P1, lum_part(P2), zero_me,
-                                zero_n, nullptr, 0.f, make_f64(p, L1), L1, L2},
-                               trace, h->sw.force_rescan ? 1 : 0};
+    const plane_t *inL = h->L16[in].get(), *inD = h->D16[in].get();
+    plane_t *outL = h->L16[out].get(), *outD = h->D16[out].get();
+    auto exact_args = [&] {
+        return FusedExactArgs{inL, inD, outL, outD, g, P1, lum_part(P2), zero_me, zero_n, pstats, thr_hi, make_f64(p, L1), L1, L2};
+    };
+    if (trace && exact) {
+        const TraceExactArgs A{exact_args(), trace, h->sw.force_rescan ? 1 : 0};
         with_int<kFusedRot, kFusedOvl>(pl.fused_mode, [&](auto MODE) {
             with_bool(pl.sym_albedo, [&](auto SYM) {
                 hipLaunchKernelGGL((trace_pair_exact<MODE, SYM>), grid, dim3(256), 0, h->stream, A);
@@ -892,12 +891,11 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
         });
     } else if (trace) {
         with_int<kFusedRot, kFusedOvl>(pl.fused_mode, [&](auto MODE) {
-            hipLaunchKernelGGL((trace_pair_fast<MODE>), grid, dim3(256), 0, h->stream, h->L16[in].get(), h->D16[in].get(),
-                               h->L16[out].get(), h->D16[out].get(), g, P1, P2, zero_me, zero_n, trace);
+            hipLaunchKernelGGL((trace_pair_fast<MODE>), grid, dim3(256), 0, h->stream, inL, inD, outL, outD, g, P1, P2, zero_me,
+                               zero_n, trace);
         });
-    } else if (p.precision == DW_PRECISION_EXACT) {
-        const FusedExactArgs A{h->L16[in].get(), h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P1, lum_part(P2), zero_me, zero_n,
-                               pstats, thr_hi, make_f64(p, L1), L1, L2};
+    } else if (exact) {
+        const FusedExactArgs A = exact_args();
         with_bool(pstats != nullptr, [&](auto STATS) {
             with_fused_layout(pl, [&](auto MODE, auto PACK) {
                 with_bool(pl.sym_albedo, [&](auto SYM) {
@@ -908,9 +906,8 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
     } else {
         with_bool(pstats != nullptr, [&](auto STATS) {
             with_fused_layout(pl, [&](auto MODE, auto PACK) {
-                hipLaunchKernelGGL((step_stream_fused2<MODE, PACK, STATS>), grid, dim3(256), 0, h->stream, h->L16[in].get(),
-                                   h->D16[in].get(), h->L16[out].get(), h->D16[out].get(), g, P1, P2, zero_me, zero_n, pstats,
-                                   thr_hi);
+                hipLaunchKernelGGL((step_stream_fused2<MODE, PACK, STATS>), grid, dim3(256), 0, h->stream, inL, inD, outL, outD, g,
+                                   P1, P2, zero_me, zero_n, pstats, thr_hi);
             });
         });
     }
@@ -1439,11 +1436,7 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
         // wide grids: pairs of steps share one HBM round trip; the last one or two steps are ordinary launches
         // so that the retained previous state is the true predecessor.  HIP events around the run of fused
         // launches feed dw_last_step_n_timing (the dominant kernel's duration, measured on its own stream).
-        // The first fused launch ends the life of an un-quantised PREVIOUS state (after it the retained state is two
-        // steps back anyway): drop it here, so that release_unquantised's synchronise + free of 128 GiB at the
-        // north-star shape happen in front of the timed window and not inside it.
-        if (h->unq == OWN_PREV) { h->unq = OWN_NONE; h->stepped = false; }
-        release_unquantised(h);
+        drop_unquantised_previous(h);
         HIPCHK(hipEventRecord(h->evf0, h->stream));
         int launched = 0;
         while (nsteps - s0 >= 3) {
@@ -1499,9 +1492,8 @@ int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_w
             // a pair where dw_step_n would issue one (the closing one or two steps stay ordinary launches: the retained
             // previous state is the true predecessor) and both rows lie in this chunk
             if (h->plan.trace_pairs && cur_quantised(h) && nsteps - t >= 3 && t + 2 <= c0 + cn) {
-                if (first_pair) {                               // (as dw_step_n: an un-quantised previous state ends here)
-                    if (h->unq == OWN_PREV) { h->unq = OWN_NONE; h->stepped = false; }
-                    release_unquantised(h);
+                if (first_pair) {
+                    drop_unquantised_previous(h);
                     first_pair = false;
                 }
                 if (int rc = launch_forward_fused2(h, L_schedule[t], L_schedule[t + 1], nullptr, 0.f, row)) return rc;

@@ -119,11 +119,7 @@ __device__ __forceinline__ void cells4(const PhysF32& P, const Row4& upL, const 
                                        const Row4& upD, const Row4& miD, const Row4& dnD, float* ol, float* od,
                                        F* tie) {
 #pragma clang fp contract(off)
-#ifdef DW_SCALAR_CELLS
-    using T = float;
-#else
     using T = dw_f32x2;
-#endif
     constexpr int N = Lanes<T>::N;
 #pragma unroll
     for (int i = 0; i < 4; i += N) {

@@ -105,8 +105,8 @@ constexpr int kMismatchCap = 64;            // float32 step-1 mismatches per wav
 // cone was uncertain.  Queue / mismatch-list overflow: the whole strip is recomputed in float64.
 // Fused launches leave the per-world reductions untouched (dw_step_n always ends with a single step,
 // which recomputes them), they only keep the double-buffer protocol.
-// LAG (all kernels): step 2 runs one row further behind step 1, so that the two row maps of an iteration
-// are independent (see the loop below).
+// Step 2 runs one row further behind step 1 than it has to, so that the two row maps of an iteration are
+// independent (see the loop below).
 // PACK (with ROT): narrow worlds (W | 256) side by side in the wave row, as in step_stream<halo=packed>:
 // every lane has its own world, the horizontal wrap is a rotation inside the world's lane group, and a
 // local column lc of the wave row decodes to (world, column) = (lc / W, lc % W).
@@ -137,16 +137,9 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
                                             unsigned long long* __restrict__ zero_me, int zero_n,
                                             unsigned int* __restrict__ pstats = nullptr, float thr_hi = 0.f,
                                             StatsDev* __restrict__ trace = nullptr, int trace_rescan = 0) {
-    // LAG: step 2 runs one row further behind step 1, on results of earlier iterations only (see below).
-    // Measured: exact kernels -5...-11 %, packed float32 -6 %, W = 256 float32 -4 %,
-    // overlapped strips -1.5 %.  (-DDW_FUSED_LAG=0 builds the dependent order for comparison.)
-#ifndef DW_FUSED_LAG
-#define DW_FUSED_LAG 1
-#endif
-    constexpr bool LAG = DW_FUSED_LAG != 0;
     constexpr bool ROT = MODE == kFusedRot, RING = MODE == kFusedRing;
-    static_assert(!RING || (LAG && !PACK), "the ring exchange is written for the lagged loop of un-packed worlds");
-    static_assert(!TRACE || (LAG && !PACK && !STATS && !RING), "the trace form exists for un-packed overlapped / rotating strips");
+    static_assert(!RING || !PACK, "the ring exchange is written for un-packed worlds");
+    static_assert(!TRACE || (!PACK && !STATS && !RING), "the trace form exists for un-packed overlapped / rotating strips");
     __shared__ float s_edge[RING ? 2 * 4 * 8 : 1];               // RING: [parity][wave][.w of lane 63 x4 | .x of lane 0 x4]
     __shared__ uint4 s_queue[EXACT ? 4 * kWaveQueueCap * 3 : 1];
     __shared__ unsigned int s_mm[EXACT ? 4 * kMismatchCap : 1];
@@ -286,7 +279,6 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     // is exactly thr + 1; st_c2w = wave total of output row groups whose float32 step-2 maximum is >= thr + 2 (exact
     // mode; float32-only mode: > thr).  Packed worlds keep one maximum / count per lane (several worlds per wave).
     constexpr bool CHEAP = STATS && !PACK;
-    static_assert(LAG || !CHEAP, "the dependent-order loop (DW_FUSED_LAG=0, experiments) keeps the per-lane statistics");
     float st_m1 = 0.f, st_x1 = 0.f;
     unsigned int st_c2 = 0, st_nmm = 0, st_c2w = 0;
     // CHEAP: both results are only ever read as predicates by agents_lookahead_patch - "some step-1 value > thr" and
@@ -326,38 +318,10 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
 #pragma unroll
         for (int i = 0; i < 4; ++i) asm("v_max3_i32 %0, %0, %1, %2" : "+v"(tr_m2) : "v"(ol[i]), "v"(od[i]));
     };
-    // one row of the map with coefficient set P: (up, mid, down) -> new values; exact mode also queues
-    // the near-tie cells (kind 1 = step 1, 2 = step 2; lrow = row index relative to grid row r0-2)
-    auto row_map = [&](const PhysF32& P, const Row4& upL, const Row4& miL, const Row4& dnL, const Row4& upD,
-                       const Row4& miD, const Row4& dnD, float4& nl, float4& nd, int kind, int lrow,
-                       const TieT* use, float* sure_max = nullptr) {
-        float ol[4], od[4];
-        TieT tie[4];
-        cells4<EXACT, SYM, TieT>(P, upL, miL, dnL, upD, miD, dnD, ol, od, tie);
-        if (EXACT) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) tie[i] = tie[i] & use[i];
-        }
-        if (STATS && sure_max) {
-            if (CHEAP) {                                         // the row group's float32 maximum (four v_max3)
-                *sure_max = fmaxf(fmaxf(fmaxf(ol[0], ol[1]), fmaxf(ol[2], ol[3])), fmaxf(fmaxf(od[0], od[1]), fmaxf(od[2], od[3])));
-            } else {                                             // max over the cells whose float32 value is certain
-                float m = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) m = fmaxf(m, (EXACT && tie_lane(tie[i])) ? 0.f : fmaxf(ol[i], od[i]));
-                *sure_max = m;
-            }
-        }
-        nl = make_float4(ol[0], ol[1], ol[2], ol[3]);
-        nd = make_float4(od[0], od[1], od[2], od[3]);
-        if (EXACT && tie_mask(TieT(tie[0] | tie[1] | tie[2] | tie[3])) != 0ull) {
-            queue_tie<0>(tie[0], nq, q, (unsigned)G.qcap, kind, lrow, 4 * lane, upL, miL, dnL, upD, miD, dnD, ol, od);
-            queue_tie<1>(tie[1], nq, q, (unsigned)G.qcap, kind, lrow, 4 * lane, upL, miL, dnL, upD, miD, dnD, ol, od);
-            queue_tie<2>(tie[2], nq, q, (unsigned)G.qcap, kind, lrow, 4 * lane, upL, miL, dnL, upD, miD, dnD, ol, od);
-            queue_tie<3>(tie[3], nq, q, (unsigned)G.qcap, kind, lrow, 4 * lane, upL, miL, dnL, upD, miD, dnD, ol, od);
-        }
-    };
-    // the same in two halves (LAG: the cells of both steps first, then their queue pushes)
+    // one row of the map with coefficient set P, in two halves (an iteration runs the cells of both steps first, then
+    // their queue pushes).  row_cells: (up, mid, down) -> new values and, in exact mode, the near-tie flags of the
+    // cells that matter (`use`); row_queue: queues those cells (kind 1 = step 1, 2 = step 2; lrow = row index
+    // relative to grid row r0-2)
     auto row_cells = [&](const PhysF32& P, const Row4& upL, const Row4& miL, const Row4& dnL, const Row4& upD,
                          const Row4& miD, const Row4& dnD, float* ol, float* od, TieT* tie,
                          const TieT* use, float* sure_max = nullptr) {
@@ -387,7 +351,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
             queue_tie<3>(tie[3], nq, q, (unsigned)G.qcap, kind, lrow, 4 * lane, upL, miL, dnL, upD, miD, dnD, ol, od);
         }
     };
-    // STATS bookkeeping of one step-2 / step-1 row map (sm = what row_cells / row_map returned through sure_max)
+    // STATS bookkeeping of one step-2 / step-1 row map (sm = what row_cells returned through sure_max)
     auto stats_step2 = [&](float sm) {
         if (CHEAP) st_c2w += (unsigned int)__popcll(__builtin_amdgcn_fcmpf(sm, thr_c2, 2 /* OGT */) & writes_mask);
         else if (writes && sm > thr_hi) st_c2 += 1u;
@@ -535,133 +499,96 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     using U0 = std::integral_constant<int, 0>;
     using U1 = std::integral_constant<int, 1>;
     using U2 = std::integral_constant<int, 2>;
-    if constexpr (LAG) {
-        // Software-pipelined by one row: iteration j = 1 .. nr+3 computes
-        //   (D1: j <= nr+2)  step-1 row j (grid row r0-2+j) from input rows j-1, j, j+1, and
-        //   (D2: j >= 4)     the output row with local index j-2 (grid row r0+j-4) from step-1 rows j-3, j-2, j-1,
-        // which are all results of EARLIER iterations: the two row maps of an iteration are independent, so
-        // their transcendental chains overlap instead of waiting for each other.  Step-1 row j then replaces
-        // step-1 row j-3 in the window.
-        auto iter = [&](auto U, auto D1, auto D2, int j, auto ST, auto MINE) {   // MINE: step-1 row j is known to be an output row
-            constexpr int u = decltype(U)::value;                  // u == j % 3
-            constexpr bool do1 = decltype(D1)::value, do2 = decltype(D2)::value;
-            constexpr bool st_on = STATS && decltype(ST)::value;   // (the quiet copy of the loop: statistics off)
-            RawIn nx;
-            if (do1) nx = load_raw(r0 + j);                        // input row j+2, needed by the NEXT iteration
-            __builtin_amdgcn_sched_barrier(0);
-            float l1[4], d1[4], l2[4], d2[4];
-            TieT tie1[4], tie2[4];
-            float sm1 = 0.f, sm2 = 0.f;
-            if (do2)
-                row_cells(P2, SL[u], SL[(u + 1) % 3], SL[(u + 2) % 3], SD[u], SD[(u + 1) % 3], SD[(u + 2) % 3], l2, d2, tie2,
-                          use2, st_on ? &sm2 : nullptr);
-            if (do1)
-                row_cells(P1, IL[(u + 2) % 3], IL[u], IL[(u + 1) % 3], ID[(u + 2) % 3], ID[u], ID[(u + 1) % 3], l1, d1, tie1,
-                          need1m, st_on ? &sm1 : nullptr);
-            if (do2) {
-                row_queue(SL[u], SL[(u + 1) % 3], SL[(u + 2) % 3], SD[u], SD[(u + 1) % 3], SD[(u + 2) % 3], l2, d2, tie2, 2,
-                          j - 2);
-                if (st_on) stats_step2(sm2);
-                if constexpr (TRACE) trace_step2(l2, d2);
-                if (writes) {
-                    const size_t off = woff + (size_t)(r0 + j - 4) * G.W + col;
-                    stream_store4(outL + off, make_float4(l2[0], l2[1], l2[2], l2[3]));
-                    stream_store4(outD + off, make_float4(d2[0], d2[1], d2[2], d2[3]));
-                }
-            }
-            if (do1) {
-                row_queue(IL[(u + 2) % 3], IL[u], IL[(u + 1) % 3], ID[(u + 2) % 3], ID[u], ID[(u + 1) % 3], l1, d1, tie1, 1, j);
-                if (st_on) stats_step1(sm1, l1, d1, tie1, j >= 2 && j <= nr + 1);
-                if constexpr (TRACE) {                              // step-1 rows of MY output cells only (wave-uniform)
-                    if (decltype(MINE)::value || (j >= 2 && j <= nr + 1)) trace_step1(l1, d1, tie1);
-                }
-                if constexpr (RING) {                               // both new rows in ONE exchange (one barrier per iteration)
-                    const float4 v[4] = {make_float4(l1[0], l1[1], l1[2], l1[3]), make_float4(d1[0], d1[1], d1[2], d1[3]),
-                                         widen4(nx.l), widen4(nx.d)};
-                    Row4* const o[4] = {&SL[u], &SD[u], &IL[(u + 2) % 3], &ID[(u + 2) % 3]};
-                    rows_ring(v, o, std::integral_constant<int, 4>{});
-                } else {
-                    to_rows4(make_float4(l1[0], l1[1], l1[2], l1[3]), make_float4(d1[0], d1[1], d1[2], d1[3]), SL[u], SD[u]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    to_rows4(widen4(nx.l), widen4(nx.d), IL[(u + 2) % 3], ID[(u + 2) % 3]);   // input row j+2 replaces input row j-1
-                    if (!PACK) pin_edge_sums(IL[(u + 2) % 3], ID[(u + 2) % 3]);
-                }
-            }
-        };
-        using Yes = std::true_type;
-        using No = std::false_type;
-        iter(U1{}, Yes{}, No{}, 1, Yes{}, No{});                    // nr >= 1: rows 1..3 always exist
-        iter(U2{}, Yes{}, No{}, 2, Yes{}, No{});
-        iter(U0{}, Yes{}, No{}, 3, Yes{}, No{});
-        const int jend = nr + 2;
-        // TRACE: the loop stops one row earlier, so that every step-1 row it computes (j + 2 <= nr + 1) is an output row
-        // and the ownership test stays out of it; the tail then has up to three rows
-        const int jloop = TRACE ? jend - 1 : jend;
-        int j = 4;
-        for (; j + 2 <= jloop; j += 3) {                            // j % 3 == 1 at the top
-            iter(U1{}, Yes{}, Yes{}, j, Yes{}, Yes{});
-            iter(U2{}, Yes{}, Yes{}, j + 1, Yes{}, Yes{});
-            iter(U0{}, Yes{}, Yes{}, j + 2, Yes{}, Yes{});
-            // wave-uniform and rare (see sweep_queue); not in the STATS variants, which are at their register budget: their
-            // live values would spill on the main path (they keep one sweep at the end of the strip)
-            if (EXACT && !STATS && __builtin_expect(nq >= (unsigned)flush_at, 0)) sweep_queue();
-            if (CHEAP && st_sure1 && st_c2w >= (unsigned int)G.sure_need) { j += 3; break; }   // both predicates are decided: see st_sure1
-        }
-        if constexpr (CHEAP) {
-            // the rest of the strip with the statistics switched off: a second copy of the row loop rather than a
-            // branch around the statistics in the first (that one costs the exact kernels registers they do not have)
-            for (; j + 2 <= jend; j += 3) {
-                iter(U1{}, Yes{}, Yes{}, j, No{}, No{});
-                iter(U2{}, Yes{}, Yes{}, j + 1, No{}, No{});
-                iter(U0{}, Yes{}, Yes{}, j + 2, No{}, No{});
+    // Software-pipelined by one row: iteration j = 1 .. nr+3 computes
+    //   (D1: j <= nr+2)  step-1 row j (grid row r0-2+j) from input rows j-1, j, j+1, and
+    //   (D2: j >= 4)     the output row with local index j-2 (grid row r0+j-4) from step-1 rows j-3, j-2, j-1,
+    // which are all results of EARLIER iterations: the two row maps of an iteration are independent, so
+    // their transcendental chains overlap instead of waiting for each other (against step 2 right behind step 1,
+    // exact kernels -5...-11 %, packed float32 -6 %, W = 256 float32 -4 %, overlapped strips
+    // -1.5 %).  Step-1 row j then replaces step-1 row j-3 in the window.
+    auto iter = [&](auto U, auto D1, auto D2, int j, auto ST, auto MINE) {   // MINE: step-1 row j is known to be an output row
+        constexpr int u = decltype(U)::value;                  // u == j % 3
+        constexpr bool do1 = decltype(D1)::value, do2 = decltype(D2)::value;
+        constexpr bool st_on = STATS && decltype(ST)::value;   // (the quiet copy of the loop: statistics off)
+        RawIn nx;
+        if (do1) nx = load_raw(r0 + j);                        // input row j+2, needed by the NEXT iteration
+        __builtin_amdgcn_sched_barrier(0);
+        float l1[4], d1[4], l2[4], d2[4];
+        TieT tie1[4], tie2[4];
+        float sm1 = 0.f, sm2 = 0.f;
+        if (do2)
+            row_cells(P2, SL[u], SL[(u + 1) % 3], SL[(u + 2) % 3], SD[u], SD[(u + 1) % 3], SD[(u + 2) % 3], l2, d2, tie2,
+                      use2, st_on ? &sm2 : nullptr);
+        if (do1)
+            row_cells(P1, IL[(u + 2) % 3], IL[u], IL[(u + 1) % 3], ID[(u + 2) % 3], ID[u], ID[(u + 1) % 3], l1, d1, tie1,
+                      need1m, st_on ? &sm1 : nullptr);
+        if (do2) {
+            row_queue(SL[u], SL[(u + 1) % 3], SL[(u + 2) % 3], SD[u], SD[(u + 1) % 3], SD[(u + 2) % 3], l2, d2, tie2, 2,
+                      j - 2);
+            if (st_on) stats_step2(sm2);
+            if constexpr (TRACE) trace_step2(l2, d2);
+            if (writes) {
+                const size_t off = woff + (size_t)(r0 + j - 4) * G.W + col;
+                stream_store4(outL + off, make_float4(l2[0], l2[1], l2[2], l2[3]));
+                stream_store4(outD + off, make_float4(d2[0], d2[1], d2[2], d2[3]));
             }
         }
-        if (j <= jend) { iter(U1{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }   // (the last rows: statistics on again - they only grow)
-        if (j <= jend) { iter(U2{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }
-        if constexpr (TRACE) {
-            if (j <= jend) { iter(U0{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }
-        }
-        // j == nr + 3: the last output row
-        if (j % 3 == 1) iter(U1{}, No{}, Yes{}, j, Yes{}, No{});
-        else if (j % 3 == 2) iter(U2{}, No{}, Yes{}, j, Yes{}, No{});
-        else iter(U0{}, No{}, Yes{}, j, Yes{}, No{});
-    } else {
-        // iteration j = 1 .. nr+2: step-1 row j (grid row r0-2+j) from input rows j-1, j, j+1; then, from j = 3
-        // on, output row k = j-3 (local row j-1) from step-1 rows j-2, j-1, j
-        auto iter = [&](auto U, int j) {
-            constexpr int u = decltype(U)::value;                  // u == j % 3
-            const RawIn nx = load_raw(r0 + j);                       // input row j+2, needed by the NEXT iteration
-            __builtin_amdgcn_sched_barrier(0);
-            float4 l1, d1;
-            float sm = 0.f;
-            row_map(P1, IL[(u + 2) % 3], IL[u], IL[(u + 1) % 3], ID[(u + 2) % 3], ID[u], ID[(u + 1) % 3], l1, d1, 1, j, need1m,
-                    STATS ? &sm : nullptr);
-            if (STATS && writes && j >= 2 && j <= nr + 1) st_m1 = fmaxf(st_m1, sm);   // step-1 rows of MY output cells
-            to_rows4(l1, d1, SL[u], SD[u]);                        // step-1 row j replaces step-1 row j-3
-            if (j >= 3) {
-                float4 l2, d2;
-                row_map(P2, SL[(u + 1) % 3], SL[(u + 2) % 3], SL[u], SD[(u + 1) % 3], SD[(u + 2) % 3], SD[u], l2, d2, 2, j - 1,
-                        use2, STATS ? &sm : nullptr);
-                if (STATS && writes && sm > thr_hi) st_c2 += 1u;
-                if (writes) {
-                    const size_t off = woff + (size_t)(r0 + j - 3) * G.W + col;
-                    stream_store4(outL + off, l2);
-                    stream_store4(outD + off, d2);
-                }
+        if (do1) {
+            row_queue(IL[(u + 2) % 3], IL[u], IL[(u + 1) % 3], ID[(u + 2) % 3], ID[u], ID[(u + 1) % 3], l1, d1, tie1, 1, j);
+            if (st_on) stats_step1(sm1, l1, d1, tie1, j >= 2 && j <= nr + 1);
+            if constexpr (TRACE) {                              // step-1 rows of MY output cells only (wave-uniform)
+                if (decltype(MINE)::value || (j >= 2 && j <= nr + 1)) trace_step1(l1, d1, tie1);
             }
-            __builtin_amdgcn_sched_barrier(0);
-            to_rows4(widen4(nx.l), widen4(nx.d), IL[(u + 2) % 3], ID[(u + 2) % 3]);   // input row j+2 replaces input row j-1
-        };
-        const int jend = nr + 2;
-        int j = 1;
-        for (; j + 2 <= jend; j += 3) {                             // j % 3 == 1 at the top
-            iter(U1{}, j);
-            iter(U2{}, j + 1);
-            iter(U0{}, j + 2);
+            if constexpr (RING) {                               // both new rows in ONE exchange (one barrier per iteration)
+                const float4 v[4] = {make_float4(l1[0], l1[1], l1[2], l1[3]), make_float4(d1[0], d1[1], d1[2], d1[3]),
+                                     widen4(nx.l), widen4(nx.d)};
+                Row4* const o[4] = {&SL[u], &SD[u], &IL[(u + 2) % 3], &ID[(u + 2) % 3]};
+                rows_ring(v, o, std::integral_constant<int, 4>{});
+            } else {
+                to_rows4(make_float4(l1[0], l1[1], l1[2], l1[3]), make_float4(d1[0], d1[1], d1[2], d1[3]), SL[u], SD[u]);
+                __builtin_amdgcn_sched_barrier(0);
+                to_rows4(widen4(nx.l), widen4(nx.d), IL[(u + 2) % 3], ID[(u + 2) % 3]);   // input row j+2 replaces input row j-1
+                if (!PACK) pin_edge_sums(IL[(u + 2) % 3], ID[(u + 2) % 3]);
+            }
         }
-        if (j <= jend) iter(U1{}, j);
-        if (j + 1 <= jend) iter(U2{}, j + 1);
+    };
+    using Yes = std::true_type;
+    using No = std::false_type;
+    iter(U1{}, Yes{}, No{}, 1, Yes{}, No{});                    // nr >= 1: rows 1..3 always exist
+    iter(U2{}, Yes{}, No{}, 2, Yes{}, No{});
+    iter(U0{}, Yes{}, No{}, 3, Yes{}, No{});
+    const int jend = nr + 2;
+    // TRACE: the loop stops one row earlier, so that every step-1 row it computes (j + 2 <= nr + 1) is an output row
+    // and the ownership test stays out of it; the tail then has up to three rows
+    const int jloop = TRACE ? jend - 1 : jend;
+    int j = 4;
+    for (; j + 2 <= jloop; j += 3) {                            // j % 3 == 1 at the top
+        iter(U1{}, Yes{}, Yes{}, j, Yes{}, Yes{});
+        iter(U2{}, Yes{}, Yes{}, j + 1, Yes{}, Yes{});
+        iter(U0{}, Yes{}, Yes{}, j + 2, Yes{}, Yes{});
+        // wave-uniform and rare (see sweep_queue); not in the STATS variants, which are at their register budget: their
+        // live values would spill on the main path (they keep one sweep at the end of the strip)
+        if (EXACT && !STATS && __builtin_expect(nq >= (unsigned)flush_at, 0)) sweep_queue();
+        if (CHEAP && st_sure1 && st_c2w >= (unsigned int)G.sure_need) { j += 3; break; }   // both predicates are decided: see st_sure1
     }
+    if constexpr (CHEAP) {
+        // the rest of the strip with the statistics switched off: a second copy of the row loop rather than a
+        // branch around the statistics in the first (that one costs the exact kernels registers they do not have)
+        for (; j + 2 <= jend; j += 3) {
+            iter(U1{}, Yes{}, Yes{}, j, No{}, No{});
+            iter(U2{}, Yes{}, Yes{}, j + 1, No{}, No{});
+            iter(U0{}, Yes{}, Yes{}, j + 2, No{}, No{});
+        }
+    }
+    if (j <= jend) { iter(U1{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }   // (the last rows: statistics on again - they only grow)
+    if (j <= jend) { iter(U2{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }
+    if constexpr (TRACE) {
+        if (j <= jend) { iter(U0{}, Yes{}, Yes{}, j, Yes{}, No{}); ++j; }
+    }
+    // j == nr + 3: the last output row
+    if (j % 3 == 1) iter(U1{}, No{}, Yes{}, j, Yes{}, No{});
+    else if (j % 3 == 2) iter(U2{}, No{}, Yes{}, j, Yes{}, No{});
+    else iter(U0{}, No{}, Yes{}, j, Yes{}, No{});
 
     if (EXACT) {
         PhysF64 Pa = P64, Pb = P64;

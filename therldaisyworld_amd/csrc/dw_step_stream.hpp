@@ -65,26 +65,14 @@ constexpr int kDppWaveShl1 = 0x130, kDppWaveRol1 = 0x134, kDppWaveShr1 = 0x138, 
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float old, float src) {
-#ifdef DW_NO_DPP   // tuning experiment: same data movement through ds_bpermute
-    const int lane = threadIdx.x & 63;
-    if (CTRL == kDppWaveShr1) { const float v = __shfl(src, (lane + 63) & 63, 64); return lane == 0 ? old : v; }
-    if (CTRL == kDppWaveShl1) { const float v = __shfl(src, (lane + 1) & 63, 64); return lane == 63 ? old : v; }
-    if (CTRL == kDppWaveRor1) return __shfl(src, (lane + 63) & 63, 64);
-    return __shfl(src, (lane + 1) & 63, 64);
-#else
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, 0xf, 0xf, false));
-#endif
 }
 
 // the same move when no lane needs an `old` value (rotations; shifts whose edge lane is unused): bound_ctrl
 // lets the hardware supply 0 there, so no register has to be zeroed for the tied destination
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov_nb(float src) {
-#ifdef DW_NO_DPP
-    return dpp_mov<CTRL>(0.f, src);
-#else
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(src), CTRL, 0xf, 0xf, true));
-#endif
 }
 
 // left / right neighbour values of the lane's 4-column group for one plane
@@ -200,17 +188,7 @@ __device__ __forceinline__ void stream_body(const plane_t* __restrict__ inL, con
                                             unsigned long long* __restrict__ fixups,
                                             unsigned long long* __restrict__ zero_me, int zero_n) {
     __shared__ uint4 s_queue[EXACT ? 4 * kWaveQueueCap * 3 : 1];
-    // exact kernels: the addend constants of fmas whose multiplier is a scalar pair too, held in VGPRs for the whole
-    // strip (see the fused kernels' PIN; bit mask: 2 pck, 4 eKb, 8 gt)
-#ifndef DW_STREAM_PIN
-#define DW_STREAM_PIN 0
-#endif
-    PhysF32 P = P_;
-    if constexpr (EXACT && DW_STREAM_PIN != 0) {
-        if constexpr ((DW_STREAM_PIN & 2) != 0) asm volatile("" : "+v"(P.pck));
-        if constexpr ((DW_STREAM_PIN & 4) != 0) asm volatile("" : "+v"(P.eKb));
-        if constexpr ((DW_STREAM_PIN & 8) != 0) asm volatile("" : "+v"(P.gt));
-    }
+    const PhysF32 P = P_;                                       // the wave's own copy: no store can alias the constants
     const int bid = blockIdx.x;
     const int wg = (bid & 7) * G.chunk + (bid >> 3);            // XCD-aware: contiguous run per XCD
     if (wg >= G.nwg) return;

@@ -2,6 +2,7 @@
 """isa_report.py — per-kernel resource table and hot-loop instruction histogram from the gfx950 assembly.
 
     python tools/isa_report.py [--build] [--asm PATH] [--kernel SUBSTR] [--loop]
+    python tools/isa_report.py --compare OLD.s NEW.s
 
 --build compiles therldaisyworld_amd/csrc/dw_api.hip with --save-temps into /tmp/dw_isa (the flags of
 therldaisyworld_amd/build.py) and reads the resulting .s; otherwise --asm names an existing one.
@@ -72,8 +73,34 @@ def classify(op):
     return "other"
 
 
+KERNEL_RE = re.compile(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", re.S)   # name, descriptor block
+
+
+def body_of(text, name):
+    """the lines between a kernel's label and its .Lfunc_end"""
+    m = re.search(r"\n" + re.escape(name) + r":[^\n]*\n(.*?)\n\.Lfunc_end", text, re.S)
+    return m.group(1).split("\n") if m else []
+
+
+def compare(old, new):
+    """--compare: kernels whose instructions or descriptor differ between two assembly files; exit status 1 if any"""
+    def kernels(path):
+        text = "\n".join(ln for ln in open(path).read().split("\n") if "__hip_cuid_" not in ln)
+        text = re.sub(r"\.LBB\d+_", ".LBB_", text)              # block labels carry the function's place in the file
+        strip = lambda lines: [s for s in (ln.split(";")[0].rstrip() for ln in lines) if s]   # comments, blank lines
+        return {name: (strip(body_of(text, name)), strip(meta.split("\n"))) for name, meta in KERNEL_RE.findall(text)}
+    a, b = kernels(old), kernels(new)
+    names = [n for n in sorted(set(a) | set(b)) if a.get(n) != b.get(n)]
+    for n, d in zip(names, demangle(names)):
+        what = "removed" if n not in b else ("added" if n not in a else f"differs ({len(a[n][0])} -> {len(b[n][0])} lines)")
+        print(f"{what}: {d}")
+    print(f"{len(a)} -> {len(b)} kernels, {len(names)} differ")
+    return 1 if names else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--compare", nargs=2, metavar=("OLD.s", "NEW.s"), help="report the kernels that differ; no other output")
     ap.add_argument("--build", action="store_true")
     ap.add_argument("--asm", default=os.path.join(OUT, "dw_api-hip-amdgcn-amd-amdhsa-gfx950.s"))
     ap.add_argument("--kernel", default="")
@@ -81,10 +108,12 @@ def main():
     ap.add_argument("--dump", default="", help="write the hot loop of the (single) selected kernel to this file")
     ap.add_argument("--flag", action="append", default=[], help="extra compiler flag for --build (repeatable)")
     a = ap.parse_args()
+    if a.compare:
+        sys.exit(compare(*a.compare))
     path = build(a.flag) if a.build else a.asm
     text = open(path).read()
     # split into functions: "name:" ... ".end_amdhsa_kernel" blocks carry the metadata
-    kern = re.findall(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", text, re.S)
+    kern = KERNEL_RE.findall(text)
     names = [k for k, _ in kern]
     dem = dict(zip(names, demangle(names)))
     rows = []
@@ -109,10 +138,9 @@ def main():
         short = re.sub(r"\(.*", "", d)
         print(f"{v:5d} {ag:5d} {s:5d} {sc:6d} {oc:4d} {lds:7d} {code:7d}  {short}")
         if a.loop:
-            m = re.search(r"\n" + re.escape(name) + r":[^\n]*\n(.*?)\n\.Lfunc_end", text, re.S)
-            if not m:
+            lines = body_of(text, name)
+            if not lines:
                 continue
-            lines = m.group(1).split("\n")
             labels = {}
             for i, ln in enumerate(lines):
                 mm = re.match(r"(\.LBB\S+):", ln)
