@@ -198,7 +198,8 @@ int dw_download_grid(dw_handle* h, double L_init, double* grid7);
 /* Side-effect caches of the last physics pass, each optional (NULL to skip):
  * temps [B][3][H][W] = temp, temp_light, temp_dark (un-rounded; ref :415-419),
  * betas [B][3][H][W] = beta, beta_l, beta_d (ref :345-347), growth [B][2][H][W] (ref :373),
- * temp_effective [B][H][W] (ref :404).  L is the luminosity of that pass. */
+ * temp_effective [B][H][W] (ref :404).  L is the luminosity of that pass: ONE value for all worlds (after
+ * dw_step_n_trace_per_world the caller's L is used as it stands, for every world). */
 int dw_download_caches(dw_handle* h, double L, double* temps, double* betas, double* growth,
                        double* temp_effective);
 
@@ -242,6 +243,26 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
  * kernels themselves, see dw_kernel_info: "trace: step pairs" / "trace: single steps") and downloaded once per 32 MiB of
  * records.  nsteps == 0 is a no-op.  Synchronises (it fills a host buffer). */
 int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace /* [nsteps][B] */);
+
+/* The same run with a luminosity per WORLD: world b takes step t at L_schedule[t*B + b] (the luminosity enters the map
+ * through the local temperature, ref daisy_world_rl.py:405,408) - an ensemble that scans the forcing in one call:
+ * equilibrium cover against luminosity, collapse points, the hysteresis between a rising and a falling branch.  nsteps
+ * single steps with no agent update; `trace` may be NULL, otherwise it is filled exactly as dw_step_n_trace fills it.
+ * Afterwards the planes of world b, the retained previous state, dw_reduce and dw_last_fixup_count (summed over the
+ * worlds) are what nsteps calls dw_step(h1, NULL, 0, 0, L_schedule[t*B + b]) leave on a ONE-world handle that holds
+ * world b - bit for bit, in all three precisions, from a quantised or an un-quantised state.  W >= 256 (a multiple of
+ * 4) steps by wave-strip kernels that read each world's constants from a device table by scalar loads, every other
+ * shape and the first step from an un-quantised state by the one-thread-per-cell kernel (dw_kernel_info says which).
+ * DW_EINVAL: null handle or schedule, or a luminosity that is not finite or is negative (checked before anything is
+ * launched: the state is untouched); DW_ESTATE: no state; DW_ENOMEM: the table of constants could not be allocated
+ * (nothing is kept: a later call allocates again).
+ * The handle has no single luminosity of the last step afterwards, so whatever derives temperature channels from it -
+ * dw_download_grid, dw_get_obs, the observations of dw_run_episode* - returns DW_ESTATE ("per-world") until a
+ * shared-L step (dw_step, dw_step_n, dw_env_step, ...) or an upload / dw_init_random has been made.  dw_download_planes,
+ * dw_reduce, dw_device_planes and the snapshots work as ever; dw_download_caches takes its L argument, ONE luminosity
+ * for all worlds. */
+int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule /* [nsteps][B] */,
+                              dw_world_stats* trace /* [nsteps][B], may be NULL */);
 
 /* Measurement aid (bench.py): duration of the run of fused step-pair launches issued by the LAST
  * dw_step_n call, from HIP events recorded on the handle's stream immediately before the first and after the

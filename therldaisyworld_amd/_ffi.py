@@ -78,6 +78,7 @@ SIGNATURES = {
     "dw_download_actions": (C.c_int, [_vp, _pi]),
     "dw_step_n": (C.c_int, [_vp, _i32, _pd, _dbl, _dbl, _dbl, C.c_int]),
     "dw_step_n_trace": (C.c_int, [_vp, _i32, _pd, C.POINTER(DwWorldStats)]),
+    "dw_step_n_trace_per_world": (C.c_int, [_vp, _i32, _pd, C.POINTER(DwWorldStats)]),
     "dw_last_step_n_timing": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(_i32), C.POINTER(_i32)]),
     "dw_update_agents": (C.c_int, [_vp, _pi, _i32, _i32]),
     "dw_forward_f64": (C.c_int, [_vp, _pd, _pd, _dbl, _pd, _pd, _pd, _pd, _pd]),

@@ -129,6 +129,8 @@ struct StepPlan {
     bool first_stream = false;        // ... in the wave-strip form (step_first_stream)
     FirstGeom first_geom{};
     bool need_fixq = false;           // exact tiled steps: the global near-tie queues
+    bool pw_stream = false;           // dw_step_n_trace_per_world: the wave-strip kernels with per-world constants
+                                      // (un-packed strips: a wave works on one world); otherwise step_generic_pw
 };
 
 // The handle owns its buffers (dw_host_util.hpp): device memory, and page-locked host memory for the staging images.
@@ -167,6 +169,7 @@ struct dw_handle {
     bool have_state = false;
     bool stepped = false;             // prev/cur form a forward() pair
     double L_last = 0.0;              // luminosity of the last forward()
+    bool L_per_world = false;         // ... which took one per world (dw_step_n_trace_per_world): L_last means nothing
     DevBuf<int> idx;                  // [B][N][2]
     DevBuf<double> st;                // [B][N]
     DevBuf<int> action;               // [B][N]
@@ -201,6 +204,10 @@ struct dw_handle {
                                       // of that call were recorded (an error return in between leaves 0)
     DevBuf<StatsDev> side_stats;      // reductions of dw_forward_f64's side computation (not the handle's)
     DevBuf<StatsDev> trace_d;         // dw_step_n_trace: [rows][B] records of the chunk of steps in flight (grown on demand)
+    // dw_step_n_trace_per_world: the constants of a chunk of steps, one entry per step and world (PwLayout), and their
+    // page-locked host image
+    DevBuf<unsigned char> pw_tab;
+    PinnedBuf<unsigned char> pw_pinned;
     PinnedBuf<unsigned char> pinned;  // page-locked host staging of dw_env_step (actions in, obs/reward/done out)
     // dw_snapshot_save[_slot] / dw_snapshot_restore[_slot]: device copies of the current state (two slots: a harness
     // that runs chunk c + 1 while it still accounts for chunk c keeps the starts of both)
@@ -209,6 +216,7 @@ struct dw_handle {
         DevBuf<plane_t> PL, PD;       // the retained previous state (observations, caches) when there is one
         bool stepped = false;
         double L_last = 0.0;
+        bool L_per_world = false;
         UnqOwner unq = OWN_NONE;
         DevBuf<int> idx;
         DevBuf<double> st;
@@ -220,6 +228,14 @@ struct dw_handle {
 };
 
 static inline bool cur_quantised(const dw_handle* h) { return h->unq != OWN_CUR; }
+
+// After a step the temperature channels of observations and of the materialised grid derive from the pre-step state and
+// the luminosity of that step (L_last).  A per-world step has no such number.
+static inline bool lacks_shared_L(const dw_handle* h) { return h->stepped && h->L_per_world; }
+#define NEED_SHARED_L(h, what)                                                                                          \
+    NEED(!lacks_shared_L(h), DW_ESTATE,                                                                                 \
+         "%s derives its temperature channels from the last step's luminosity, and the last step "                      \
+         "(dw_step_n_trace_per_world) took a per-world luminosity: take a shared-L step or upload a state first", what)
 
 // ------------------------------------------------------------------------------------------------
 // runtime values -> template arguments.  Each helper instantiates `f` for every value it lists, so it is used only
@@ -663,6 +679,7 @@ static StepPlan plan_steps(const dw_params& p, const Switches& sw) {
         s.tile_lds = (size_t)2 * (TR + 2) * (s.tcq + 2) * 4 * sizeof(float);
     }                                                           // narrow grids and DW_PRECISION_F64: generic kernel
     s.need_fixq = p.precision == DW_PRECISION_EXACT && s.kind == STEP_TILED;
+    s.pw_stream = s.kind == STEP_STREAM && !s.packed;
     // The first step from an un-quantised state reads it in its upload format: float32 (fast mode); exact mode: float32
     // with the tie bound for non-integer inputs, float64 only for the flagged cells (DW_FIRST_STEP_F64=1: every cell in
     // float64, as in round 2 - experiments); f64 mode: float64 (bit-identical to the reference's first step).
@@ -812,12 +829,13 @@ static int launch_step(dw_handle* h, const StepOut& o) {
 }
 
 // A step wrote the other buffer: it holds the current state now, and the reductions swap with it.
-static void step_done(dw_handle* h, double L, bool stepped) {
+static void step_done(dw_handle* h, double L, bool stepped, bool per_world = false) {
     h->cur = 1 - h->cur;
     h->sp = 1 - h->sp;
     h->unq = h->unq == OWN_CUR ? OWN_PREV : OWN_NONE;
     h->stepped = stepped;
     h->L_last = L;
+    h->L_per_world = per_world;
     release_unquantised(h);
 }
 
@@ -839,7 +857,7 @@ static int launch_forward(dw_handle* h, double L) {
                                reinterpret_cast<const float4*>(h->L16[in].get()), reinterpret_cast<const float4*>(h->D16[in].get()),
                                reinterpret_cast<float4*>(h->L16[out].get()), reinterpret_cast<float4*>(h->D16[out].get()), n4);
             HIPCHK(hipGetLastError());
-            h->cur = out; h->sp = 1 - h->sp; h->stepped = true; h->L_last = L;
+            h->cur = out; h->sp = 1 - h->sp; h->stepped = true; h->L_last = L; h->L_per_world = false;
             return DW_OK;
         }
         const int v = std::strcmp(e, "nomath") == 0 ? 1 : 0;
@@ -848,6 +866,68 @@ static int launch_forward(dw_handle* h, double L) {
 #endif
     if (int rc = h->unq == OWN_CUR ? launch_first_step(h, L, o) : launch_step(h, o)) return rc;
     step_done(h, L, true);
+    return DW_OK;
+}
+
+// ---- per-world luminosities (dw_step_n_trace_per_world) --------------------------------------------------------------
+// The constants of a chunk of steps: [rows][B] PhysF32 | [rows][B] PhysF64 | [B] FirstStepBound (the first step of a
+// call from an un-quantised state in the exact mode; otherwise unused).  One device buffer, one page-locked image, one
+// upload per chunk; a launch gets the addresses of its row.
+struct PwLayout {
+    size_t B, rows, o64, ofb, bytes;
+    PwLayout(size_t B_, size_t rows_) : B(B_), rows(rows_) {
+        o64 = sizeof(PhysF32) * rows * B;
+        ofb = o64 + sizeof(PhysF64) * rows * B;
+        bytes = ofb + sizeof(FirstStepBound) * B;
+    }
+    // row `row` of each part of the table that starts at `base` (the device buffer or its host image)
+    PhysF32* p32(unsigned char* base, size_t row) const { return reinterpret_cast<PhysF32*>(base) + row * B; }
+    PhysF64* p64(unsigned char* base, size_t row) const { return reinterpret_cast<PhysF64*>(base + o64) + row * B; }
+    FirstStepBound* fb(unsigned char* base) const { return reinterpret_cast<FirstStepBound*>(base + ofb); }
+};
+
+// One step, world b with the constants row32[b] / row64[b] (device addresses): the first step from an un-quantised state
+// and every shape the per-world wave-strip kernels do not take by step_generic_pw.
+static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* row64, const FirstStepBound* rowfb) {
+    const dw_params& p = h->prm;
+    const StepPlan& pl = h->plan;
+    const int out = 1 - h->cur;
+    plane_t *oL = h->L16[out].get(), *oD = h->D16[out].get();
+    StatsDev* stats = h->stats2[1 - h->sp].get();                       // invariant: all zero
+    unsigned long long* fixups = &stats[p.batch].sum_l;
+    unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get());
+    const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
+    const bool ex = p.precision == DW_PRECISION_EXACT;
+    auto generic = [&](auto* iL, auto* iD, auto PR) {
+        const int cpt = generic_cells_per_thread(p.batch, (long long)p.height * p.width);
+        const dim3 grid((unsigned)(((long long)p.height * p.width + 256LL * cpt - 1) / (256LL * cpt)), (unsigned)p.batch);
+        hipLaunchKernelGGL((step_generic_pw<elem_t<decltype(iL)>, PR>), grid, dim3(256), 0, h->stream, iL, iD, oL, oD, p.height,
+                           p.width, row32, row64, rowfb, stats, fixups, zero_me, zero_n, cpt);
+    };
+    const plane_t* iL = h->L16[h->cur].get();
+    const plane_t* iD = h->D16[h->cur].get();
+    if (h->unq == OWN_CUR) {                                    // PREC as launch_first_step: 1 float32, 3 bounded, 2 float64
+        with_unq_planes(h, [&](auto* uL, auto* uD) {
+            with_int<1, 3, 2>(pl.first_prec, [&](auto PR) { generic(uL, uD, PR); });
+        });
+    } else if (pl.pw_stream && ex) {
+        const StreamExactPwArgs A{iL, iD, oL, oD, pl.sgeom, row32, row64, stats, fixups, zero_me, zero_n};
+        with_int<0, 1, 2>(pl.halo, [&](auto HL) {
+            with_bool(pl.sym_albedo, [&](auto SYM) {
+                hipLaunchKernelGGL((step_stream_exact_pw<HL, SYM>), dim3((unsigned)pl.sgeom.chunk * 8u), dim3(256), 0, h->stream, A);
+            });
+        });
+    } else if (pl.pw_stream) {
+        with_int<0, 1, 2>(pl.halo, [&](auto HL) {
+            hipLaunchKernelGGL((step_stream_fast_pw<HL>), dim3((unsigned)pl.sgeom.chunk * 8u), dim3(256), 0, h->stream, iL, iD, oL,
+                               oD, pl.sgeom, row32, row64, stats, fixups, zero_me, zero_n);
+        });
+    } else {                                                    // PREC 0 exact, 1 fast, 2 f64
+        const int prec = p.precision == DW_PRECISION_F64 ? 2 : (ex ? 0 : 1);
+        with_int<2, 0, 1>(prec, [&](auto PR) { generic(iL, iD, PR); });
+    }
+    HIPCHK(hipGetLastError());
+    step_done(h, 0.0, true, true);
     return DW_OK;
 }
 
@@ -1296,7 +1376,7 @@ static int run_materialise(dw_handle* h, double L, double* d_grid7, double* d_te
                            double* d_growth, double* d_teff) {
     const dw_params& p = h->prm;
     const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
-    const PhysF64 P = make_f64(p, h->stepped ? h->L_last : L);
+    const PhysF64 P = make_f64(p, h->stepped && !h->L_per_world ? h->L_last : L);   // (per-world: dw_download_caches' own L)
     const plane_t* cL = h->L16[h->cur].get();            // read by the POST variants only
     const plane_t* cD = h->D16[h->cur].get();
     with_derived_from(h, [&](auto* pL, auto* pD, auto POST) {
@@ -1315,6 +1395,7 @@ static int run_materialise(dw_handle* h, double L, double* d_grid7, double* d_te
 int dw_download_grid(dw_handle* h, double L_init, double* grid7) {
     NEED(h && grid7, DW_EINVAL, "null argument");
     NEED(h->have_state, DW_ESTATE, "no state");
+    NEED_SHARED_L(h, "dw_download_grid");
     HIPCHK(hipSetDevice(h->prm.device));
     const size_t bytes = sizeof(double) * 7 * h->cells;
     int rc = ensure_scratch(h, bytes);
@@ -1506,6 +1587,103 @@ int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_w
         }
         HIPCHK(hipMemcpyAsync(trace + (size_t)c0 * B, h->trace_d.get(), (size_t)cn * row_bytes, hipMemcpyDeviceToHost,
                               h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    sync.disarm();
+    return DW_OK;
+}
+
+int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace) {
+    NEED(h && L_schedule, DW_EINVAL, "null argument");
+    NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
+    if (nsteps == 0) return DW_OK;
+    NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
+    static_assert(sizeof(dw_world_stats) == sizeof(StatsDev), "stats layout");
+    const dw_params& p = h->prm;
+    const size_t B = (size_t)p.batch, row_bytes = sizeof(StatsDev) * B;
+    for (size_t i = 0; i < (size_t)nsteps * B; ++i)
+        NEED(std::isfinite(L_schedule[i]) && L_schedule[i] >= 0.0, DW_EINVAL,
+             "L_schedule[step %zu][world %zu] = %g: a luminosity is finite and not negative", i / B, i % B, L_schedule[i]);
+    HIPCHK(hipSetDevice(p.device));
+    // rows of the series on the device at a time: as dw_step_n_trace (no pairs here: any number of rows will do)
+    size_t rows = h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / row_bytes;
+    rows = rows < 1 ? 1 : (rows > (size_t)nsteps ? (size_t)nsteps : rows);
+    // rows of the table: 8 MiB of constants (256 B per step and world), under the test hook as many as trace rows
+    size_t trows = ((size_t)8 << 20) / ((sizeof(PhysF32) + sizeof(PhysF64)) * B);
+    if (h->sw.trace_rows >= 1 && trows > (size_t)h->sw.trace_rows) trows = (size_t)h->sw.trace_rows;
+    trows = trows < 1 ? 1 : (trows > (size_t)nsteps ? (size_t)nsteps : trows);
+    const PwLayout lay(B, trows);
+    // the table and (when a series is wanted) the trace buffer: all or nothing; then the table's page-locked image
+    if (trace) {
+        if (int rc = alloc_group(h, "the per-world constants and the trace buffer",
+                                 {{h->pw_tab, lay.bytes}, {h->trace_d, rows * row_bytes}})) return rc;
+    } else if (int rc = alloc_group(h, "the per-world constants", {{h->pw_tab, lay.bytes}})) {
+        return rc;
+    }
+    if (int rc = reserve(h->pw_pinned, "the page-locked image of the per-world constants", lay.bytes)) {
+        h->pw_tab.reset();
+        return rc;
+    }
+    hipEvent_t uploaded = nullptr;                              // the image may be written again once its upload has run
+    HIPCHK(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+    struct EventGuard { hipEvent_t e; ~EventGuard() { (void)hipEventDestroy(e); } } event_guard{uploaded};
+    SyncOnExit sync(h->stream);                                 // the downloads below fill the caller's array
+    h->fused_launches = 0;
+    unsigned char* img = h->pw_pinned.get();
+    unsigned char* tab = h->pw_tab.get();
+    // a world whose luminosity did not change since its last step keeps its constants (a sweep at fixed L derives B sets,
+    // not nsteps * B)
+    std::vector<double> lastL(B, -1.0);
+    std::vector<PhysF32> last32(B);
+    std::vector<PhysF64> last64(B);
+    const bool first_bound = h->unq == OWN_CUR && h->plan.first_prec == 3;
+    bool image_in_flight = false;
+    // A step whose luminosities all equal the previous step's shares its row (a sweep at fixed luminosities: ONE row, one
+    // upload of B entries for the whole run); a chunk is the steps that `trows` distinct rows serve.
+    std::vector<size_t> row_of(trows ? (size_t)nsteps : 0);
+    int chunk_end = 0;                                          // the steps before it have their rows on the device
+    for (int t = 0; t < nsteps; ++t) {
+        const size_t sr = (size_t)t % rows;
+        if (t == chunk_end) {                                   // this chunk's constants: derived in float64, one upload
+            if (image_in_flight) HIPCHK(hipEventSynchronize(uploaded));
+            size_t tn = 0;
+            for (; chunk_end < nsteps; ++chunk_end) {
+                const double* Ls = L_schedule + (size_t)chunk_end * B;
+                if (tn && std::memcmp(Ls, Ls - B, sizeof(double) * B) == 0) { row_of[chunk_end] = tn - 1; continue; }
+                if (tn == trows) break;
+                PhysF32* r32 = lay.p32(img, tn);
+                PhysF64* r64 = lay.p64(img, tn);
+                for (size_t b = 0; b < B; ++b) {
+                    if (Ls[b] != lastL[b]) {
+                        lastL[b] = Ls[b];
+                        last32[b] = derive_f32(p, Ls[b]);
+                        last64[b] = make_f64(p, Ls[b]);
+                    }
+                    r32[b] = last32[b];
+                    r64[b] = last64[b];
+                }
+                row_of[chunk_end] = tn++;
+            }
+            if (t == 0 && first_bound)
+                for (size_t b = 0; b < B; ++b)
+                    lay.fb(img)[b] = derive_first_bound(p, L_schedule[b], lay.p32(img, 0)[b], h->unq_kind == UNQ_F64,
+                                                        h->sw.first_slack);     // (row 0 of the first chunk is step 0)
+            // (the rows in use of both parts)
+            HIPCHK(hipMemcpyAsync(h->pw_tab.get(), img, sizeof(PhysF32) * tn * B, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->pw_tab.get() + lay.o64, img + lay.o64, sizeof(PhysF64) * tn * B, hipMemcpyHostToDevice, h->stream));
+            if (t == 0 && first_bound)
+                HIPCHK(hipMemcpyAsync(h->pw_tab.get() + lay.ofb, img + lay.ofb, sizeof(FirstStepBound) * B, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipEventRecord(uploaded, h->stream));
+            image_in_flight = true;
+        }
+        const size_t tr = row_of[t];
+        if (int rc = launch_forward_pw(h, lay.p32(tab, tr), lay.p64(tab, tr), lay.fb(tab))) return rc;
+        if (trace) {
+            HIPCHK(hipMemcpyAsync(h->trace_d.get() + sr * B, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
+            if (sr + 1 == rows || t + 1 == nsteps)
+                HIPCHK(hipMemcpyAsync(trace + ((size_t)t - sr) * B, h->trace_d.get(), (sr + 1) * row_bytes, hipMemcpyDeviceToHost,
+                                      h->stream));
+        }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     sync.disarm();
@@ -1779,6 +1957,7 @@ int dw_policy_per_agent(dw_handle* h, const int32_t* agent_mode) {
 static int observe_into_scratch(dw_handle* h, double L_init, size_t extra_bytes, bool reward_tail) {
     const dw_params& p = h->prm;
     const size_t bn = (size_t)p.batch * p.n_agents;
+    NEED_SHARED_L(h, "an observation");
     int rc = ensure_scratch(h, sizeof(double) * bn * 63 + extra_bytes);
     if (rc) return rc;
     double* d_rew = reward_tail ? h->scratch.get() + bn * 63 : nullptr;
@@ -1904,6 +2083,7 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     size_t t = 0;
     while (t < K) {
         if (small && cur_quantised(h) && h->stepped && h->unq == OWN_NONE) {
+            NEED_SHARED_L(h, "the episode's first observation");
             const size_t Kr = K - t;
             p32.resize(Kr);
             for (size_t i = 0; i < Kr; ++i) p32[i] = derive_f32(p, L_schedule[t + i]);
@@ -1938,6 +2118,7 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
             HIPCHK(hipGetLastError());
             h->stepped = true;
             h->L_last = L_schedule[K - 1];
+            h->L_per_world = false;
             t = K;
             break;
         }
@@ -2225,6 +2406,7 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     h->unq = OWN_NONE;
     h->stepped = true;
     h->L_last = L_schedule[K - 1];
+    h->L_per_world = false;
     release_unquantised(h);
     HIPCHK(hipStreamSynchronize(h->stream));      // flags are returned
     guard.disarm();
@@ -2307,6 +2489,7 @@ int dw_snapshot_save_slot(dw_handle* h, int32_t slot) {
     }
     sn.stepped = h->stepped;
     sn.L_last = h->L_last;
+    sn.L_per_world = h->L_per_world;
     sn.unq = h->unq;
     sn.agents = bn && h->have_agents;
     if (sn.agents) {
@@ -2346,6 +2529,7 @@ int dw_snapshot_restore_slot(dw_handle* h, int32_t slot) {
     h->unq = sn.unq;                            // OWN_PREV: the un-quantised initial state is still in its buffers
     h->stepped = sn.stepped;
     h->L_last = sn.L_last;
+    h->L_per_world = sn.L_per_world;
     return DW_OK;
 }
 
@@ -2431,6 +2615,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_step_n_trace takes (StepPlan::trace_pairs)
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, pl.trace_pairs ? "; trace: step pairs" : "; trace: single steps");
+    }
+    {                                                           // the form dw_step_n_trace_per_world takes (StepPlan::pw_stream)
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, pl.pw_stream ? "; per-world L: wave strips" : "; per-world L: generic");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

@@ -217,6 +217,7 @@ class RLDaisyWorld:
     @property
     def grid(self):
         if self._grid_m is None:
+            self._need_shared_L("env.grid")
             self._sync_to_device()
             self._grid_m = _Mirror(self._engine.download_grid(self._L_pass))
         return self._grid_m.array
@@ -342,7 +343,13 @@ class RLDaisyWorld:
         self._caches = {}
         self._cache_src = None
 
+    def _need_shared_L(self, what):
+        if getattr(self, "_per_world_L", False):
+            raise RuntimeError(f"{what}: the last run (simulate_luminosity_sweep) stepped every world at a luminosity of its "
+                               "own, so the environment has no L to continue from - call reset() first")
+
     def reset(self):
+        self._per_world_L = False
         self.L = self.min_L
         self.dL = (self.max_L - self.min_L) / self.ramp_period
         self.step_count = 0
@@ -354,6 +361,7 @@ class RLDaisyWorld:
         """Extension: device-side initial state (Philox keyed by seed / global world id / cell) with
         the distribution of initialize_grid / initialize_agents — for grids too large to draw and
         upload from the host.  Not stream-compatible with np.random."""
+        self._per_world_L = False
         self.L = self.min_L
         self.dL = (self.max_L - self.min_L) / self.ramp_period
         self.step_count = 0
@@ -518,6 +526,7 @@ class RLDaisyWorld:
 
     def step(self, action=None):
         """ref :475-497."""
+        self._need_shared_L("env.step()")
         eng = self._ensure_engine()
         self._sync_to_device()
         if action is None and self.n_agents:

@@ -178,6 +178,19 @@ class Engine:
                                         out.ctypes.data_as(C.POINTER(DwWorldStats))))
         return out
 
+    def step_n_trace_per_world(self, L, trace=True):
+        """`len(L)` agent-free steps with a luminosity per WORLD: `L` is (n, B), world b takes step t at `L[t, b]`
+        (`dw_step_n_trace_per_world`) - each world ends exactly where a one-world engine stepped with its column would.
+        Returns the (n, B) records of `step_n_trace`, or None with `trace=False`.  Afterwards the engine has no single
+        luminosity of the last step: `download_grid` / `get_obs` raise until a shared-L step or an upload."""
+        Ls = np.ascontiguousarray(L, dtype=np.float64)
+        if Ls.ndim != 2 or Ls.shape[1] != self.B:
+            raise ValueError(f"per-world luminosities need shape (n, {self.B}), got {Ls.shape}")
+        out = np.zeros(Ls.shape, dtype=_ffi.STATS_DTYPE) if trace else None
+        self._check(self._lib.dw_step_n_trace_per_world(
+            self._h, int(Ls.shape[0]), _ffi.ptr_d(Ls), out.ctypes.data_as(C.POINTER(DwWorldStats)) if trace else None))
+        return out
+
     def last_step_n_timing(self):
         """(ms spent in the fused step-pair launches of the last step_n call, their number, plane element bytes)."""
         ms, n, eb = C.c_float(0), C.c_int32(0), C.c_int32(0)
@@ -409,8 +422,8 @@ class Engine:
         return lp.value, dp.value
 
     def kernel_info(self) -> str:
-        buf = C.create_string_buffer(512)
-        self._check(self._lib.dw_kernel_info(self._h, buf, 512))
+        buf = C.create_string_buffer(1024)
+        self._check(self._lib.dw_kernel_info(self._h, buf, 1024))
         return buf.value.decode()
 
     def audit_tie_bound(self, L):

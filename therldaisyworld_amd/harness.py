@@ -237,6 +237,11 @@ def _ramp_series(env, nsteps, run_trace):
     L = np.asarray(_luminosity_schedule(env, n), dtype=np.float64)
     stats = run_trace(L)
     _advance_host_scalars(env, n)
+    return _series_dict(env, L, stats)
+
+
+def _series_dict(env, L, stats):
+    """What `simulate_ramp` and `simulate_luminosity_sweep` return, from the (n, B) records of a run."""
     cells = float(env.dim) * float(env.dim)
     max_cover = stats["max_k"] / 1000.0
     return {"L": L,
@@ -265,6 +270,35 @@ def simulate_ramp(env, nsteps, obs=None):
     eng = env._ensure_engine()
     env._sync_to_device()
     return _ramp_series(env, nsteps, eng.step_n_trace)
+
+
+def simulate_luminosity_sweep(env, L_values, nsteps, obs=None):
+    """The response of an agent-free ensemble to forcing in ONE run: world b is held at luminosity `L_values[b]` for
+    `nsteps` steps (`len(L_values) == env.batch_size`) - the bifurcation diagram the reference's notebooks assemble from
+    one run per luminosity (`run_q2_sims`, the `min_L` / `max_L` edits).  `L_values` may also be (nsteps, B): a schedule
+    per world, e.g. half the worlds ramping up and half ramping down for the hysteresis loop.  The per-step, per-world
+    reductions are recorded on the device (`dw_step_n_trace_per_world`) and come down once.  `obs=None`: reset first.
+
+    Returns the dict of `simulate_ramp` with `L` of shape (n, B).  The reference's `env.L` is ONE number and has no
+    meaning after such a run: `env.step()` and `env.grid` raise until `env.reset()` (the covers are available from
+    `env._engine.download_planes()`, the last records from the returned series)."""
+    if env.n_agents:
+        raise ValueError("simulate_luminosity_sweep is for agent-free ensembles (n_agents == 0)")
+    n = int(nsteps)
+    L = np.asarray(L_values, dtype=np.float64)
+    if L.ndim == 1:
+        L = np.broadcast_to(L, (n, L.shape[0]))
+    if L.ndim != 2 or L.shape != (n, int(env.batch_size)):
+        raise ValueError(f"L_values needs shape ({int(env.batch_size)},) or ({n}, {int(env.batch_size)}), got {np.shape(L_values)}")
+    L = np.ascontiguousarray(L)
+    if obs is None:
+        env.reset()
+    eng = env._ensure_engine()
+    env._sync_to_device()
+    stats = eng.step_n_trace_per_world(L)
+    env._invalidate()
+    env._per_world_L = True
+    return _series_dict(env, L, stats)
 
 
 def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_chunk):

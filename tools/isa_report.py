@@ -3,6 +3,7 @@
 
     python tools/isa_report.py [--build] [--asm PATH] [--kernel SUBSTR] [--loop]
     python tools/isa_report.py --compare OLD.s NEW.s
+    python tools/isa_report.py [--build] [--asm PATH] --fingerprint OUT.json
 
 --build compiles therldaisyworld_amd/csrc/dw_api.hip with --save-temps into /tmp/dw_isa (the flags of
 therldaisyworld_amd/build.py) and reads the resulting .s; otherwise --asm names an existing one.
@@ -10,6 +11,9 @@ For every kernel whose (demangled) name contains SUBSTR: VGPRs, AGPRs, SGPRs, sp
 LDS bytes, occupancy, code length; with --loop also the instruction-class histogram of the largest
 loop body (the block between the last backward branch target and its branch) and the lines that touch
 scratch memory.  Runs in the build container (no GPU).
+--fingerprint keeps what --compare needs of an assembly file - a hash per kernel of its instructions and descriptor, and
+the compiler's version - so that a later build can be held against this one without it (tests/golden/kernel_fingerprint.json:
+the kernels as they were before the per-world variants were added; tests/test_per_world_cpu.py).
 The step-pair kernels and their TRACE forms side by side:  --build --loop --kernel fused2 ;  --loop --kernel trace_pair
 """
 from __future__ import annotations
@@ -82,14 +86,30 @@ def body_of(text, name):
     return m.group(1).split("\n") if m else []
 
 
+def normalised_kernels(path):
+    """name -> (instructions, descriptor lines) of every kernel, without what depends on its place in the file"""
+    text = "\n".join(ln for ln in open(path).read().split("\n") if "__hip_cuid_" not in ln)
+    text = re.sub(r"\.LBB\d+_", ".LBB_", text)              # block labels carry the function's place in the file
+    strip = lambda lines: [s for s in (ln.split(";")[0].rstrip() for ln in lines) if s]   # comments, blank lines
+    return {name: (strip(body_of(text, name)), strip(meta.split("\n"))) for name, meta in KERNEL_RE.findall(text)}
+
+
+def compiler_version():
+    p = subprocess.run(["/opt/rocm/bin/hipcc", "--version"], text=True, capture_output=True)
+    return " | ".join(ln.strip() for ln in p.stdout.split("\n") if "version" in ln)
+
+
+def fingerprint(path):
+    """--fingerprint: {"compiler": ..., "kernels": {name: sha256 of the normalised instructions and descriptor}}"""
+    import hashlib
+    ks = normalised_kernels(path)
+    return {"compiler": compiler_version(),
+            "kernels": {n: hashlib.sha256("\n".join(body + ["--"] + meta).encode()).hexdigest()[:20] for n, (body, meta) in sorted(ks.items())}}
+
+
 def compare(old, new):
     """--compare: kernels whose instructions or descriptor differ between two assembly files; exit status 1 if any"""
-    def kernels(path):
-        text = "\n".join(ln for ln in open(path).read().split("\n") if "__hip_cuid_" not in ln)
-        text = re.sub(r"\.LBB\d+_", ".LBB_", text)              # block labels carry the function's place in the file
-        strip = lambda lines: [s for s in (ln.split(";")[0].rstrip() for ln in lines) if s]   # comments, blank lines
-        return {name: (strip(body_of(text, name)), strip(meta.split("\n"))) for name, meta in KERNEL_RE.findall(text)}
-    a, b = kernels(old), kernels(new)
+    a, b = normalised_kernels(old), normalised_kernels(new)
     names = [n for n in sorted(set(a) | set(b)) if a.get(n) != b.get(n)]
     for n, d in zip(names, demangle(names)):
         what = "removed" if n not in b else ("added" if n not in a else f"differs ({len(a[n][0])} -> {len(b[n][0])} lines)")
@@ -101,6 +121,7 @@ def compare(old, new):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--compare", nargs=2, metavar=("OLD.s", "NEW.s"), help="report the kernels that differ; no other output")
+    ap.add_argument("--fingerprint", metavar="OUT.json", help="write the per-kernel hashes of the assembly; no other output")
     ap.add_argument("--build", action="store_true")
     ap.add_argument("--asm", default=os.path.join(OUT, "dw_api-hip-amdgcn-amd-amdhsa-gfx950.s"))
     ap.add_argument("--kernel", default="")
@@ -111,6 +132,12 @@ def main():
     if a.compare:
         sys.exit(compare(*a.compare))
     path = build(a.flag) if a.build else a.asm
+    if a.fingerprint:
+        import json
+        with open(a.fingerprint, "w") as f:
+            json.dump(fingerprint(path), f, indent=0, sort_keys=True)
+            f.write("\n")
+        return
     text = open(path).read()
     # split into functions: "name:" ... ".end_amdhsa_kernel" blocks carry the metadata
     kern = KERNEL_RE.findall(text)
