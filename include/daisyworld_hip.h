@@ -431,7 +431,12 @@ int dw_timer_stop(dw_handle* h, float* elapsed_ms);
 int dw_device_planes(dw_handle* h, int which, void** light, void** dark);
 
 /* Name and geometry of the step kernel the handle dispatches for its shape, for bench/profiles:
- * writes a NUL-terminated description into buf. */
+ * writes a NUL-terminated description into buf.  Appended fragments name the forms of the other entry points:
+ * "; trace: ...", "; per-world L: ...", and "; episode: F; mlp episode: F" - the form dw_run_episode and
+ * dw_run_episode_mlp take for the handle's shape, agent count, precision, collision mode and switches, F one of
+ * "one wave per world" (H*W <= 256 and at most 64 agents, MLP: at most 4), "workgroup (LDS)" (H*W <= 4096) and
+ * "launches per step" (dw_run_episode_mlp takes its first steps that way until the current and the previous state are
+ * quantised, whatever the form). */
 int dw_kernel_info(dw_handle* h, char* buf, size_t buflen);
 
 /* Diagnostics for the exact-mode error bound: number of cells re-evaluated in float64 by the last

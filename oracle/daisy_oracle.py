@@ -211,6 +211,11 @@ class OracleDaisyWorld:
         self.beta = self.beta_l = self.beta_d = None
         self.growth = None
 
+    @property
+    def shape(self):
+        """(H, W) of the grid held: square (dim, dim) unless set_initial_cover was given rectangular covers."""
+        return (self.P.dim, self.P.dim) if self.grid is None else tuple(self.grid.shape[-2:])
+
     @classmethod
     def like_reference_ctor(cls, **kw):
         """Consume the legacy global RNG exactly as ``RLDaisyWorld.__init__`` does
@@ -240,9 +245,13 @@ class OracleDaisyWorld:
 
     def set_initial_cover(self, light, dark):
         """Second half of ref :304-324: assemble the 7-channel grid from given covers and fill the
-        three temperature channels with one physics pass at the current L (un-rounded)."""
+        three temperature channels with one physics pass at the current L (un-rounded).
+
+        The grid takes its shape from ``light.shape[-2:]``: the reference is square (``% self.dim``, ref :208,259-260),
+        and so are :meth:`reset`, :meth:`initialize_grid` and :meth:`initialize_agents`; an H x W world set here is
+        the same algorithm with rows wrapped by H and columns by W (update_agents, get_obs, _collisions)."""
         P = self.P
-        grid = np.zeros((P.batch_size, P.ch, P.dim, P.dim))
+        grid = np.zeros((P.batch_size, P.ch) + tuple(np.shape(light)[-2:]))
         grid[:, CH_BARE] = P.p - light - dark
         grid[:, CH_LIGHT] = light
         grid[:, CH_DARK] = dark
@@ -315,7 +324,7 @@ class OracleDaisyWorld:
                         self.agent_indices[bb, nn, 0] += 1
                     elif a % 4 == 3:
                         self.agent_indices[bb, nn, 1] += 1
-                    self.agent_indices[bb, nn] %= P.dim   # ref :208 wraps everything; same effect
+                    self.agent_indices[bb, nn] %= self.shape   # ref :208 wraps everything (by dim); same effect
                     if a > 4:
                         r, c = self.agent_indices[bb, nn, 0], self.agent_indices[bb, nn, 1]
                         self.agent_states[bb, nn, 0] += self.grid[bb, 1:3, r, c].sum()
@@ -331,9 +340,10 @@ class OracleDaisyWorld:
         (the reference's ``*= 0.0`` acts on a fancy-indexed copy, :242).  One ``rand`` draw of the
         whole (1,N,1) block per multiply-occupied cell (:233)."""
         P = self.P
+        H, W = self.shape
         for bb in range(self.agent_indices.shape[0]):
-            for r in range(P.dim):
-                for c in range(P.dim):
+            for r in range(H):
+                for c in range(W):
                     residents = (self.agent_indices[bb] == np.array([r, c])).all(-1)
                     if residents.sum() > 1:
                         jitter = np.random.rand(1, *self.agent_states[bb].shape)[0]
@@ -346,13 +356,14 @@ class OracleDaisyWorld:
     def get_obs(self, agent_indices):
         """ref: daisy_world_rl.py:246-263 — 3x3 wrap-around patch of all 7 channels, times mask."""
         P = self.P
+        H, W = self.shape
         B, N = agent_indices.shape[:2]
         obs = np.zeros((B, N, P.ch, 3, 3))
         off = np.arange(-1, 2)
         for bb in range(B):
             for nn in range(N):
-                rows = (agent_indices[bb, nn, 0] + off) % P.dim
-                cols = (agent_indices[bb, nn, 1] + off) % P.dim
+                rows = (agent_indices[bb, nn, 0] + off) % H
+                cols = (agent_indices[bb, nn, 1] + off) % W
                 obs[bb, nn] = self.grid[bb][:, rows][:, :, cols]
         return obs * self.neighborhood
 

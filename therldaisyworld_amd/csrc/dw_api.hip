@@ -356,6 +356,11 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
                             const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
                             uint8_t* world_alive, uint8_t* agent_ok);
 static bool episode_kernel_applies(const dw_handle* h);
+// The form a handle's episode calls take: a pure function of its parameters and switches.  The dispatch of
+// run_episode_impl / dw_run_episode_mlp and the text of dw_kernel_info both read these two predicates.
+enum EpisodeForm { EPISODE_STEPWISE, EPISODE_WORKGROUP, EPISODE_WAVE };   // launches per step | episode_small / episode_mlp | one wave per world
+static EpisodeForm episode_form(const dw_handle* h);
+static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes = nullptr);
 static int observe_into_scratch(dw_handle* h, double L_init, size_t extra_bytes, bool reward_tail = false);
 
 static int ensure_scratch(dw_handle* h, size_t bytes) { return reserve(h->scratch, "scratch", bytes); }
@@ -2072,12 +2077,9 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     // previous state is the un-quantised upload - and for large worlds: one launch sequence per step.
     const int Cc = p.height * p.width;
     const int wpb = Cc <= 256 ? 4 : (Cc <= 1024 ? 2 : 1);
-    // H*W <= 256 with at most four agents (the ES trainers' own 16x16 x 4): one wave per world (dw_episode_wave.hpp)
-    const bool wave_kernel = Cc <= kEwMaxCells && 16 * N <= 64 && !h->sw.no_episode_wave;
-    const size_t lds = wave_kernel ? episode_wave_shared_bytes() + episode_mlp_wave_world_bytes(Cc, N) * 4
-                                   : episode_mlp_world_bytes(Cc, N) * wpb;
-    const bool small = Cc <= 4096 && lds <= 160 * 1024 && p.precision != DW_PRECISION_F64 &&
-                       !h->sw.no_episode_kernel;
+    size_t lds = 0;
+    const EpisodeForm form = episode_mlp_form(h, &lds);
+    const bool wave_kernel = form == EPISODE_WAVE, small = form != EPISODE_STEPWISE;
     std::vector<PhysF32> p32;
     SyncOnExit guard2(h->stream);                             // p32 (filled below) must outlive its upload
     size_t t = 0;
@@ -2187,11 +2189,34 @@ int dw_run_episode(dw_handle* h, int32_t nsteps, const double* L_schedule, int p
     return run_episode_impl(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok);
 }
 
-static bool episode_kernel_applies(const dw_handle* h) {
+// dw_run_episode (and the agent-free runs dw_step_n hands to it).  DW_PRECISION_F64 and collision_mode 1 have no
+// LDS-resident kernel: dw_step_n launches per step, dw_run_episode itself rejects them.
+static EpisodeForm episode_form(const dw_handle* h) {
     const dw_params& p = h->prm;
-    return p.height * p.width <= 4096 && p.precision != DW_PRECISION_F64 && p.collision_mode == 0 &&
-           cur_quantised(h) && !h->sw.no_episode_kernel;
+    const int C = p.height * p.width, N = p.n_agents;
+    if (C > 4096 || p.precision == DW_PRECISION_F64 || p.collision_mode != 0 || h->sw.no_episode_kernel)
+        return EPISODE_STEPWISE;
+    // H*W <= 256 (the README sweep's 8x8, the ES trainers' 16x16): one wave per world (dw_episode_wave.hpp)
+    return C <= kEwMaxCells && N <= 64 && !h->sw.no_episode_wave ? EPISODE_WAVE : EPISODE_WORKGROUP;
 }
+
+// dw_run_episode_mlp, once current and previous state are quantised (until then: launches per step whatever the form);
+// *lds_bytes: the dynamic LDS of the launch
+static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes) {
+    const dw_params& p = h->prm;
+    const int Cc = p.height * p.width, N = p.n_agents;
+    const int wpb = Cc <= 256 ? 4 : (Cc <= 1024 ? 2 : 1);
+    // H*W <= 256 with at most four agents (the ES trainers' own 16x16 x 4): one wave per world (dw_episode_wave.hpp)
+    const bool wave_kernel = Cc <= kEwMaxCells && 16 * N <= 64 && !h->sw.no_episode_wave;
+    const size_t lds = wave_kernel ? episode_wave_shared_bytes() + episode_mlp_wave_world_bytes(Cc, N) * 4
+                                   : episode_mlp_world_bytes(Cc, N) * wpb;
+    if (lds_bytes) *lds_bytes = lds;
+    const bool small = Cc <= 4096 && lds <= 160 * 1024 && p.precision != DW_PRECISION_F64 && p.collision_mode == 0 &&
+                       !h->sw.no_episode_kernel;
+    return !small ? EPISODE_STEPWISE : (wave_kernel ? EPISODE_WAVE : EPISODE_WORKGROUP);
+}
+
+static bool episode_kernel_applies(const dw_handle* h) { return episode_form(h) != EPISODE_STEPWISE && cur_quantised(h); }
 
 // dw_run_episode for worlds that do not fit LDS: the same K steps as K x (policy, dw_step) issued
 // back-to-back on the handle's stream - policy kernel or table slice -> update_agents -> step kernel ->
@@ -2314,11 +2339,11 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     NEED(policy_mode != DW_POLICY_TABLE || table, DW_EINVAL, "DW_POLICY_TABLE needs a table");
     if (use_table && !table)
         for (int t = 0; t < nsteps; ++t) NEED(!use_table[t], DW_EINVAL, "use_table set but no table given");
-    if (C > 4096 || h->sw.no_episode_kernel)
+    const EpisodeForm form = episode_form(h);                  // (F64 / collision_mode 1 were rejected above)
+    if (form == EPISODE_STEPWISE)
         return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
                                     agent_ok);
-    // H*W <= 256 (the README sweep's 8x8, the ES trainers' 16x16): one wave per world (dw_episode_wave.hpp)
-    const bool wave_kernel = C <= kEwMaxCells && N <= 64 && !h->sw.no_episode_wave;
+    const bool wave_kernel = form == EPISODE_WAVE;
     const int wpb = C <= 256 ? 4 : (C <= 1024 ? 2 : 1);
     const size_t world_bytes = wave_kernel ? episode_wave_world_bytes(C, N) : episode_world_bytes(C, N);
     const size_t lds = world_bytes * wpb + (wave_kernel ? episode_wave_shared_bytes() : 0);
@@ -2619,6 +2644,11 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_step_n_trace_per_world takes (StepPlan::pw_stream)
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, pl.pw_stream ? "; per-world L: wave strips" : "; per-world L: generic");
+    }
+    {                                                           // the forms dw_run_episode / dw_run_episode_mlp take
+        static const char* const form_name[] = {"launches per step", "workgroup (LDS)", "one wave per world"};   // by EpisodeForm
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; episode: %s; mlp episode: %s", form_name[episode_form(h)], form_name[episode_mlp_form(h)]);
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);
