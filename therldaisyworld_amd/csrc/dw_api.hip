@@ -67,10 +67,12 @@ enum UnqOwner { OWN_NONE = 0, OWN_CUR = 1, OWN_PREV = 2 };
 // DW_TEST_HOOKS is set as well: a stray variable in a user's environment cannot inject failures.
 //   DW_STRIP_ROWS=n        rows per wave-strip of the steady-state, step-pair AND first-step kernels instead of strip_rows()'s
 //                          choice (the first-step kernel: at most 64, the height its float32 partial sums stay exact at)
+//   DW_NO_FMT_PLANES=1     the plain overlapped-strip step pairs read and write their rows with ordinary global accesses
+//                          instead of format buffer accesses (StepPlan::fmt_planes): an A/B in one process
 //   DW_TEST_TRACE_ROWS=n   (test hook) dw_step_n_trace holds n rows of the series on the device at a time (rounded down to
 //                          even, at least 2) instead of 32 MiB of them: multi-chunk runs with a handful of worlds
 struct Switches {
-    bool no_sym = false, no_pack = false, no_fuse = false, no_ring = false, no_episode_kernel = false,
+    bool no_sym = false, no_pack = false, no_fuse = false, no_ring = false, no_fmt_planes = false, no_episode_kernel = false,
          no_episode_wave = false, no_agent_fuse = false, no_agent_preapply = false, first_f64 = false,
          first_generic = false, force_rescan = false, test_hooks = false;
     int pack_min_strips = -1, strip_rows = 0, tile_rpt = 0, queue_cap = -1, mismatch_cap = -1, trace_rows = 0;
@@ -93,6 +95,7 @@ static Switches read_switches() {
     };
     w.test_hooks = std::getenv("DW_TEST_HOOKS") != nullptr;
     flag("DW_NO_SYM", w.no_sym); flag("DW_NO_PACK", w.no_pack); flag("DW_NO_FUSE", w.no_fuse); flag("DW_NO_RING", w.no_ring);
+    flag("DW_NO_FMT_PLANES", w.no_fmt_planes);
     flag("DW_NO_EPISODE_KERNEL", w.no_episode_kernel); flag("DW_NO_EPISODE_WAVE", w.no_episode_wave);
     flag("DW_NO_AGENT_FUSE", w.no_agent_fuse); flag("DW_NO_AGENT_PREAPPLY", w.no_agent_preapply);
     flag("DW_FIRST_STEP_F64", w.first_f64); flag("DW_FIRST_GENERIC", w.first_generic);
@@ -115,6 +118,8 @@ struct StepPlan {
     bool packed = false;              // STEP_STREAM with W < 256: several worlds side by side in a wave row
     bool allow_fuse = false;          // STEP_STREAM only: dw_step_n / dw_run_episode fuse pairs of steps ...
     int fused_mode = kFusedOvl;       // ... with this strip layout (packed worlds: kFusedRot)
+    bool fmt_planes = false;          // ... whose plain (no STATS, no trace) float32 launches on overlapped strips take the
+                                      // format buffer access kernel (step_stream_fused2_fmt_pw)
     bool trace_pairs = false;         // dw_step_n_trace records step pairs (trace_pair_fast / trace_pair_exact: un-packed
                                       // overlapped or rotating strips); otherwise single steps, a copy of B records each
     bool sym_albedo = false;          // a_dark - a_bare == -(a_light - a_bare) exactly: the exact wave-strip kernels use
@@ -663,6 +668,9 @@ static StepPlan plan_steps(const dw_params& p, const Switches& sw) {
         f.mcap = mcap;
         f.sure_need = 9 * p.n_agents + 9 * mcap + 1;            // (dw_step_fused.hpp, STATS)
         s.trace_pairs = s.allow_fuse && !s.packed && s.fused_mode != kFusedRing;
+        // (a world's plane is addressed by 32-bit byte offsets there)
+        s.fmt_planes = p.precision == DW_PRECISION_FAST && s.allow_fuse && !s.packed && s.fused_mode == kFusedOvl && !sw.no_fmt_planes &&
+                       (size_t)p.height * p.width * sizeof(plane_t) < ((size_t)1 << 31);
     } else if (quads && p.width >= 64) {
         s.kind = STEP_TILED;
         const int Wq = p.width / 4;
@@ -979,6 +987,9 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
             hipLaunchKernelGGL((trace_pair_fast<MODE>), grid, dim3(256), 0, h->stream, inL, inD, outL, outD, g, P1, P2, zero_me,
                                zero_n, trace);
         });
+    } else if (pl.fmt_planes && !pstats && !exact) {
+        hipLaunchKernelGGL((step_stream_fused2_fmt_pw<kFusedOvl>), grid, dim3(256), 0, h->stream, inL, inD, outL, outD, g, P1, P2,
+                           zero_me, zero_n);
     } else if (exact) {
         const FusedExactArgs A = exact_args();
         with_bool(pstats != nullptr, [&](auto STATS) {
@@ -2624,8 +2635,8 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
                  g.chunk * 8);
         if (pl.allow_fuse) {
             const size_t n = std::strlen(buf);
-            snprintf(buf + n, buflen - n, "; dw_step_n fuses step pairs (step_stream_fused2%s)",
-                     p.precision == DW_PRECISION_EXACT ? "_exact" : "");
+            snprintf(buf + n, buflen - n, "; dw_step_n fuses step pairs (step_stream_fused2%s%s)",
+                     p.precision == DW_PRECISION_EXACT ? "_exact" : "", pl.fmt_planes ? "_fmt_pw, format buffer accesses" : "");
         }
     } else if (pl.kind == STEP_TILED) {
         const int TR = (256 / pl.tcq) * pl.rpt;

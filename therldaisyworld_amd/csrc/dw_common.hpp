@@ -74,6 +74,53 @@ __device__ __forceinline__ void stream_store4(plane_t* p, const float4& v) {
     __builtin_nontemporal_store(t, reinterpret_cast<dw_u32x2*>(p));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Format buffer accesses of a binary16 plane: the memory path converts binary16 <-> float32 (four cells per access, as
+// float32 in the registers) and the row's byte offset travels in a scalar register, so a row access costs the vector
+// unit no conversion and no 64-bit address arithmetic.  Exact both ways: the loads widen, and the stored values are
+// integers in [0, 1000], which binary16 holds whatever the rounding (0 is no denormal).
+// The compiler has no builtin for them; the LLVM intrinsics are declared by their names, so its own s_waitcnt
+// insertion tracks them like any other vector memory access.
+// ---------------------------------------------------------------------------------------------
+typedef float dw_fmt_f32x4 __attribute__((ext_vector_type(4)));
+typedef int dw_i32x4 __attribute__((ext_vector_type(4)));
+__device__ dw_fmt_f32x4 dw_buf_load_fmt4(dw_i32x4 rsrc, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.load.format.v4f32");
+__device__ void dw_buf_store_fmt4(dw_fmt_f32x4 v, dw_i32x4 rsrc, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.format.v4f32");
+constexpr int kBufAuxNonTemporal = 2;                           // the `nt` bit of a buffer access (as stream_store4's stores)
+// The descriptor of ONE world's plane; `world` and `world_bytes` (H * W * 2 < 2^31) must be wave-uniform.  The base is a
+// 64-bit scalar computation (a plane of the whole ensemble exceeds 4 GiB), the offsets within a world fit 32 bits.
+//   word 0  base[31:0]       word 1  base[47:32], stride 0 (a raw buffer)       word 2  num_records = world_bytes
+//   word 3  dst_sel x/y/z/w = 4/5/6/7 [11:0] | num_format FLOAT (7) [14:12] | data_format 16_16_16_16 (12) [18:15]
+// An access whose VECTOR offset leaves the world reads zero / is dropped (the scalar offset takes no part in the
+// range check: the callers' rows are wrapped onto the torus before they become one).
+__device__ __forceinline__ dw_i32x4 fmt_plane_rsrc(const plane_t* plane, int world, unsigned int world_bytes) {
+    const unsigned long long base = (unsigned long long)plane + (unsigned long long)world * world_bytes;
+    dw_i32x4 r;
+    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned int)base);
+    r.y = __builtin_amdgcn_readfirstlane((int)(unsigned int)(base >> 32)) & 0xffff;
+    r.z = __builtin_amdgcn_readfirstlane((int)world_bytes);
+    r.w = 0x00067FAC;
+    return r;
+}
+__device__ __forceinline__ float4 fmt_load4(const dw_i32x4& rsrc, int voff, int soff) {
+    const dw_fmt_f32x4 v = dw_buf_load_fmt4(rsrc, voff, soff, 0);
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void fmt_store4(const dw_i32x4& rsrc, int voff, int soff, const float4& v) {
+    dw_buf_store_fmt4(dw_fmt_f32x4{v.x, v.y, v.z, v.w}, rsrc, voff, soff, kBufAuxNonTemporal);
+}
+// A prefetched row out of the load's registers into its slot of a register window: the window's slots rotate with the
+// unrolled loop, the prefetch's registers do not, so the row has to move once - two cells per v_pk_mov_b32 (where the
+// binary16 form paid one conversion per cell, which was that move).  Left to the compiler: one v_mov_b32 per cell.
+__device__ __forceinline__ float4 widen4(const float4& v) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    unsigned long long lo, hi;                                  // (not float pairs: their sums would be formed as packed adds
+    asm("v_pk_mov_b32 %0, %1, %1 op_sel:[0,1]" : "=v"(lo) : "v"(f2{v.x, v.y}));   //  across the window's register pairs)
+    asm("v_pk_mov_b32 %0, %1, %1 op_sel:[0,1]" : "=v"(hi) : "v"(f2{v.z, v.w}));
+    return make_float4(__uint_as_float((unsigned int)lo), __uint_as_float((unsigned int)(lo >> 32)),
+                       __uint_as_float((unsigned int)hi), __uint_as_float((unsigned int)(hi >> 32)));
+}
+
 // a coordinate at most one period outside [0, n) back onto the torus (agents move by one cell, stencils reach two)
 __device__ __forceinline__ int wrap_near(int v, int n) { return v < 0 ? v + n : (v >= n ? v - n : v); }
 // ... at most TWO periods outside (a repair reaches four rows beyond a strip of a world that may be only three rows tall)

@@ -128,8 +128,11 @@ enum { kFusedOvl = 0, kFusedRot = 1, kFusedRing = 2 };
 //               running maximum A takes every float32 value; the repairs keep N = max of the values they wrote and
 //               LW = max of the values they LOWERED.  M = max(A, N) is the largest value any cell ever held, so it is
 //               a current value unless a cell that held it was lowered: only if LW >= M the finished strip is re-read.
+// FMT (step_stream_fused2_fmt_pw below: the plain float32 kernel on overlapped strips): the rows of the row
+// loop travel through format buffer accesses (dw_common.hpp) - loaded as float32, stored from float32, their row offset
+// in a scalar register.  The repairs' scattered patches and gathers stay plain global accesses (cold).
 template <int MODE, bool EXACT, bool PACK = false, bool STATS = false, bool SYM = false, typename TI = plane_t,
-          typename TO = plane_t, bool TRACE = false>
+          typename TO = plane_t, bool TRACE = false, bool FMT = false>
 __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI* __restrict__ inD,
                                             TO* __restrict__ outL, TO* __restrict__ outD, const FusedGeom& G,
                                             const PhysF32& P1_, const PhysF32& P2_, const PhysF64& P64,
@@ -140,6 +143,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     constexpr bool ROT = MODE == kFusedRot, RING = MODE == kFusedRing;
     static_assert(!RING || !PACK, "the ring exchange is written for un-packed worlds");
     static_assert(!TRACE || (!PACK && !STATS && !RING), "the trace form exists for un-packed overlapped / rotating strips");
+    static_assert(!FMT || (MODE == kFusedOvl && !EXACT && !PACK && !STATS && !TRACE), "the format-access form exists for the plain float32 kernel on overlapped strips");
     __shared__ float s_edge[RING ? 2 * 4 * 8 : 1];               // RING: [parity][wave][.w of lane 63 x4 | .x of lane 0 x4]
     __shared__ uint4 s_queue[EXACT ? 4 * kWaveQueueCap * 3 : 1];
     __shared__ unsigned int s_mm[EXACT ? 4 * kMismatchCap : 1];
@@ -200,14 +204,32 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     const TI* pL = inL + woff;
     const TI* pD = inD + woff;
 
-    struct RawIn { dw_f16x4 l, d; };                            // one row of both planes as loaded (4 x binary16 each)
+    // FMT: one descriptor per plane of this wave's world; a lane's byte offset within a row, a row's within the world
+    dw_i32x4 fmt_inL, fmt_inD, fmt_outL, fmt_outD;
+    int fmt_col = 0, fmt_row = 0;
+    if constexpr (FMT) {
+        const unsigned int world_bytes = (unsigned int)(G.H * G.W) * 2u;
+        fmt_inL = fmt_plane_rsrc(inL, b, world_bytes);
+        fmt_inD = fmt_plane_rsrc(inD, b, world_bytes);
+        fmt_outL = fmt_plane_rsrc(outL, b, world_bytes);
+        fmt_outD = fmt_plane_rsrc(outD, b, world_bytes);
+        fmt_col = col * 2;
+        fmt_row = G.W * 2;
+    }
+    // one row of both planes as loaded (4 x binary16 each; FMT: already float32)
+    struct RawIn { std::conditional_t<FMT, float4, dw_f16x4> l, d; };
     auto load_raw = [&](int rr) -> RawIn {                      // rr in [r0-2, r0+nr+1], clamped + wrapped
         rr = min(rr, r0 + nr + 1);
         rr = rr < 0 ? rr + G.H : rr;
         rr = rr >= G.H ? rr - G.H : rr;
         RawIn w;
-        w.l = stream_load4_raw(pL + (size_t)rr * G.W + col);
-        w.d = stream_load4_raw(pD + (size_t)rr * G.W + col);
+        if constexpr (FMT) {
+            w.l = fmt_load4(fmt_inL, fmt_col, rr * fmt_row);
+            w.d = fmt_load4(fmt_inD, fmt_col, rr * fmt_row);
+        } else {
+            w.l = stream_load4_raw(pL + (size_t)rr * G.W + col);
+            w.d = stream_load4_raw(pD + (size_t)rr * G.W + col);
+        }
         return w;
     };
     // The edge sums of a prefetched row are wanted HERE: left alone, the compiler sinks the adds (and half of the
@@ -527,7 +549,12 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
                       j - 2);
             if (st_on) stats_step2(sm2);
             if constexpr (TRACE) trace_step2(l2, d2);
-            if (writes) {
+            if constexpr (FMT) {
+                if (writes) {
+                    fmt_store4(fmt_outL, fmt_col, (r0 + j - 4) * fmt_row, make_float4(l2[0], l2[1], l2[2], l2[3]));
+                    fmt_store4(fmt_outD, fmt_col, (r0 + j - 4) * fmt_row, make_float4(d2[0], d2[1], d2[2], d2[3]));
+                }
+            } else if (writes) {
                 const size_t off = woff + (size_t)(r0 + j - 4) * G.W + col;
                 stream_store4(outL + off, make_float4(l2[0], l2[1], l2[2], l2[3]));
                 stream_store4(outD + off, make_float4(d2[0], d2[1], d2[2], d2[3]));
@@ -845,6 +872,21 @@ void step_stream_fused2(const plane_t* __restrict__ inL, const plane_t* __restri
     const PhysF64 dummy{};
     const double zero = 0.0;
     fused2_body<MODE, false, PACK, STATS>(inL, inD, outL, outD, G, P1, P2, dummy, zero, zero, zero_me, zero_n, pstats, thr_hi);
+}
+
+// The format-access form of the plain overlapped-strip kernel (fused2_body, FMT).  `_pw` in the name marks a kernel ADDED
+// AFTER the recorded kernel fingerprint (tests/test_per_world_cpu.py accepts additions by that mark); these are NOT
+// per-world-luminosity kernels.  There is no exact form: with four descriptors (16 SGPRs) the exact kernels spill scalar
+// registers inside the row loop.
+template <int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DW_FUSED_FAST_WAVES, DW_FUSED_FAST_WAVES)))
+void step_stream_fused2_fmt_pw(const plane_t* __restrict__ inL, const plane_t* __restrict__ inD,
+                               plane_t* __restrict__ outL, plane_t* __restrict__ outD, FusedGeom G, PhysF32 P1, PhysF32 P2,
+                               unsigned long long* __restrict__ zero_me, int zero_n) {
+    const PhysF64 dummy{};
+    const double zero = 0.0;
+    fused2_body<MODE, false, false, false, false, plane_t, plane_t, false, true>(inL, inD, outL, outD, G, P1, P2, dummy, zero,
+                                                                                  zero, zero_me, zero_n);
 }
 
 // Waves per SIMD of the exact kernels: the plain variants fit 3 waves/SIMD (151-161 VGPRs), and since the constant
