@@ -1,6 +1,6 @@
 """GPU tests (``-m gpu``) of the wave-strip kernels at the strip heights production shapes run: 16, 32 and 64 rows.
 
-The oracle-compared tests elsewhere use a handful of worlds, for which ``strip_rows`` (dw_api.hip) falls through to 8-row
+The oracle-compared tests elsewhere use a handful of worlds, for which ``strip_rows`` (dw_plan.hpp) falls through to 8-row
 strips.  Here the height is forced with ``DW_STRIP_ROWS`` on small worlds (it governs the steady-state, the step-pair and
 the first-step kernels) or chosen by the batch size alone, and every case first asserts from ``kernel_info()`` that the
 height it asked for is the one in use.  What changes with the height: the trip count of the row loop and its prologue /
@@ -272,7 +272,7 @@ NWG_TARGETS = (1, 7, 8, 9, 13)
 
 
 def _geometry(B, H, W, SR):
-    """plan_steps' strip counts for the shape at strip height SR (dw_api.hip): steady-state strips, the workgroups of the
+    """plan_steps' strip counts for the shape at strip height SR (dw_plan.hpp): steady-state strips, the workgroups of the
     single-step launch and of the step-pair launch."""
     sr = min(SR, H)
     nrs = (H + sr - 1) // sr
@@ -370,7 +370,7 @@ def test_trace_from_a_developed_state_repairs_the_same_cells(amd, monkeypatch, S
 # heights chosen by the batch size alone
 # ---------------------------------------------------------------------------------------------------------------------
 def _strip_rows(groups, H, target):
-    """strip_rows of dw_api.hip: 64 rows, halved down to 8 until the launch has at least `target` strips."""
+    """strip_rows of dw_plan.hpp: 64 rows, halved down to 8 until the launch has at least `target` strips."""
     sr = 64
     while sr > 8 and groups * ((H + sr - 1) // sr) < target:
         sr >>= 1

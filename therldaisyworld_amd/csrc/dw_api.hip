@@ -1,10 +1,9 @@
 // dw_api.hip — C ABI (include/daisyworld_hip.h) over the gfx950 kernels in dw_kernels.hpp.
 //
-// Host-side responsibilities: device state (ping-pong binary16 per-mille planes, agents, reductions),
-// per-step derivation of the float32 coefficient set from the float64 constants and the current
-// luminosity, kernel selection by grid shape, and the bookkeeping of the un-quantised initial state
-// (float64 or float32 buffers that live until the first step has consumed them).  No CPU compute path
-// exists here.
+// Host-side responsibilities: device state (ping-pong binary16 per-mille planes, agents, reductions), the
+// launches, and the bookkeeping of the un-quantised initial state (float64 or float32 buffers that live until
+// the first step has consumed them).  Which kernels take a step, and the float32 coefficient set derived for it
+// from the float64 constants and the current luminosity: dw_plan.hpp.  No CPU compute path exists here.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,6 +19,7 @@
 #include "../../include/daisyworld_hip.h"
 #include "dw_kernels.hpp"
 #include "dw_host_util.hpp"
+#include "dw_plan.hpp"
 
 using namespace dw;
 
@@ -60,83 +60,6 @@ static int fail(int code, const char* fmt, ...) {
 // binary16 planes of the `cur` buffer are undefined.
 enum UnqKind { UNQ_F64 = 1, UNQ_F32 = 2 };
 enum UnqOwner { OWN_NONE = 0, OWN_CUR = 1, OWN_PREV = 2 };
-
-// Experiment and test switches (environment variables), read ONCE per handle at dw_create - a handle behaves the same for
-// its whole life whatever the environment does afterwards - and reported by dw_kernel_info when any is set.  None changes
-// results.  The DW_TEST_* hooks (shrunk queues, injected allocation failures, forced fallbacks) are honoured only when
-// DW_TEST_HOOKS is set as well: a stray variable in a user's environment cannot inject failures.
-//   DW_STRIP_ROWS=n        rows per wave-strip of the steady-state, step-pair AND first-step kernels instead of strip_rows()'s
-//                          choice (the first-step kernel: at most 64, the height its float32 partial sums stay exact at)
-//   DW_NO_FMT_PLANES=1     the plain overlapped-strip step pairs read and write their rows with ordinary global accesses
-//                          instead of format buffer accesses (StepPlan::fmt_planes): an A/B in one process
-//   DW_TEST_TRACE_ROWS=n   (test hook) dw_step_n_trace holds n rows of the series on the device at a time (rounded down to
-//                          even, at least 2) instead of 32 MiB of them: multi-chunk runs with a handful of worlds
-struct Switches {
-    bool no_sym = false, no_pack = false, no_fuse = false, no_ring = false, no_fmt_planes = false, no_episode_kernel = false,
-         no_episode_wave = false, no_agent_fuse = false, no_agent_preapply = false, first_f64 = false,
-         first_generic = false, force_rescan = false, test_hooks = false;
-    int pack_min_strips = -1, strip_rows = 0, tile_rpt = 0, queue_cap = -1, mismatch_cap = -1, trace_rows = 0;
-    double first_slack = -1.0;
-    char kernel[16] = {0};           // DW_KERNEL: "tiled" | "stream"
-    char text[256] = {0};            // what was set, for dw_kernel_info
-};
-static const char* test_hook(const char* name) {              // a DW_TEST_* variable, only under DW_TEST_HOOKS
-    return std::getenv("DW_TEST_HOOKS") ? std::getenv(name) : nullptr;
-}
-static Switches read_switches() {
-    Switches w;
-    auto note = [&](const char* name, const char* val) {
-        const size_t n = std::strlen(w.text);
-        snprintf(w.text + n, sizeof(w.text) - n, "%s%s%s%s", n ? " " : "", name, val ? "=" : "", val ? val : "");
-    };
-    auto flag = [&](const char* name, bool& dst) { if (std::getenv(name)) { dst = true; note(name, nullptr); } };
-    auto num = [&](const char* name, int& dst, bool test) {
-        if (const char* e = test ? test_hook(name) : std::getenv(name)) { dst = std::atoi(e); note(name, e); }
-    };
-    w.test_hooks = std::getenv("DW_TEST_HOOKS") != nullptr;
-    flag("DW_NO_SYM", w.no_sym); flag("DW_NO_PACK", w.no_pack); flag("DW_NO_FUSE", w.no_fuse); flag("DW_NO_RING", w.no_ring);
-    flag("DW_NO_FMT_PLANES", w.no_fmt_planes);
-    flag("DW_NO_EPISODE_KERNEL", w.no_episode_kernel); flag("DW_NO_EPISODE_WAVE", w.no_episode_wave);
-    flag("DW_NO_AGENT_FUSE", w.no_agent_fuse); flag("DW_NO_AGENT_PREAPPLY", w.no_agent_preapply);
-    flag("DW_FIRST_STEP_F64", w.first_f64); flag("DW_FIRST_GENERIC", w.first_generic);
-    num("DW_PACK_MIN_STRIPS", w.pack_min_strips, false); num("DW_STRIP_ROWS", w.strip_rows, false);
-    num("DW_TILE_RPT", w.tile_rpt, false);
-    num("DW_TEST_QUEUE_CAP", w.queue_cap, true); num("DW_TEST_MISMATCH_CAP", w.mismatch_cap, true);
-    num("DW_TEST_TRACE_ROWS", w.trace_rows, true);
-    if (test_hook("DW_TEST_FORCE_RESCAN")) { w.force_rescan = true; note("DW_TEST_FORCE_RESCAN", nullptr); }
-    if (const char* e = test_hook("DW_TEST_FIRST_SLACK")) { w.first_slack = std::atof(e); note("DW_TEST_FIRST_SLACK", e); }
-    if (const char* e = std::getenv("DW_KERNEL")) { snprintf(w.kernel, sizeof(w.kernel), "%s", e); note("DW_KERNEL", e); }
-    return w;
-}
-
-// Which kernels take the steps, and their launch geometry: a pure function of the parameters and the switches
-// (plan_steps), computed when a handle is created or its parameters change and committed together with them.
-enum StepKind { STEP_GENERIC, STEP_TILED, STEP_STREAM };
-struct StepPlan {
-    StepKind kind = STEP_GENERIC;     // the step from a quantised state (DW_PRECISION_F64: always generic)
-    int halo = 0;                     // wave-strip halo form of the single-step kernels, first step included (halo_form)
-    bool packed = false;              // STEP_STREAM with W < 256: several worlds side by side in a wave row
-    bool allow_fuse = false;          // STEP_STREAM only: dw_step_n / dw_run_episode fuse pairs of steps ...
-    int fused_mode = kFusedOvl;       // ... with this strip layout (packed worlds: kFusedRot)
-    bool fmt_planes = false;          // ... whose plain (no STATS, no trace) float32 launches on overlapped strips take the
-                                      // format buffer access kernel (step_stream_fused2_fmt_pw)
-    bool trace_pairs = false;         // dw_step_n_trace records step pairs (trace_pair_fast / trace_pair_exact: un-packed
-                                      // overlapped or rotating strips); otherwise single steps, a copy of B records each
-    bool sym_albedo = false;          // a_dark - a_bare == -(a_light - a_bare) exactly: the exact wave-strip kernels use
-                                      // the two-term coefficient chain (growth_t<.., SYM>)
-    int tcq = 0, rpt = 0;             // STEP_TILED: tile columns (quads) and rows per thread
-    Geom geom{};
-    size_t tile_lds = 0;
-    StripGeom sgeom{};                // STEP_STREAM
-    FusedGeom fgeom{};
-    int first_prec = 2;               // the first step from an un-quantised state: PREC of step_generic /
-                                      // step_first_stream (1 float32, 2 float64, 3 float32 with the tie bound) ...
-    bool first_stream = false;        // ... in the wave-strip form (step_first_stream)
-    FirstGeom first_geom{};
-    bool need_fixq = false;           // exact tiled steps: the global near-tie queues
-    bool pw_stream = false;           // dw_step_n_trace_per_world: the wave-strip kernels with per-world constants
-                                      // (un-packed strips: a wave works on one world); otherwise step_generic_pw
-};
 
 // The handle owns its buffers (dw_host_util.hpp): device memory, and page-locked host memory for the staging images.
 // DW_TEST_FAIL_GROUP_ALLOC=<n> (tests, under DW_TEST_HOOKS; process-wide countdown, read when a group is first allocated
@@ -366,6 +289,8 @@ static bool episode_kernel_applies(const dw_handle* h);
 enum EpisodeForm { EPISODE_STEPWISE, EPISODE_WORKGROUP, EPISODE_WAVE };   // launches per step | episode_small / episode_mlp | one wave per world
 static EpisodeForm episode_form(const dw_handle* h);
 static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes = nullptr);
+// worlds a workgroup of the LDS-resident episode kernels holds (dw_episode.hpp: 256 / wpb threads per world)
+static int worlds_per_block(int cells) { return cells <= 256 ? 4 : (cells <= 1024 ? 2 : 1); }
 static int observe_into_scratch(dw_handle* h, double L_init, size_t extra_bytes, bool reward_tail = false);
 
 static int ensure_scratch(dw_handle* h, size_t bytes) { return reserve(h->scratch, "scratch", bytes); }
@@ -391,332 +316,6 @@ static int set_lds_limit(dw_handle* h, Kernel kern, size_t bytes) {
     return DW_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// constants: float64 set and the per-step float32 set
-// ------------------------------------------------------------------------------------------------
-static PhysF64 make_f64(const dw_params& p, double L) {
-    PhysF64 P;
-    P.p = p.p; P.g = p.g; P.S = p.S; P.sigma = p.sigma; P.gamma = p.gamma; P.q = p.q; P.q2 = p.q2;
-    P.dt = p.dt; P.ab = p.albedo_bare; P.al = p.albedo_light; P.ad = p.albedo_dark;
-    P.To = p.temp_optimal; P.L = L;
-    // ref daisy_world_rl.py:270-273: ones*e^-1, centre 1, corners e^-2, normalised
-    const double e1 = std::exp(-1.0), e2 = std::exp(-2.0);
-    const double s = 1.0 + 4.0 * e1 + 4.0 * e2;
-    P.w0 = 1.0 / s; P.w1 = e1 / s; P.w2 = e2 / s;
-    return P;
-}
-
-// kbeta = 1 / sqrt(g To^2) in float64 (g = 0: a denominator so large that w^2 vanishes)
-static double cbeta_host(const dw_params& p) {
-    const double cbeta = p.g * p.temp_optimal * p.temp_optimal;
-    return cbeta > 1e-30 ? 1.0 / std::sqrt(cbeta) : 0x1p60;
-}
-
-static void split_hi_lo(double v, double scale, float* hi, float* lo) {
-    const double h = std::nearbyint(v * scale) / scale;
-    *hi = (float)h;
-    *lo = (float)(v - h);
-}
-
-// Derivation of the fused float32 coefficients (see dw_physics.hpp, PhysF32) and of the exact-mode
-// tie bound (DESIGN.md §"Exact mode").  All in float64, rounded once.
-static PhysF32 derive_f32(const dw_params& p, double L, int hb_cap = 40) {
-    const double To4 = std::pow(p.temp_optimal, 4);
-    const double K = p.S * L / p.sigma;
-    const double dal = p.albedo_light - p.albedo_bare, dad = p.albedo_dark - p.albedo_bare;
-    const double a1 = (p.q - K) * dal / (8000.0 * To4);
-    const double a2 = (p.q - K) * dad / (8000.0 * To4);
-    const double a3 = (-p.q + p.q2) * dal / (1000.0 * To4);
-    const double a4 = (-p.q + p.q2) * dad / (1000.0 * To4);
-    const double e0 = K * (1.0 - p.albedo_bare * p.p) / To4 - 1.0;
-    const double c0l = e0 + p.q2 * (p.albedo_bare * p.p - p.albedo_light) / To4;
-    const double c0d = e0 + p.q2 * (p.albedo_bare * p.p - p.albedo_dark) / To4;
-    // hi parts are multiples of 2^-hb with hb chosen so that every partial sum of the hi chain
-    // (|.| <= maxsum) stays below 2^(24-hb): exactly representable in float32 for integer inputs.
-    const double kmax = 1000.0;                                  // covers are clipped to [0, 1] whatever p is (ref :449)
-    const double maxsum = std::fabs(a1) * 8 * kmax + std::fabs(a2) * 8 * kmax + std::fabs(a3) * kmax +
-                          std::fabs(a4) * kmax + std::fmax(std::fabs(c0l), std::fabs(c0d));
-    int hb = 23 - (int)std::ceil(std::log2(std::fmax(maxsum, 1e-30)));
-    if (hb > hb_cap) hb = hb_cap;                               // a coarser split is always admissible
-    if (hb < 0) hb = 0;
-    const double scale = std::ldexp(1.0, hb);
-    PhysF32 P;
-    P.hi_bits = hb;
-    split_hi_lo(a1, scale, &P.a1h, &P.a1l);
-    split_hi_lo(a2, scale, &P.a2h, &P.a2l);
-    split_hi_lo(a3, scale, &P.a3h, &P.a3l);
-    split_hi_lo(a4, scale, &P.a4h, &P.a4l);
-    split_hi_lo(c0l, scale, &P.c0lh, &P.c0ll);
-    float c0dl;
-    split_hi_lo(c0d, scale, &P.c0dh, &c0dl);
-    P.dc0l = c0dl - P.c0ll;                                      // the lo chain carries light's lo constant
-    // float32-only mode: every coefficient rounded once (= fl(hi + lo): the sum of two floats is exact in double)
-    P.a1 = (float)((double)P.a1h + P.a1l); P.a2 = (float)((double)P.a2h + P.a2l);
-    P.a3 = (float)((double)P.a3h + P.a3l); P.a4 = (float)((double)P.a4h + P.a4l);
-    P.c0ls = (float)((double)P.c0lh + P.c0ll); P.c0ds = (float)((double)P.c0dh + c0dl);
-    // kbeta = 1 / sqrt(g * To^2) (dw_physics.hpp); g = 0 (beta = 1 everywhere): a denominator so large that w^2
-    // vanishes.  g < 0 is refused for the float32 modes by check_params.
-    {
-        const double cbeta = p.g * p.temp_optimal * p.temp_optimal;
-        P.kbeta = cbeta > 1e-30 ? (float)(1.0 / std::sqrt(cbeta)) : 0x1p60f;
-    }
-    const PhysF64 P64 = make_f64(p, L);
-    // dt folded into the density weights (dK = dt * density is what the map needs); the bare fraction then is
-    // kb = p - (dKl + dKd) * 0.001 / dt  (dt = 0: no growth at all - weights 0, kb = p)
-    P.dw0 = (float)(p.dt * P64.w0); P.dw1 = (float)(p.dt * P64.w1); P.dw2 = (float)(p.dt * P64.w2);
-    P.p = (float)p.p; P.ck = p.dt != 0.0 ? (float)(0.001 / p.dt) : 0.f;
-    P.ngamma = (float)(-p.gamma);
-    // ---- tie bound (per-mille), DESIGN.md "Exact mode":
-    //   |gq32 - gq64| <= A0 + eA*|gq| + |dt*K| * (eK0 + eK1*om),   om = 1 - beta >= 0
-    const double u = std::ldexp(1.0, -24);
-    // absolute error of e: only the lo chain rounds (hi chain exact); lo coefficients <= 2^-(hb+1)
-    const double lo_mag = std::ldexp(1.0, -(hb + 1)) * 18.0 * kmax + std::ldexp(1.0, -(hb + 1));
-    const double de_abs = 6.0 * u * lo_mag + 1e-9;
-    // admissible interval of e over all states with covers in [0, kmax] (signs of the coefficients respected)
-    // (light and dark cover are clipped separately: both may be full in the same cell)
-    const double pos = (std::fmax(a1, 0.0) + std::fmax(a2, 0.0)) * 8 * kmax + (std::fmax(a3, 0.0) + std::fmax(a4, 0.0)) * kmax;
-    const double neg = (std::fmin(a1, 0.0) + std::fmin(a2, 0.0)) * 8 * kmax + (std::fmin(a3, 0.0) + std::fmin(a4, 0.0)) * kmax;
-    const double emax = std::fmax(c0l, c0d) + pos, emin = std::fmin(c0l, c0d) + neg;
-    // Round-3 derivation (every step numbered there).  With v = 1 + e, s = sqrt(v), y = sqrt(s),
-    // D = kbeta (y+1)(s+1), w = e/D, om = w^2, the hardware's sqrt / rcp at 1 ulp (relative 2u) and every other
-    // operation correctly rounded (relative u):
-    //   rel(v)  <= u (1 + re) + de/vmin =: ev                 re = max |e| / (1 + e)
-    //   rel(D)  <= 3u + (ev/2 + 2u) sg + (ev/4 + 3u) et       sg = max s/(s+1), et = max y/(y+1)
-    //   rel(w)  <= 4u + rel(D) + de/|e| = ew + de/|e|
-    //   |beta^ - beta| <= 2 ew om + u (1 + om) + 2 de max(|e| / D^2)
-    //   |kb^ - kb| <= pu + 6u Dt + u |kb|       (kb = p - Dt, Dt = ck S the summed densities: S carries 5u, ck u; pu = u|p|
-    //                                             unless p is a float) <= pu + 6u|p| + 7u|kb| [kb < 0]
-    //   |f^ - f| <= (pu + 6u|p|)(1 + om) + 7u (|f| + |gamma|) + kbmax (2 ew om + u (1 + om) + Ae) + u |gamma| + u |f|
-    //               (|beta^| <= 1 + om; |kb beta| = |f + gamma|)
-    //   |gq^ - gq| <= |K| |f^ - f| + 5u |gq|        (K carries 4u, the product u)
-    // kbmax = max |kb| over states with covers in [0, 1]: the two densities sum to [0, 2].
-    const double vmin = 1.0 + emin, vmax = 1.0 + emax;
-    const bool admissible = vmin > 0.02;                          // otherwise: flag every cell (float64 everywhere)
-    const double vlo = std::fmax(vmin, 0.02);
-    const double smax = std::sqrt(std::fmax(vmax, vlo));
-    const double ymax = std::sqrt(smax);
-    const double sg = smax / (smax + 1.0), et = ymax / (ymax + 1.0);
-    const double re = std::fmax(std::fabs(emin) / vlo, std::fabs(emax) / std::fmax(vmax, vlo));
-    const double ev = u * (1.0 + re) + de_abs / vlo;
-    const double eD = 3.0 * u + (0.5 * ev + 2.0 * u) * sg + (0.25 * ev + 3.0 * u) * et;
-    const double ew = 4.0 * u + eD;
-    const double kbe = cbeta_host(p);                            // kbeta in float64
-    auto e_over_D2 = [&](double e) {
-        const double v = std::fmax(1.0 + e, vlo), sv = std::sqrt(v), yv = std::sqrt(sv);
-        const double D = kbe * (yv + 1.0) * (sv + 1.0);
-        return std::fabs(e) / (D * D);
-    };
-    const double Ae = 2.0 * de_abs * std::fmax(e_over_D2(emin), e_over_D2(emax));
-    const double kbmax = std::fmax(std::fabs(p.p), std::fabs(p.p - 2.0));
-    const double safety = 1.0 + 0x1p-7;                           // the second-order terms dropped above (~u relative)
-    const double pu = (double)(float)p.p == p.p ? 0.0 : std::fabs(p.p);
-    double A0 = safety * (kmax * std::fabs(p.dt) * kbmax * Ae + 2e-6);   // 2e-6: the float32 arithmetic of the threshold
-    if (!admissible) A0 = 1.0;                                    // tie_lo < 0: every cell goes to float64
-    const double eA = safety * 13.0 * u;
-    const double eK0d = safety * (6.0 * std::fabs(p.p) + pu + kbmax + 8.0 * std::fabs(p.gamma)) * u;
-    const double eK1d = safety * ((6.0 * std::fabs(p.p) + pu) * u + kbmax * (u + 2.0 * ew));
-    auto up = [](double v) { float f = (float)v; return (double)f < v ? std::nextafterf(f, INFINITY) : f; };   // never round a bound DOWN
-    P.tie_lo = (float)(0.5 - A0);
-    if ((double)P.tie_lo > 0.5 - A0) P.tie_lo = std::nextafterf(P.tie_lo, -INFINITY);
-    P.eA = up(eA);
-    const float eK0 = up(eK0d), eK1 = up(eK1d);
-    P.eK0s = p.dt < 0.0 ? eK0 : -eK0;
-    P.eK1s = p.dt < 0.0 ? eK1 : -eK1;
-    P.neK1s = -P.eK1s;                                           // the bracket in beta: (eK0s + eK1s) - eK1s*beta
-    P.eK01s = (float)((double)P.eK0s + (double)P.eK1s);
-    if (std::fabs((double)P.eK01s) < std::fabs((double)P.eK0s + (double)P.eK1s))     // never round the bound DOWN
-        P.eK01s = std::nextafterf(P.eK01s, P.eK01s < 0.f ? -1.f : 1.f);
-    return P;
-}
-
-// Coefficient sets of the two steps of a fused exact launch, split at the SAME scale (the coarser of
-// the two) and with the more conservative of the two tie thresholds: they then differ only in the
-// luminosity-dependent members (PhysLumF32).
-static void derive_f32_pair(const dw_params& p, double L1, double L2, PhysF32* P1, PhysF32* P2) {
-    const PhysF32 a = derive_f32(p, L1), b = derive_f32(p, L2);
-    const int hb = a.hi_bits < b.hi_bits ? a.hi_bits : b.hi_bits;
-    *P1 = derive_f32(p, L1, hb);
-    *P2 = derive_f32(p, L2, hb);
-    const float tie_lo = P1->tie_lo < P2->tie_lo ? P1->tie_lo : P2->tie_lo;
-    P1->tie_lo = tie_lo;
-    P2->tie_lo = tie_lo;
-}
-
-// Error bound of the float32 map on an UN-quantised state (step_generic<In, 3>, dw_step_generic.hpp; the first step of
-// an episode in the exact mode).  Same chain of estimates as derive_f32's round-3 bound with: iota = u for a float64
-// state (its values are rounded to float32 on the way in; the float64 re-evaluation reads the originals), 0 for a
-// float32 state; stencil sums of non-integers round (2u per sum of four, 3u for the sum of eight); the density
-// carries 5u + iota; the coefficient chain is the rounded one (no exact hi part): its absolute error is
-// (8u + iota) M + u |c0| with the per-cell M the kernel evaluates.
-static FirstStepBound derive_first_bound(const dw_params& p, double L, const PhysF32& P, bool from_f64,
-                                         double test_slack = -1.0) {
-    const double u = std::ldexp(1.0, -24), iota = from_f64 ? u : 0.0;
-    const double kmax = 1000.0;
-    const double To4 = std::pow(p.temp_optimal, 4), K = p.S * L / p.sigma;
-    const double e0 = K * (1.0 - p.albedo_bare * p.p) / To4 - 1.0;
-    const double c0l = e0 + p.q2 * (p.albedo_bare * p.p - p.albedo_light) / To4;
-    const double c0d = e0 + p.q2 * (p.albedo_bare * p.p - p.albedo_dark) / To4;
-    const double a1 = std::fabs((double)P.a1), a2 = std::fabs((double)P.a2), a3 = std::fabs((double)P.a3), a4 = std::fabs((double)P.a4);
-    const double c0m = std::fmax(std::fabs(c0l), std::fabs(c0d));
-    // admissible interval of e (both covers may be full in the same cell) and the worst-case absolute error of e
-    const double pos = (std::fmax((double)P.a1, 0.0) + std::fmax((double)P.a2, 0.0)) * 8 * kmax +
-                       (std::fmax((double)P.a3, 0.0) + std::fmax((double)P.a4, 0.0)) * kmax;
-    const double neg = (std::fmin((double)P.a1, 0.0) + std::fmin((double)P.a2, 0.0)) * 8 * kmax +
-                       (std::fmin((double)P.a3, 0.0) + std::fmin((double)P.a4, 0.0)) * kmax;
-    const double emax = std::fmax(c0l, c0d) + pos, emin = std::fmin(c0l, c0d) + neg;
-    const double Mmax = (a1 + a2) * 8 * kmax + (a3 + a4) * kmax;
-    const double de_max = (8.0 * u + iota) * Mmax + u * c0m;
-    const double vmin = 1.0 + emin, vmax = 1.0 + emax;
-    const bool admissible = vmin > 0.02;
-    const double vlo = std::fmax(vmin, 0.02);
-    const double smax = std::sqrt(std::fmax(vmax, vlo)), ymax = std::sqrt(smax);
-    const double sg = smax / (smax + 1.0), et = ymax / (ymax + 1.0);
-    const double re = std::fmax(std::fabs(emin) / vlo, std::fabs(emax) / std::fmax(vmax, vlo));
-    const double ev = u * (1.0 + re) + de_max / vlo;
-    const double eD = 3.0 * u + (0.5 * ev + 2.0 * u) * sg + (0.25 * ev + 3.0 * u) * et;
-    const double ew = 4.0 * u + eD;
-    const double kbe = cbeta_host(p);
-    const double Dmin = kbe * (std::sqrt(std::sqrt(vlo)) + 1.0) * (std::sqrt(vlo) + 1.0);
-    const double kbmax = std::fmax(std::fabs(p.p), std::fabs(p.p - 2.0));
-    const double pu = (double)(float)p.p == p.p ? 0.0 : std::fabs(p.p);
-    const double safety = 1.0 + 0x1p-7;
-    const double kK = 5.0 * u + iota;                             // relative error of a density
-    auto up = [](double v) { float f = (float)v; return (double)f < v ? std::nextafterf(f, INFINITY) : f; };
-    FirstStepBound B;
-    B.a1 = up(a1); B.a2 = up(a2); B.a3 = up(a3); B.a4 = up(a4);
-    B.c_de = up(safety * (8.0 * u + iota) * (1.0 + 8.0 * u));     // (1 + 8u): M itself is a float32 chain
-    B.c_c0 = up(safety * u * c0m);
-    // |kb^ - kb| <= pu + (kK + 2u)|p| + (kK + 3u)|kb| [kb < 0];  |gq^ - gq| <= |K| |f^ - f| + (kK + u)|gq|
-    B.eK0 = up(safety * (pu + (kK + 2.0 * u) * std::fabs(p.p) + kbmax * u + ((kK + 3.0 * u) + u) * std::fabs(p.gamma)));
-    B.eK1 = up(safety * (pu + (kK + 2.0 * u) * std::fabs(p.p) + kbmax * (u + 2.0 * ew)));
-    B.cW = up(safety * 2.0 * kbmax / Dmin);                       // 2 de |e| / D^2 <= 2 de |w| / Dmin
-    B.eA = up(safety * ((kK + 3.0 * u) + u + (kK + u)));
-    B.cS = up(safety * u);                                        // the sum k + gq rounds (u |sum|); a float64 k was rounded (u k)
-    B.slack = admissible ? 4e-6f : 1.0f;                          // the float32 arithmetic of eps itself; inadmissible: all float64
-    if (test_slack > (double)B.slack) B.slack = (float)test_slack;   // tests: a wider bracket flags many cells (list sweeps)
-    return B;
-}
-
-// ------------------------------------------------------------------------------------------------
-// kernel selection
-// ------------------------------------------------------------------------------------------------
-// Halo form of the wave-strip single-step kernels (HALO of step_stream_* and step_first_stream): 0 W == 256 (rotate),
-// 1 another multiple of 256, 2 any other W >= 256, 3 packed worlds (W < 256)
-static int halo_form(int W) { return W < 256 ? 3 : (W == 256 ? 0 : (W % 256 == 0 ? 1 : 2)); }
-
-// Rows per wave-strip: 64 (3 % halo re-reads) when `groups` columns of strips then make at least `target` strips; shorter
-// strips for smaller jobs - a strip is a serial march of ~0.8 us per row, so with few strips the launch takes as long as
-// ONE strip and most SIMDs idle.  Never more than the grid's height.
-static int strip_rows(long groups, int H, long target) {
-    int sr = 64;
-    while (sr > 8 && groups * ((H + sr - 1) / sr) < target) sr >>= 1;
-    return H < sr ? H : sr;
-}
-
-static StepPlan plan_steps(const dw_params& p, const Switches& sw) {
-    StepPlan s;
-    s.sym_albedo = (p.albedo_dark - p.albedo_bare) == -(p.albedo_light - p.albedo_bare) && !sw.no_sym;
-    s.halo = halo_form(p.width);
-    // Packed mode of the wave-strip kernels: narrow worlds whose width divides 256 sit side by side in one 256-column wave
-    // row (256/W worlds per wave) - only for ensembles with enough wave-strips to occupy the GPU: a lone strip is a serial
-    // march down 64 rows, ~50 us, where the tiled kernel answers in ~9 us; DW_PACK_MIN_STRIPS overrides for tests.
-    // Any width below 256 that is a multiple of 4, provided at least 70 % of the 64 lanes get columns (W = 96: 2 worlds on
-    // 48 lanes; W = 132: one world on 33 lanes - left to the tiled kernel).
-    const int lpw = p.width / 4, wpr = lpw ? 64 / lpw : 0;
-    const bool pack_shape = p.width >= 8 && p.width < 256 && wpr >= 1 && wpr * lpw * 10 >= 64 * 7 && !sw.no_pack;
-    const long pack_strips = pack_shape ? (long)((p.batch + wpr - 1) / wpr) * ((p.height + 63) / 64) : 0;
-    const bool packable = pack_shape && pack_strips >= (sw.pack_min_strips >= 0 ? sw.pack_min_strips : 512);
-    const bool quads = p.precision != DW_PRECISION_F64 && p.width % 4 == 0;
-    // the wave-strip kernels take the step: W >= 256 or a packed ensemble, unless DW_KERNEL=tiled (A/B experiments)
-    if (quads && (p.width >= 256 || packable) && std::strcmp(sw.kernel, "tiled") != 0) {
-        s.kind = STEP_STREAM;
-        s.packed = p.width < 256;
-        StripGeom& g = s.sgeom;
-        g.B = p.batch; g.H = p.height; g.W = p.width;
-        g.ncs = (p.width + 255) / 256;
-        g.lpw = s.packed ? lpw : 64;
-        g.wpr = s.packed ? wpr : 1;
-        const long groups = s.packed ? (p.batch + wpr - 1) / wpr : p.batch;
-        // two strips per SIMD; DW_STRIP_ROWS overrides (experiments)
-        g.SR = sw.strip_rows >= 1 ? (p.height < sw.strip_rows ? p.height : sw.strip_rows)
-                                  : strip_rows(groups * g.ncs, p.height, 2048);
-        g.nrs = (p.height + g.SR - 1) / g.SR;
-        g.nstrips = (int)(groups * g.nrs * g.ncs);
-        g.nwg = (g.nstrips + 3) / 4;
-        g.chunk = (g.nwg + 7) / 8;
-        g.qcap = kWaveQueueCap;
-        int mcap = kMismatchCap;
-        if (sw.queue_cap >= 0 && sw.queue_cap < kWaveQueueCap) g.qcap = sw.queue_cap;   // tests: force the overflow fallbacks
-        if (sw.mismatch_cap >= 0 && sw.mismatch_cap < kMismatchCap) mcap = sw.mismatch_cap;
-        g.force_rescan = sw.force_rescan ? 1 : 0;               // tests: the strip maximum's re-scan path
-        s.allow_fuse = !sw.no_fuse;
-        // W == 1024: one WORKGROUP per row strip, its four waves side by side (edge columns through LDS) instead of
-        // five overlapped 248-column strips (DW_NO_RING: experiments)
-        const bool ring = p.width == 1024 && !sw.no_ring;
-        s.fused_mode = p.width <= 256 ? kFusedRot : (ring ? kFusedRing : kFusedOvl);
-        FusedGeom& f = s.fgeom;
-        f.B = p.batch; f.H = p.height; f.W = p.width;
-        f.SR = g.SR;
-        f.nrs = g.nrs;
-        f.lpw = g.lpw; f.wpr = g.wpr;
-        f.cols_per_strip = p.width <= 256 ? 256 : (ring ? 1024 : 248);
-        f.ncs = s.packed ? 1 : (p.width + f.cols_per_strip - 1) / f.cols_per_strip;
-        f.nstrips = (int)(groups * f.nrs * f.ncs);
-        f.nwg = ring ? f.nstrips : (f.nstrips + 3) / 4;
-        f.chunk = (f.nwg + 7) / 8;
-        f.qcap = g.qcap;
-        f.mcap = mcap;
-        f.sure_need = 9 * p.n_agents + 9 * mcap + 1;            // (dw_step_fused.hpp, STATS)
-        s.trace_pairs = s.allow_fuse && !s.packed && s.fused_mode != kFusedRing;
-        // (a world's plane is addressed by 32-bit byte offsets there)
-        s.fmt_planes = p.precision == DW_PRECISION_FAST && s.allow_fuse && !s.packed && s.fused_mode == kFusedOvl && !sw.no_fmt_planes &&
-                       (size_t)p.height * p.width * sizeof(plane_t) < ((size_t)1 << 31);
-    } else if (quads && p.width >= 64) {
-        s.kind = STEP_TILED;
-        const int Wq = p.width / 4;
-        if (Wq >= 64) {
-            s.tcq = 64; s.rpt = 4;
-            if (sw.tile_rpt == 2 || sw.tile_rpt == 4 || sw.tile_rpt == 8) s.rpt = sw.tile_rpt;   // tuning experiments only
-        }
-        else if (Wq >= 32) { s.tcq = 32; s.rpt = 4; }
-        else { s.tcq = 16; s.rpt = 2; }
-        const int TR = (256 / s.tcq) * s.rpt;
-        Geom& g = s.geom;
-        g.B = p.batch; g.H = p.height; g.W = p.width; g.Wq = Wq;
-        g.tiles_r = (p.height + TR - 1) / TR;
-        g.tiles_c = (Wq + s.tcq - 1) / s.tcq;
-        g.ntiles = p.batch * g.tiles_r * g.tiles_c;
-        g.chunk = (g.ntiles + 7) / 8;
-        g.qcap = kMaxFix;
-        if (sw.queue_cap >= 0 && sw.queue_cap < kMaxFix) g.qcap = sw.queue_cap;   // tests: force the overflow fallbacks
-        s.tile_lds = (size_t)2 * (TR + 2) * (s.tcq + 2) * 4 * sizeof(float);
-    }                                                           // narrow grids and DW_PRECISION_F64: generic kernel
-    s.need_fixq = p.precision == DW_PRECISION_EXACT && s.kind == STEP_TILED;
-    s.pw_stream = s.kind == STEP_STREAM && !s.packed;
-    // The first step from an un-quantised state reads it in its upload format: float32 (fast mode); exact mode: float32
-    // with the tie bound for non-integer inputs, float64 only for the flagged cells (DW_FIRST_STEP_F64=1: every cell in
-    // float64, as in round 2 - experiments); f64 mode: float64 (bit-identical to the reference's first step).
-    s.first_prec = p.precision == DW_PRECISION_FAST ? 1 : (p.precision == DW_PRECISION_EXACT && !sw.first_f64 ? 3 : 2);
-    // Every shape the steady-state wave-strip kernels take, and any multiple of 256: the wave-strip form of the same
-    // arithmetic (dw_step_first.hpp; ~4x fewer vector instructions per cell).  DW_FIRST_GENERIC=1: the one-thread-per-cell
-    // kernel (experiments, tests)
-    s.first_stream = (p.width % 256 == 0 || s.kind == STEP_STREAM) && s.first_prec != 2 && !sw.first_generic;
-    if (s.first_stream) {
-        FirstGeom& fg = s.first_geom;
-        fg.B = p.batch; fg.H = p.height; fg.W = p.width;
-        fg.lpw = s.packed ? lpw : 64;
-        fg.wpr = s.packed ? wpr : 1;
-        fg.ncs = s.packed ? 1 : (p.width + 255) / 256;
-        const long groups = s.packed ? (p.batch + fg.wpr - 1) / fg.wpr : p.batch;
-        // four strips per SIMD; DW_STRIP_ROWS overrides (experiments, tests), never above the 64 rows FirstGeom::SR allows
-        const int want = sw.strip_rows < 64 ? sw.strip_rows : 64;
-        fg.SR = sw.strip_rows >= 1 ? (p.height < want ? p.height : want) : strip_rows(groups * fg.ncs, p.height, 4096);
-        fg.nrs = (p.height + fg.SR - 1) / fg.SR;
-        fg.nstrips = (int)(groups * fg.nrs * fg.ncs);
-    }
-    return s;
-}
-
 // near-tie queues of the tiled exact kernel (the streaming kernel keeps them in LDS) when `plan` needs them: room for 1/64
 // of all cells (the bound flags ~0.3-0.5 %), at least 2048 entries per queue; 48 bytes per entry, i.e. 0.75 B per cell
 // on top of the 16 B of state
@@ -734,16 +333,24 @@ static int ensure_fixq(dw_handle* h, const StepPlan& plan) {
     return DW_OK;
 }
 
-// What every single-step launch passes besides its input planes
+// What every step launch passes besides its input planes
 struct StepOut {
     plane_t* L; plane_t* D;                   // the binary16 planes of the other buffer
-    PhysF32 P;
+    PhysF32 P;                                // the constants of a single step at one luminosity (launch_forward) ...
     PhysF64 P64;
     StatsDev* stats;                          // the new state's reductions (all zero before the step) ...
     unsigned long long* fixups;               // ... and the float64 fix-up counter behind them
     unsigned long long* zero_me;              // the old state's reductions: cleared for the step after this one
     int zero_n;
 };
+// ... all of it but the constants
+static StepOut step_out(const dw_handle* h) {
+    const int out = 1 - h->cur;
+    StatsDev* stats = h->stats2[1 - h->sp].get();                       // invariant: all zero
+    return StepOut{h->L16[out].get(), h->D16[out].get(), PhysF32{}, PhysF64{}, stats, &stats[h->prm.batch].sum_l,
+                   reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get()),
+                   (int)(h->stats_bytes / sizeof(unsigned long long))};
+}
 
 template <int TCQ, int RPT, bool EXACT>
 static int launch_tiled(dw_handle* h, const plane_t* iL, const plane_t* iD, const StepOut& o, const FixQ& fq) {
@@ -768,12 +375,18 @@ static int launch_tiled(dw_handle* h, const plane_t* iL, const plane_t* iD, cons
     return DW_OK;
 }
 
-// one thread per cell (several for big jobs), any input format
+// one thread per cell (several for big jobs: *cpt): the grid of step_generic / step_generic_pw
+static dim3 generic_grid(const dw_params& p, int* cpt) {
+    *cpt = generic_cells_per_thread(p.batch, (long long)p.height * p.width);
+    return dim3((unsigned)(((long long)p.height * p.width + 256LL * *cpt - 1) / (256LL * *cpt)), (unsigned)p.batch);
+}
+
+// ... any input format
 template <class T, int PREC>
 static auto launch_generic(dw_handle* h, const T* iL, const T* iD, const StepOut& o, const FirstStepBound& fb = {}) {
     const dw_params& p = h->prm;
-    const int cpt = generic_cells_per_thread(p.batch, (long long)p.height * p.width);
-    const dim3 grid((unsigned)(((long long)p.height * p.width + 256LL * cpt - 1) / (256LL * cpt)), (unsigned)p.batch);
+    int cpt;
+    const dim3 grid = generic_grid(p, &cpt);
     hipLaunchKernelGGL((step_generic<T, PREC>), grid, dim3(256), 0, h->stream, iL, iD, o.L, o.D, p.height, p.width, o.P, o.P64,
                        o.stats, o.fixups, o.zero_me, o.zero_n, cpt, fb);
 }
@@ -856,11 +469,9 @@ static void step_done(dw_handle* h, double L, bool stepped, bool per_world = fal
 static int launch_forward(dw_handle* h, double L) {
     const dw_params& p = h->prm;
     NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
-    const int out = 1 - h->cur;
-    StatsDev* stats = h->stats2[1 - h->sp].get();                       // invariant: all zero
-    const StepOut o{h->L16[out].get(), h->D16[out].get(), derive_f32(p, L), make_f64(p, L), stats, &stats[p.batch].sum_l,
-                    reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get()),
-                    (int)(h->stats_bytes / sizeof(unsigned long long))};
+    StepOut o = step_out(h);
+    o.P = derive_f32(p, L);
+    o.P64 = make_f64(p, L);
 #ifdef DW_TUNING
     if (const char* e = std::getenv("DW_ABLATE")) {
         if (std::strcmp(e, "copy") == 0) {
@@ -868,9 +479,9 @@ static int launch_forward(dw_handle* h, double L) {
             const size_t n4 = h->cells * sizeof(plane_t) / 16;
             hipLaunchKernelGGL(copy_planes, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, h->stream,
                                reinterpret_cast<const float4*>(h->L16[in].get()), reinterpret_cast<const float4*>(h->D16[in].get()),
-                               reinterpret_cast<float4*>(h->L16[out].get()), reinterpret_cast<float4*>(h->D16[out].get()), n4);
+                               reinterpret_cast<float4*>(o.L), reinterpret_cast<float4*>(o.D), n4);
             HIPCHK(hipGetLastError());
-            h->cur = out; h->sp = 1 - h->sp; h->stepped = true; h->L_last = L; h->L_per_world = false;
+            step_done(h, L, true);
             return DW_OK;
         }
         const int v = std::strcmp(e, "nomath") == 0 ? 1 : 0;
@@ -904,18 +515,13 @@ struct PwLayout {
 static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* row64, const FirstStepBound* rowfb) {
     const dw_params& p = h->prm;
     const StepPlan& pl = h->plan;
-    const int out = 1 - h->cur;
-    plane_t *oL = h->L16[out].get(), *oD = h->D16[out].get();
-    StatsDev* stats = h->stats2[1 - h->sp].get();                       // invariant: all zero
-    unsigned long long* fixups = &stats[p.batch].sum_l;
-    unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get());
-    const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
+    const StepOut o = step_out(h);                              // (its constants stay unset: the rows carry them)
     const bool ex = p.precision == DW_PRECISION_EXACT;
     auto generic = [&](auto* iL, auto* iD, auto PR) {
-        const int cpt = generic_cells_per_thread(p.batch, (long long)p.height * p.width);
-        const dim3 grid((unsigned)(((long long)p.height * p.width + 256LL * cpt - 1) / (256LL * cpt)), (unsigned)p.batch);
-        hipLaunchKernelGGL((step_generic_pw<elem_t<decltype(iL)>, PR>), grid, dim3(256), 0, h->stream, iL, iD, oL, oD, p.height,
-                           p.width, row32, row64, rowfb, stats, fixups, zero_me, zero_n, cpt);
+        int cpt;
+        const dim3 grid = generic_grid(p, &cpt);
+        hipLaunchKernelGGL((step_generic_pw<elem_t<decltype(iL)>, PR>), grid, dim3(256), 0, h->stream, iL, iD, o.L, o.D,
+                           p.height, p.width, row32, row64, rowfb, o.stats, o.fixups, o.zero_me, o.zero_n, cpt);
     };
     const plane_t* iL = h->L16[h->cur].get();
     const plane_t* iD = h->D16[h->cur].get();
@@ -924,7 +530,7 @@ static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* 
             with_int<1, 3, 2>(pl.first_prec, [&](auto PR) { generic(uL, uD, PR); });
         });
     } else if (pl.pw_stream && ex) {
-        const StreamExactPwArgs A{iL, iD, oL, oD, pl.sgeom, row32, row64, stats, fixups, zero_me, zero_n};
+        const StreamExactPwArgs A{iL, iD, o.L, o.D, pl.sgeom, row32, row64, o.stats, o.fixups, o.zero_me, o.zero_n};
         with_int<0, 1, 2>(pl.halo, [&](auto HL) {
             with_bool(pl.sym_albedo, [&](auto SYM) {
                 hipLaunchKernelGGL((step_stream_exact_pw<HL, SYM>), dim3((unsigned)pl.sgeom.chunk * 8u), dim3(256), 0, h->stream, A);
@@ -932,8 +538,8 @@ static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* 
         });
     } else if (pl.pw_stream) {
         with_int<0, 1, 2>(pl.halo, [&](auto HL) {
-            hipLaunchKernelGGL((step_stream_fast_pw<HL>), dim3((unsigned)pl.sgeom.chunk * 8u), dim3(256), 0, h->stream, iL, iD, oL,
-                               oD, pl.sgeom, row32, row64, stats, fixups, zero_me, zero_n);
+            hipLaunchKernelGGL((step_stream_fast_pw<HL>), dim3((unsigned)pl.sgeom.chunk * 8u), dim3(256), 0, h->stream, iL, iD, o.L,
+                               o.D, pl.sgeom, row32, row64, o.stats, o.fixups, o.zero_me, o.zero_n);
         });
     } else {                                                    // PREC 0 exact, 1 fast, 2 f64
         const int prec = p.precision == DW_PRECISION_F64 ? 2 : (ex ? 0 : 1);
@@ -961,19 +567,16 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
                                  float thr_hi = 0.f, StatsDev* trace = nullptr) {
     const dw_params& p = h->prm;
     const StepPlan& pl = h->plan;
-    const int in = h->cur, out = 1 - h->cur;
     const bool exact = p.precision == DW_PRECISION_EXACT;
     PhysF32 P1, P2;
     if (exact) derive_f32_pair(p, L1, L2, &P1, &P2);
     else { P1 = derive_f32(p, L1); P2 = derive_f32(p, L2); }
-    unsigned long long* zero_me = reinterpret_cast<unsigned long long*>(h->stats2[h->sp].get());
-    const int zero_n = (int)(h->stats_bytes / sizeof(unsigned long long));
+    const StepOut o = step_out(h);                              // (the pair's constants: P1, P2; no reductions)
     const FusedGeom& g = pl.fgeom;
     const dim3 grid((unsigned)g.chunk * 8u);
-    const plane_t *inL = h->L16[in].get(), *inD = h->D16[in].get();
-    plane_t *outL = h->L16[out].get(), *outD = h->D16[out].get();
+    const plane_t *inL = h->L16[h->cur].get(), *inD = h->D16[h->cur].get();
     auto exact_args = [&] {
-        return FusedExactArgs{inL, inD, outL, outD, g, P1, lum_part(P2), zero_me, zero_n, pstats, thr_hi, make_f64(p, L1), L1, L2};
+        return FusedExactArgs{inL, inD, o.L, o.D, g, P1, lum_part(P2), o.zero_me, o.zero_n, pstats, thr_hi, make_f64(p, L1), L1, L2};
     };
     if (trace && exact) {
         const TraceExactArgs A{exact_args(), trace, h->sw.force_rescan ? 1 : 0};
@@ -984,12 +587,12 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
         });
     } else if (trace) {
         with_int<kFusedRot, kFusedOvl>(pl.fused_mode, [&](auto MODE) {
-            hipLaunchKernelGGL((trace_pair_fast<MODE>), grid, dim3(256), 0, h->stream, inL, inD, outL, outD, g, P1, P2, zero_me,
-                               zero_n, trace);
+            hipLaunchKernelGGL((trace_pair_fast<MODE>), grid, dim3(256), 0, h->stream, inL, inD, o.L, o.D, g, P1, P2, o.zero_me,
+                               o.zero_n, trace);
         });
     } else if (pl.fmt_planes && !pstats && !exact) {
-        hipLaunchKernelGGL((step_stream_fused2_fmt_pw<kFusedOvl>), grid, dim3(256), 0, h->stream, inL, inD, outL, outD, g, P1, P2,
-                           zero_me, zero_n);
+        hipLaunchKernelGGL((step_stream_fused2_fmt_pw<kFusedOvl>), grid, dim3(256), 0, h->stream, inL, inD, o.L, o.D, g, P1, P2,
+                           o.zero_me, o.zero_n);
     } else if (exact) {
         const FusedExactArgs A = exact_args();
         with_bool(pstats != nullptr, [&](auto STATS) {
@@ -1002,8 +605,8 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
     } else {
         with_bool(pstats != nullptr, [&](auto STATS) {
             with_fused_layout(pl, [&](auto MODE, auto PACK) {
-                hipLaunchKernelGGL((step_stream_fused2<MODE, PACK, STATS>), grid, dim3(256), 0, h->stream, inL, inD, outL, outD, g,
-                                   P1, P2, zero_me, zero_n, pstats, thr_hi);
+                hipLaunchKernelGGL((step_stream_fused2<MODE, PACK, STATS>), grid, dim3(256), 0, h->stream, inL, inD, o.L, o.D, g,
+                                   P1, P2, o.zero_me, o.zero_n, pstats, thr_hi);
             });
         });
     }
@@ -1041,6 +644,48 @@ static int stage_host_actions(dw_handle* h, const int32_t* action, int b, int n)
         HIPCHK(hipMemcpyAsync(h->action_tmp.get(), action, sizeof(int) * (size_t)b * n, hipMemcpyHostToDevice,
                               h->stream));
     return DW_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// a new state
+// ------------------------------------------------------------------------------------------------
+static int clear_stats(dw_handle* h) {
+    for (int i = 0; i < 2; ++i) HIPCHK(hipMemsetAsync(h->stats2[i].get(), 0, h->stats_bytes, h->stream));
+    return DW_OK;
+}
+
+// An upload or a draw has queued a new current state: quantised in the `cur` planes (OWN_NONE) or un-quantised in the
+// buffers of `kind` (OWN_CUR).  There is no step pair any more, and no snapshot either (a snapshot's previous state may
+// have lived in the un-quantised buffers).
+static void state_arrived(dw_handle* h, UnqOwner unq, UnqKind kind = UNQ_F64) {
+    if (unq == OWN_CUR) h->unq_kind = kind;
+    h->unq = unq;
+    h->have_state = true;
+    h->stepped = false;
+    for (auto& sn : h->snap) sn.valid = false;
+}
+
+// dw_init_random[_quantised]: the synthetic initial state drawn into the planes L, D, and the agents.  The draw reduces
+// its own values into the per-world statistics (no second pass over the planes).
+template <class T>
+static auto init_random_into(dw_handle* h, uint64_t seed, T* L, T* D) {
+    const dw_params& p = h->prm;
+    if (int crc = clear_stats(h)) return crc;
+    const int ncell = p.height * p.width;
+    const dim3 g((unsigned)((ncell + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
+    hipLaunchKernelGGL((init_random_cells<T>), g, dim3(256), 0, h->stream, L, D, ncell,
+                       (long long)p.world_offset, (unsigned long long)seed, (float)p.light_proportion,
+                       (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp].get());
+    HIPCHK(hipGetLastError());
+    if (p.n_agents) {
+        const int bn = p.batch * p.n_agents;
+        hipLaunchKernelGGL(init_random_agents, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->idx.get(), h->st.get(),
+                           p.batch, p.n_agents, p.height, p.width, (long long)p.world_offset,
+                           (unsigned long long)seed);
+        HIPCHK(hipGetLastError());
+    }
+    h->have_agents = true;
+    return (int)DW_OK;                          // (statistics: reduced by the draw itself)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1190,11 +835,7 @@ int dw_get_params(const dw_handle* h, dw_params* out) {
 
 // ---- state in / out ---------------------------------------------------------------------------
 
-// reductions of the current state, whatever its format (after uploads / init, so that dw_reduce is always valid)
-static int clear_stats(dw_handle* h) {
-    for (int i = 0; i < 2; ++i) HIPCHK(hipMemsetAsync(h->stats2[i].get(), 0, h->stats_bytes, h->stream));
-    return DW_OK;
-}
+// reductions of the current state, whatever its format (after uploads, so that dw_reduce is always valid)
 static int refresh_stats(dw_handle* h) {
     const dw_params& p = h->prm;
     if (int rc = clear_stats(h)) return rc;
@@ -1215,11 +856,7 @@ int dw_upload_state_f64(dw_handle* h, const double* light, const double* dark) {
     if (int arc = ensure_f64(h)) return arc;
     HIPCHK(hipMemcpyAsync(h->L64.get(), light, sizeof(double) * h->cells, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->D64.get(), dark, sizeof(double) * h->cells, hipMemcpyHostToDevice, h->stream));
-    h->unq_kind = UNQ_F64;
-    h->unq = OWN_CUR;
-    h->have_state = true;
-    h->stepped = false;
-    for (auto& sn : h->snap) sn.valid = false;                      // a snapshot's previous state may have lived in these buffers
+    state_arrived(h, OWN_CUR, UNQ_F64);
     int rc = refresh_stats(h);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller
@@ -1241,7 +878,7 @@ int dw_upload_state_f32(dw_handle* h, const float* light, const float* dark, int
         hipLaunchKernelGGL(f32nat_to_plane, dim3(blocks), dim3(256), 0, h->stream, sL, h->L16[h->cur].get(), h->cells);
         hipLaunchKernelGGL(f32nat_to_plane, dim3(blocks), dim3(256), 0, h->stream, sD, h->D16[h->cur].get(), h->cells);
         HIPCHK(hipGetLastError());
-        h->unq = OWN_NONE;
+        state_arrived(h, OWN_NONE);
     } else {
         int rc = ensure_u32(h);
         if (rc) return rc;
@@ -1250,12 +887,8 @@ int dw_upload_state_f32(dw_handle* h, const float* light, const float* dark, int
         hipLaunchKernelGGL(f32nat_to_permille, dim3(blocks), dim3(256), 0, h->stream, h->U32L.get(), h->U32L.get(), h->cells);
         hipLaunchKernelGGL(f32nat_to_permille, dim3(blocks), dim3(256), 0, h->stream, h->U32D.get(), h->U32D.get(), h->cells);
         HIPCHK(hipGetLastError());
-        h->unq_kind = UNQ_F32;
-        h->unq = OWN_CUR;
+        state_arrived(h, OWN_CUR, UNQ_F32);
     }
-    h->have_state = true;
-    h->stepped = false;
-    for (auto& sn : h->snap) sn.valid = false;
     int rc = refresh_stats(h);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1299,59 +932,20 @@ int dw_download_agents(dw_handle* h, int32_t* indices, double* states) {
 
 int dw_init_random(dw_handle* h, uint64_t seed) {
     NEED(h, DW_EINVAL, "null handle");
-    const dw_params& p = h->prm;
-    HIPCHK(hipSetDevice(p.device));
-    int rc = ensure_u32(h);                     // the synthetic initial state is un-quantised like the reference's
-    if (rc) return rc;
-    // the draw reduces its own values into the per-world statistics (no second pass over the planes)
-    if (int crc = clear_stats(h)) return crc;
-    const int ncell = p.height * p.width;
-    const dim3 g((unsigned)((ncell + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
-    hipLaunchKernelGGL((init_random_cells<float>), g, dim3(256), 0, h->stream, h->U32L.get(), h->U32D.get(), ncell,
-                       (long long)p.world_offset, (unsigned long long)seed, (float)p.light_proportion,
-                       (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp].get());
-    HIPCHK(hipGetLastError());
-    if (p.n_agents) {
-        const int bn = p.batch * p.n_agents;
-        hipLaunchKernelGGL(init_random_agents, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->idx.get(), h->st.get(),
-                           p.batch, p.n_agents, p.height, p.width, (long long)p.world_offset,
-                           (unsigned long long)seed);
-        HIPCHK(hipGetLastError());
-    }
-    h->have_agents = true;
-    h->unq_kind = UNQ_F32;
-    h->unq = OWN_CUR;
-    h->have_state = true;
-    h->stepped = false;
-    for (auto& sn : h->snap) sn.valid = false;
-    return DW_OK;                               // (statistics: reduced by the draw itself)
+    HIPCHK(hipSetDevice(h->prm.device));
+    if (int rc = ensure_u32(h)) return rc;      // the synthetic initial state is un-quantised like the reference's
+    if (int rc = init_random_into(h, seed, h->U32L.get(), h->U32D.get())) return rc;
+    state_arrived(h, OWN_CUR, UNQ_F32);
+    return DW_OK;
 }
 
 int dw_init_random_quantised(dw_handle* h, uint64_t seed) {
     NEED(h, DW_EINVAL, "null handle");
-    const dw_params& p = h->prm;
-    HIPCHK(hipSetDevice(p.device));
-    if (int crc = clear_stats(h)) return crc;
-    const int ncell = p.height * p.width;
-    const dim3 g((unsigned)((ncell + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
-    hipLaunchKernelGGL((init_random_cells<plane_t>), g, dim3(256), 0, h->stream, h->L16[h->cur].get(), h->D16[h->cur].get(), ncell,
-                       (long long)p.world_offset, (unsigned long long)seed, (float)p.light_proportion,
-                       (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp].get());
-    HIPCHK(hipGetLastError());
-    if (p.n_agents) {
-        const int bn = p.batch * p.n_agents;
-        hipLaunchKernelGGL(init_random_agents, dim3((bn + 255) / 256), dim3(256), 0, h->stream, h->idx.get(), h->st.get(),
-                           p.batch, p.n_agents, p.height, p.width, (long long)p.world_offset,
-                           (unsigned long long)seed);
-        HIPCHK(hipGetLastError());
-    }
-    h->have_agents = true;
-    h->unq = OWN_NONE;
-    h->have_state = true;
-    h->stepped = false;
-    for (auto& sn : h->snap) sn.valid = false;
+    HIPCHK(hipSetDevice(h->prm.device));
+    if (int rc = init_random_into(h, seed, h->L16[h->cur].get(), h->D16[h->cur].get())) return rc;
+    state_arrived(h, OWN_NONE);
     release_unquantised(h);
-    return DW_OK;                               // (statistics: reduced by the draw itself)
+    return DW_OK;
 }
 
 int dw_download_planes(dw_handle* h, int which, double* light, double* dark) {
@@ -2087,7 +1681,7 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     // launch, worlds in LDS (episode_mlp).  Until then - the first two steps of an episode, whose current /
     // previous state is the un-quantised upload - and for large worlds: one launch sequence per step.
     const int Cc = p.height * p.width;
-    const int wpb = Cc <= 256 ? 4 : (Cc <= 1024 ? 2 : 1);
+    const int wpb = worlds_per_block(Cc);
     size_t lds = 0;
     const EpisodeForm form = episode_mlp_form(h, &lds);
     const bool wave_kernel = form == EPISODE_WAVE, small = form != EPISODE_STEPWISE;
@@ -2216,7 +1810,7 @@ static EpisodeForm episode_form(const dw_handle* h) {
 static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes) {
     const dw_params& p = h->prm;
     const int Cc = p.height * p.width, N = p.n_agents;
-    const int wpb = Cc <= 256 ? 4 : (Cc <= 1024 ? 2 : 1);
+    const int wpb = worlds_per_block(Cc);
     // H*W <= 256 with at most four agents (the ES trainers' own 16x16 x 4): one wave per world (dw_episode_wave.hpp)
     const bool wave_kernel = Cc <= kEwMaxCells && 16 * N <= 64 && !h->sw.no_episode_wave;
     const size_t lds = wave_kernel ? episode_wave_shared_bytes() + episode_mlp_wave_world_bytes(Cc, N) * 4
@@ -2355,7 +1949,7 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
         return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
                                     agent_ok);
     const bool wave_kernel = form == EPISODE_WAVE;
-    const int wpb = C <= 256 ? 4 : (C <= 1024 ? 2 : 1);
+    const int wpb = worlds_per_block(C);
     const size_t world_bytes = wave_kernel ? episode_wave_world_bytes(C, N) : episode_world_bytes(C, N);
     const size_t lds = world_bytes * wpb + (wave_kernel ? episode_wave_shared_bytes() : 0);
     NEED(lds <= 160 * 1024, DW_EINVAL, "too many agents for the LDS-resident episode kernel");

@@ -5,24 +5,9 @@
 #include <type_traits>
 
 #include "dw_physics.hpp"
+#include "dw_types.hpp"    // StatsDev, Geom, plane_t
 
 namespace dw {
-
-struct StatsDev {             // mirrors dw_world_stats
-    unsigned int max_k;
-    unsigned int reserved;    // the one-wave-per-world episode kernels: float64 re-evaluations of the world's last step
-    unsigned long long sum_l;
-    unsigned long long sum_d;
-};
-
-struct Geom {
-    int B, H, W;
-    int Wq;                   // W / 4 (tiled kernel only)
-    int tiles_r, tiles_c;     // tiles per world
-    int ntiles;               // B * tiles_r * tiles_c
-    int chunk;                // ceil(ntiles / 8): tiles per XCD
-    int qcap;                 // near-tie LDS queue capacity in use (<= kMaxFix; tests shrink it)
-};
 
 // ---------------------------------------------------------------------------------------------
 // wave / workgroup reductions (wavefront shuffles, 64 lanes)
@@ -49,7 +34,6 @@ __device__ __forceinline__ float wave_max(float v) {
 // The two un-quantised formats exist only until the first step has consumed them (then one step longer as the
 // "previous state" observations are derived from); the adaptors below let the cold kernels read all three.
 // ---------------------------------------------------------------------------------------------
-typedef _Float16 plane_t;
 __device__ __forceinline__ double to_natural(double x) { return x; }
 __device__ __forceinline__ double to_natural(float k) { return (double)k / 1000.0; }
 // (a binary16 plane holds per-mille INTEGERS: the division-free form is the correctly rounded k / 1000.0, dw_physics.hpp)

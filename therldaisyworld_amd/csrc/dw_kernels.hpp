@@ -1,5 +1,7 @@
 // dw_kernels.hpp — HIP kernels of the RLDaisyWorld hot path for gfx950 (MI355X), one header per family:
 //
+//   dw_types.hpp          plain data shared with the host code: constant sets, launch geometry, capacities (no HIP)
+//   dw_plan.hpp           host only: switches, kernel selection and launch geometry, the constants of a step (no HIP)
 //   dw_physics.hpp        per-cell arithmetic (float64 staging; fused float32 algebra, packed two-cell form)
 //   dw_common.hpp         reductions, adaptors, the four-cell row group `cells4`
 //   dw_step_generic.hpp   step_generic      one thread per cell, any shape / float64: the in-library reference

@@ -15,17 +15,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dw_types.hpp"    // PhysF64, dw_f32x2, DW_PAIR, PhysF32, PhysLumF32
+
 namespace dw {
 
 // ---------------------------------------------------------------------------------------------
 // float64 constants (host fills; passed to kernels by value)
 // ---------------------------------------------------------------------------------------------
-struct PhysF64 {
-    double p, g, S, sigma, gamma, q, q2, dt;
-    double ab, al, ad, To;       // albedo bare/light/dark, optimal temperature
-    double L;                    // luminosity of this pass
-    double w0, w1, w2;           // daisy kernel centre / edge / corner (ref :270-273)
-};
 
 // everything the reference's forward() derives for one cell
 struct CellF64 {
@@ -148,7 +144,7 @@ __device__ inline NewCoverF64 cell_f64_lean(const PhysF64& P, const unsigned int
 // With li, di the centre values and Sl8, Sd8 the sums over the 8 Moore neighbours (all per-mille),
 // K = S*L/sigma and To4 = To^4, the reference's T_x^4 (x = light, dark) is affine in them:
 //   e_x := T_x^4/To4 - 1 = c0x + a1*Sl8 + a2*Sd8 + a3*li + a4*di
-// (coefficients derived in float64 on the host every step, see derive_f32() in dw_api.hip).
+// (coefficients derived in float64 on the host every step, see derive_f32() in dw_plan.hpp).
 //
 // Accuracy devices (they are what makes the exact mode's tie bound small):
 //  * every coefficient is split as hi + lo with hi a multiple of 2^-hi_bits chosen so that, for a
@@ -168,43 +164,9 @@ __device__ inline NewCoverF64 cell_f64_lean(const PhysF64& P, const unsigned int
 // lanes with the instruction's op_sel bits (free), and constants that meet in one instruction share a pair.
 // This halves the SGPR footprint of a coefficient set (the exact fused kernel spilled ~27 SGPRs into VGPR
 // lanes and paid ~3 v_readlane per cell-evaluation for them).  Each pair is also addressable as two floats.
-typedef float dw_f32x2 __attribute__((ext_vector_type(2)));
-#define DW_PAIR(lo_name, hi_name, pair_name) \
-    union { struct { float lo_name, hi_name; }; dw_f32x2 pair_name; }
-
-struct PhysF32 {
-    // e_x = c0x + a1*Sl8 + a2*Sd8 + a3*li + a4*di, coefficients split hi + lo (exact mode) ...
-    DW_PAIR(a1h, a2h, a12h);
-    DW_PAIR(a3h, a4h, a34h);
-    DW_PAIR(a1l, a2l, a12l);
-    DW_PAIR(a3l, a4l, a34l);
-    DW_PAIR(c0lh, c0ll, c0l);    // constant for light: hi, lo (the lo part seeds the lo chain)
-    DW_PAIR(c0dh, dc0l, c0d);    // constant for dark: hi, and (its lo part - light's lo part)
-    // ... or rounded once (float32-only mode): a_i = fl(a_ih + a_il), c0x = fl(c0xh + c0xl)
-    DW_PAIR(a1, a2, a12);
-    DW_PAIR(a3, a4, a34);
-    DW_PAIR(c0ls, c0ds, c0s);
-    // dt * (daisy kernel weights): dK = dt * density comes straight out of the weighted sum
-    DW_PAIR(dw0, dw1, dw01);
-    DW_PAIR(dw2, kbeta, dw2kb);  // kbeta = 1 / sqrt(g * To^2):  beta = 1 - (((T-To)/To) / kbeta)^2
-    DW_PAIR(p, ck, pck);         // bare fraction kb = p - (dKl + dKd) * ck,  ck = 0.001 / dt
-    // exact-mode tie test (per-mille; om = 1 - beta = cbeta*((T-To)/To)^2 >= 0):
-    //   |frac(gq)| > tie_lo - eA*|gq| - |dt*K|*(eK0 + eK1*om)   =>  re-evaluate in float64
-    DW_PAIR(eK1s, eK0s, eKs);    // -sign(dt) * eK1, eK0: dK * (eK0s + eK1s*om) = -|dK| * (eK0 + eK1*om) (density >= 0)
-    DW_PAIR(ngamma, tie_lo, gt); // -gamma; the tie threshold's constant part
-    // the same bracket written in beta = 1 - om (the hot kernels have beta, not om):
-    //   eK0s + eK1s*om = (eK0s + eK1s) + (-eK1s)*beta
-    DW_PAIR(neK1s, eK01s, eKb);
-    float eA;                    // used un-packed (|gq| source modifier); eK0 = |eK0s|, eK1 = |eK1s| (host, audit)
-    int hi_bits;                 // the hi parts are multiples of 2^-hi_bits (host bookkeeping)
-};
-static_assert(sizeof(PhysF32) == 32 * sizeof(float), "PhysF32 layout");
 
 // the members of PhysF32 that depend on the luminosity (the rest is shared by the two steps of a fused
-// launch when both coefficient sets are split at the same scale, see derive_f32_pair() in dw_api.hip)
-struct PhysLumF32 {
-    dw_f32x2 a12h, a12l, c0l, c0d, a12, c0s;
-};
+// launch when both coefficient sets are split at the same scale, see derive_f32_pair() in dw_plan.hpp)
 __host__ __device__ inline PhysLumF32 lum_part(const PhysF32& P) {
     return PhysLumF32{P.a12h, P.a12l, P.c0l, P.c0d, P.a12, P.c0s};
 }
@@ -297,7 +259,7 @@ constexpr bool kFastSplit = DW_FAST_SPLIT != 0;
 // and e_x = c0x + a1*(Sl8 - Sd8) + a3*(li - di): X = Sl8 - Sd8 and Y = li - di are exact integers (|X| <= 8000 <=
 // the 8*kmax the hi grid was sized for), the hi chain a1h*X + a3h*Y is as exact as the four-term one - it is the
 // same number - and the lo chain has two roundings instead of four: 6 packed instructions per cell pair instead of
-// 8 (the host selects the variant: dw_api.hip, `sym_albedo`).
+// 8 (the host selects the variant: plan_steps in dw_plan.hpp, `sym_albedo`).
 template <bool SPLIT, typename T, bool SYM = false>
 __device__ __forceinline__ GrowthT<T> growth_t(const PhysF32& P, T li, T di, T El, T Cl, T Ed, T Cd) {
 #pragma clang fp contract(off)

@@ -18,16 +18,10 @@
 #include "dw_common.hpp"
 #include "dw_step_generic.hpp"
 #include "dw_step_stream.hpp"
+#include "dw_types.hpp"    // FirstGeom
 
 namespace dw {
 
-struct FirstGeom {
-    int B, H, W;
-    int SR;                   // rows per wave-strip (<= 64: a lane's partial sums stay exact in float32)
-    int ncs, nrs;             // column (ceil(W / 256); packed: 1) and row strips per world (packed: per world GROUP)
-    int nstrips;              // B (packed: world groups) * nrs * ncs
-    int lpw, wpr;             // packed mode (W < 256): lanes per world row (W / 4), worlds per wave row (64 / lpw)
-};
 constexpr int kFirstWaveList = 512;   // flagged cells of a wave held in LDS; swept when more than half full (a row adds <= 256)
 
 // four adjacent cells of an un-quantised plane as per-mille float32

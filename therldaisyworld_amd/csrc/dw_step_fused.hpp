@@ -3,6 +3,7 @@
 #pragma once
 #include <type_traits>
 #include "dw_step_stream.hpp"
+#include "dw_types.hpp"    // FusedGeom, kMismatchCap, kFusedOvl / kFusedRot / kFusedRing
 
 namespace dw {
 
@@ -25,17 +26,6 @@ namespace dw {
 //                   compute step 1 but only lanes 1..62 (248 columns) produce output; no halo loads.
 // Vertically a strip of SR output rows reads SR+4 input rows and computes SR+2 step-1 rows.
 // ---------------------------------------------------------------------------------------------
-struct FusedGeom {
-    int B, H, W;
-    int SR;                   // output rows per wave-strip
-    int ncs, nrs;             // column / row strips per world
-    int nstrips, nwg, chunk;
-    int cols_per_strip;       // 256 (ROT) or 248 (OVL)
-    int qcap, mcap;           // queue / mismatch-list capacities in use (tests shrink them)
-    int lpw, wpr;             // packed mode (W < 256): lanes per world row (W/4), worlds per wave row (64 / lpw)
-    int sure_need;            // STATS: sure step-2 row groups after which a wave's count cannot matter any more:
-                              // 9 per agent (patched cells) + 9 per possible step-1 mismatch (deducted) + 1
-};
 
 // float64 step-1 value of grid cell (r, c) (any integers: wrapped onto the torus) from the input planes,
 // as a packed light | dark << 16 word
@@ -91,8 +81,6 @@ __device__ inline void exact2_cell(const TI* __restrict__ pL, const TI* __restri
     kd = (float)dw_round3_k(s2.nd);
 }
 
-constexpr int kMismatchCap = 64;            // float32 step-1 mismatches per wave-strip held in LDS
-
 // EXACT variant (the default mode's dw_step_n on wide grids).  Both steps run in float32 with the
 // per-cell tie test; near-tie cells of BOTH steps are queued in the wave's LDS queue with their 3x3
 // payload (step 1: the inputs; step 2: the float32 step-1 values).  After the strip the same wave
@@ -115,7 +103,6 @@ constexpr int kMismatchCap = 64;            // float32 step-1 mismatches per wav
 //   pstats[2*world + 1] number of this world's output row groups (4 cells of a lane) holding a step-2
 //                       value above `thr_hi` that cannot be an artefact of float32 or be undone by the few
 //                       cells patched afterwards - a sound lower bound, see agents_lookahead_patch.
-enum { kFusedOvl = 0, kFusedRot = 1, kFusedRing = 2 };
 // TRACE (trace_pair_fast / trace_pair_exact below, dw_step_n_trace): the wave also leaves the strip with the three
 // per-world reductions of BOTH steps - row `trace` (step 1) and row `trace + G.B` (step 2) of the caller's series.
 //   ownership   a step-1 cell counts in the strip whose OUTPUT cell it is: lanes with `writes`, step-1 rows 2 .. nr+1

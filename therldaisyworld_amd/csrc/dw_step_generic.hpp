@@ -3,6 +3,7 @@
 // Input: any plane format (dw_common.hpp); output: always the canonical binary16 planes.
 #pragma once
 #include "dw_common.hpp"
+#include "dw_types.hpp"    // FirstStepBound
 
 namespace dw {
 
@@ -16,16 +17,11 @@ namespace dw {
 // LDS and re-evaluated in float64 from the original inputs by densely packed lanes after the cell loop.
 // ---------------------------------------------------------------------------------------------
 // Error bound of the float32 map on NON-INTEGER inputs (no exact coefficient chain: every operation rounds).
-// Derived like the bound of the quantised case (dw_api.hip derive_f32) with these changes: the
+// Derived like the bound of the quantised case (dw_plan.hpp derive_f32) with these changes: the
 // inputs carry iota (u for a float64 state converted to float32, 0 for a float32 state), stencil sums 2u-3u, the
 // density 5u + iota, and the absolute error of e is (8u + iota) * M + u |c0| with the per-cell magnitude
 // M = |a1| Sl8 + |a2| Sd8 + |a3| li + |a4| di, which enters the growth curve as 2 de |e| / D^2 <= 2 de |w| / Dmin:
 //   eps = |K| (eK0 + eK1 om + cW de |w|) + eA |gq| + cS (|k + gq| + k) + slack
-struct FirstStepBound {
-    float a1, a2, a3, a4;         // |a_i| of the rounded coefficient set
-    float c_de, c_c0;             // de = c_de * M + c_c0
-    float eK0, eK1, cW, eA, cS, slack;
-};
 constexpr int kFirstListCap = 1024;   // flagged cells per workgroup held in LDS (overflow: evaluated in line)
 
 __host__ inline int generic_cells_per_thread(long long batch, long long cells_per_world) {

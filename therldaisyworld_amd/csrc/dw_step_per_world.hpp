@@ -3,7 +3,7 @@
 //
 // The luminosity enters the coefficient chain (PhysLumF32) and, through the admissible interval of e, the tie bound;
 // the float64 repair needs it in double.  So a step's constants are ONE ROW of a device table, [B] entries of
-//   PhysF32 (128 B: the world's whole float32 set, tie bound included - exactly what derive_f32 gives a one-world
+//   PhysF32 (128 B: the world's whole float32 set, tie bound included - exactly what derive_f32 (dw_plan.hpp) gives a one-world
 //            handle at that luminosity, so the same cells are flagged and the fix-up counts agree)
 //   PhysF64 (128 B: the float64 set of the repair path and of DW_PRECISION_F64)
 // and the kernels below are the shared-L kernels' bodies (stream_body, dw_step_generic_body.hpp) handed `row[world]`

@@ -2,6 +2,7 @@
 // (register window, DPP neighbours, per-wave LDS queue + in-wave float64 fix-up in exact mode).
 #pragma once
 #include "dw_common.hpp"
+#include "dw_types.hpp"    // StripGeom, kWaveQueueCap
 
 namespace dw {
 
@@ -38,18 +39,6 @@ namespace dw {
 #ifndef DW_STREAM_WAVES_EXACT
 #define DW_STREAM_WAVES_EXACT 3
 #endif
-
-struct StripGeom {
-    int B, H, W;
-    int SR;                   // rows per wave-strip
-    int ncs, nrs;             // column / row strips per world
-    int nstrips;              // B * nrs * ncs
-    int nwg;                  // ceil(nstrips / 4) workgroups of 4 waves
-    int chunk;                // ceil(nwg / 8): workgroups per XCD
-    int qcap;                 // near-tie LDS queue capacity in use (<= kWaveQueueCap; tests shrink it)
-    int lpw, wpr;             // packed mode (W < 256): lanes per world row (W/4), worlds per wave row (64 / lpw)
-    int force_rescan;         // tests: every exact strip takes the maximum's re-scan path (see `rescan_max` in stream_body)
-};
 
 struct Raw {                  // one row AS LOADED (binary16: 6 VGPRs; widened where it is consumed): own 4 columns
     dw_f16x4 l, d;            // of both planes
@@ -133,8 +122,6 @@ __device__ __forceinline__ void pack3(const Row4& L, const Row4& D, unsigned int
     w1 = pack_ld(L.x[I], D.x[I]);
     w2 = pack_ld(lc, dc);
 }
-
-constexpr int kWaveQueueCap = 256;          // near-tie entries per wave-strip held in LDS (48 B each)
 
 // Ordering of the exact mode's repair stores.  A repaired cell is first written by the strip loop (a 16- or
 // 8-byte non-temporal row store of some lane) and later patched by another lane of the SAME wave with a scalar

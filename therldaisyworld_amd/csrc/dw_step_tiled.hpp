@@ -3,6 +3,7 @@
 // HBM (8-byte groups of four cells), float32 tile in LDS.
 #pragma once
 #include "dw_common.hpp"
+#include "dw_types.hpp"    // kMaxFix, kNumQueues
 
 namespace dw {
 
@@ -23,8 +24,6 @@ namespace dw {
 // the 8 XCDs, so id b works on tile (b % 8) * chunk + b / 8: each XCD (and its private L2) gets a
 // contiguous run of tiles, and the halo rows shared by vertically adjacent tiles hit in L2.
 // ---------------------------------------------------------------------------------------------
-constexpr int kMaxFix = 1024;     // per-workgroup LDS queue of near-tie cells
-constexpr int kNumQueues = 256;   // global queues (one counter cache line each)
 
 // Global queues of near-tie cells (exact mode).  A workgroup reserves a contiguous run in queue
 // (blockIdx % kNumQueues) with ONE atomic and copies its LDS queue there, each entry carrying the
