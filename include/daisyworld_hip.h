@@ -264,6 +264,41 @@ int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_w
 int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule /* [nsteps][B] */,
                               dw_world_stats* trace /* [nsteps][B], may be NULL */);
 
+/* Per-world statistics of the local temperature field - the reference's `self.temp` (ref daisy_world_rl.py:410,415; NOT
+ * temp_light / temp_dark), in kelvin, over the H*W cells of each world: the curves its notebooks append after every
+ * step (`env.temp.mean()`, notebooks/daisy_world_existential_risk_and_agency.ipynb cell 2 run_q2_sims; `temp.mean()` and
+ * `temp.std()`, daisy/notebook_helpers.py:50-52).  `std` is the population standard deviation (np.std, ddof = 0).  Always
+ * evaluated in float64, whatever the handle's precision, from the same per-cell values as the `temps` cache of
+ * dw_download_caches: min and max are two of those doubles.  The reduction is deterministic (fixed order, no atomics;
+ * world b reduces the same whatever the batch) and takes the moments about the temperature of the world's cell (0, 0):
+ * a uniform world has std == 0.0 and min == max == mean exactly. */
+typedef struct dw_temp_stats { double mean, std, min, max; } dw_temp_stats;   /* 32 bytes, kelvin */
+
+/* The statistics of the field dw_download_caches(h, L, temps, ...) returns as temps[:,0], without moving it: the same
+ * source state (after a step the retained previous state, before any step the uploaded one) and the same rule for the
+ * luminosity (the handle's last shared luminosity once a shared-L step has run; the caller's L otherwise - ONE value for
+ * all worlds - including after a per-world run).  After dw_step(h, NULL, 0, 0, L) it is what the reference's env.temp
+ * holds after that step (ref :415).  Synchronises.  DW_EINVAL: null argument; DW_ESTATE: no state; DW_ENOMEM: the
+ * reduction's buffers could not be allocated (nothing is kept). */
+int dw_reduce_temperature(dw_handle* h, double L, dw_temp_stats* per_world /* [B] */);
+
+/* The temperature series of an agent-free run (ref run_q2_sims, daisy/notebook_helpers.py:50-52): nsteps single steps
+ * without agents, and temps[t*B + b] = the statistics of the temperature field step t computes - world b's state BEFORE
+ * step t at that step's luminosity, which is what env.temp holds after the t-th env.step() (ref :415,437).
+ * per_world == 0: L_schedule[nsteps], one luminosity per step as dw_step_n_trace; per_world != 0:
+ * L_schedule[nsteps][B] as dw_step_n_trace_per_world, with its validation and error codes, and the handle is "per-world"
+ * afterwards as after that call.  `trace`, when given, is filled exactly as those calls fill it.  Planes, retained
+ * previous state, dw_reduce and dw_last_fixup_count afterwards are those of dw_step_n_trace / dw_step_n_trace_per_world
+ * with the same schedule, bit for bit; the first step from an un-quantised state reads it in its own format.
+ * The temperatures are reduced by a kernel of their own that reads each step's input planes in front of the step, so
+ * the steps are taken one launch each, never in fused pairs: that is the price of the series.
+ * Records stay on the device and are downloaded once per 32 MiB.  nsteps == 0 is a no-op.  Synchronises.
+ * DW_EINVAL: null handle, schedule or temps (and, per world, a luminosity that is not finite or is negative: the state
+ * is untouched); DW_ESTATE: no state; DW_ENOMEM: a buffer could not be allocated (nothing is kept). */
+int dw_step_n_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_schedule, int per_world,
+                                dw_world_stats* trace /* [nsteps][B], may be NULL */,
+                                dw_temp_stats* temps  /* [nsteps][B] */);
+
 /* Measurement aid (bench.py): duration of the run of fused step-pair launches issued by the LAST
  * dw_step_n call, from HIP events recorded on the handle's stream immediately before the first and after the
  * last of them (synchronises).  fused_launches = 0 (and fused_ms = 0) if that call issued none.

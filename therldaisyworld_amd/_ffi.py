@@ -48,6 +48,12 @@ class DwWorldStats(C.Structure):
 
 STATS_DTYPE = np.dtype([("max_k", "<u4"), ("reserved", "<u4"), ("sum_light_k", "<u8"), ("sum_dark_k", "<u8")])
 
+class DwTempStats(C.Structure):
+    _fields_ = [("mean", C.c_double), ("std", C.c_double), ("min", C.c_double), ("max", C.c_double)]
+
+
+TEMP_STATS_DTYPE = np.dtype([("mean", "<f8"), ("std", "<f8"), ("min", "<f8"), ("max", "<f8")])
+
 _vp, _i32, _i64, _u32, _u64, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 _pd, _pi, _pf, _pu8 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
 
@@ -79,6 +85,8 @@ SIGNATURES = {
     "dw_step_n": (C.c_int, [_vp, _i32, _pd, _dbl, _dbl, _dbl, C.c_int]),
     "dw_step_n_trace": (C.c_int, [_vp, _i32, _pd, C.POINTER(DwWorldStats)]),
     "dw_step_n_trace_per_world": (C.c_int, [_vp, _i32, _pd, C.POINTER(DwWorldStats)]),
+    "dw_reduce_temperature": (C.c_int, [_vp, _dbl, C.POINTER(DwTempStats)]),
+    "dw_step_n_trace_temperature": (C.c_int, [_vp, _i32, _pd, C.c_int, C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
     "dw_last_step_n_timing": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(_i32), C.POINTER(_i32)]),
     "dw_update_agents": (C.c_int, [_vp, _pi, _i32, _i32]),
     "dw_forward_f64": (C.c_int, [_vp, _pd, _pd, _dbl, _pd, _pd, _pd, _pd, _pd]),

@@ -132,6 +132,10 @@ struct dw_handle {
                                       // of that call were recorded (an error return in between leaves 0)
     DevBuf<StatsDev> side_stats;      // reductions of dw_forward_f64's side computation (not the handle's)
     DevBuf<StatsDev> trace_d;         // dw_step_n_trace: [rows][B] records of the chunk of steps in flight (grown on demand)
+    // dw_reduce_temperature / dw_step_n_trace_temperature: [rows][B] temperature records, and the [B][chunks] partials of
+    // the reduction in flight (one group: allocated all or nothing)
+    DevBuf<TempStatsDev> temp_d;
+    DevBuf<TempPartial> temp_part;
     // dw_step_n_trace_per_world: the constants of a chunk of steps, one entry per step and world (PwLayout), and their
     // page-locked host image
     DevBuf<unsigned char> pw_tab;
@@ -547,6 +551,35 @@ static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* 
     }
     HIPCHK(hipGetLastError());
     step_done(h, 0.0, true, true);
+    return DW_OK;
+}
+
+// ---- per-world temperature statistics (dw_reduce_temperature, dw_step_n_trace_temperature) ---------------------------
+static int temp_chunks(const dw_handle* h) {
+    return (int)(((long long)h->prm.height * h->prm.width + kTempChunk - 1) / kTempChunk);
+}
+static size_t temp_part_bytes(const dw_handle* h) { return sizeof(TempPartial) * (size_t)h->prm.batch * temp_chunks(h); }
+
+// The statistics of the temperature field a step at luminosity L computes from the CURRENT state (`current`: the trace
+// loop, in front of the step) or of the field the caches hold (the state with_derived_from names), into out[B] on the
+// device.  row64 != null: world b at the constants row64[b] (a row of the per-world table) instead of L.
+static int launch_temp_moments(dw_handle* h, bool current, double L, const PhysF64* row64, TempStatsDev* out) {
+    const dw_params& p = h->prm;
+    const int chunks = temp_chunks(h);
+    const PhysF64 P = row64 ? PhysF64{} : make_f64(p, L);
+    TempPartial* part = h->temp_part.get();
+    auto reduce = [&](auto* iL, auto* iD) {
+        with_bool(row64 != nullptr, [&](auto TABLE) {
+            hipLaunchKernelGGL((temp_moments_pw<elem_t<decltype(iL)>, TABLE>), dim3((unsigned)chunks, (unsigned)p.batch), dim3(256),
+                               0, h->stream, iL, iD, p.height, p.width, P, row64, part);
+        });
+    };
+    if (current) with_planes(h, h->unq == OWN_CUR, h->cur, reduce);
+    else with_derived_from(h, [&](auto* iL, auto* iD, auto) { reduce(iL, iD); });
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(temp_moments_finish_pw, dim3((unsigned)((p.batch + 63) / 64)), dim3(64), 0, h->stream, part, p.batch, chunks,
+                       (double)p.height * (double)p.width, out);
+    HIPCHK(hipGetLastError());
     return DW_OK;
 }
 
@@ -1040,6 +1073,20 @@ int dw_download_caches(dw_handle* h, double L, double* temps, double* betas, dou
     return DW_OK;
 }
 
+int dw_reduce_temperature(dw_handle* h, double L, dw_temp_stats* per_world) {
+    NEED(h && per_world, DW_EINVAL, "null argument");
+    NEED(h->have_state, DW_ESTATE, "no state");
+    static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev), "temperature record layout");
+    HIPCHK(hipSetDevice(h->prm.device));
+    const size_t bytes = sizeof(TempStatsDev) * (size_t)h->prm.batch;
+    if (int rc = alloc_group(h, "the temperature reduction", {{h->temp_part, temp_part_bytes(h)}, {h->temp_d, bytes}})) return rc;
+    // (the luminosity: run_materialise's rule - the caches' own)
+    if (int rc = launch_temp_moments(h, false, h->stepped && !h->L_per_world ? h->L_last : L, nullptr, h->temp_d.get())) return rc;
+    HIPCHK(hipMemcpyAsync(per_world, h->temp_d.get(), bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return DW_OK;
+}
+
 // ---- the hot path -----------------------------------------------------------------------------
 
 int dw_update_agents(dw_handle* h, const int32_t* action, int32_t action_b, int32_t action_n) {
@@ -1203,7 +1250,9 @@ int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_w
     return DW_OK;
 }
 
-int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace) {
+// dw_step_n_trace_per_world, and the per-world form of dw_step_n_trace_temperature (`temps` != null: the temperature
+// records of every step, reduced from the step's input planes at the step's row of the table)
+static int trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace, dw_temp_stats* temps) {
     NEED(h && L_schedule, DW_EINVAL, "null argument");
     NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
     if (nsteps == 0) return DW_OK;
@@ -1215,8 +1264,10 @@ int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_sche
         NEED(std::isfinite(L_schedule[i]) && L_schedule[i] >= 0.0, DW_EINVAL,
              "L_schedule[step %zu][world %zu] = %g: a luminosity is finite and not negative", i / B, i % B, L_schedule[i]);
     HIPCHK(hipSetDevice(p.device));
-    // rows of the series on the device at a time: as dw_step_n_trace (no pairs here: any number of rows will do)
-    size_t rows = h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / row_bytes;
+    // rows of the series on the device at a time: as dw_step_n_trace (no pairs here: any number of rows will do; with
+    // temperature records, 32 MiB of those)
+    const size_t trow_bytes = sizeof(TempStatsDev) * B;
+    size_t rows = h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / (temps ? trow_bytes : row_bytes);
     rows = rows < 1 ? 1 : (rows > (size_t)nsteps ? (size_t)nsteps : rows);
     // rows of the table: 8 MiB of constants (256 B per step and world), under the test hook as many as trace rows
     size_t trows = ((size_t)8 << 20) / ((sizeof(PhysF32) + sizeof(PhysF64)) * B);
@@ -1224,7 +1275,11 @@ int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_sche
     trows = trows < 1 ? 1 : (trows > (size_t)nsteps ? (size_t)nsteps : trows);
     const PwLayout lay(B, trows);
     // the table and (when a series is wanted) the trace buffer: all or nothing; then the table's page-locked image
-    if (trace) {
+    if (temps) {
+        if (int rc = alloc_group(h, "the per-world constants, the trace buffer and the temperature reduction",
+                                 {{h->pw_tab, lay.bytes}, {h->trace_d, trace ? rows * row_bytes : 0},
+                                  {h->temp_part, temp_part_bytes(h)}, {h->temp_d, rows * trow_bytes}})) return rc;
+    } else if (trace) {
         if (int rc = alloc_group(h, "the per-world constants and the trace buffer",
                                  {{h->pw_tab, lay.bytes}, {h->trace_d, rows * row_bytes}})) return rc;
     } else if (int rc = alloc_group(h, "the per-world constants", {{h->pw_tab, lay.bytes}})) {
@@ -1287,12 +1342,57 @@ int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_sche
             image_in_flight = true;
         }
         const size_t tr = row_of[t];
+        if (temps)
+            if (int rc = launch_temp_moments(h, true, 0.0, lay.p64(tab, tr), h->temp_d.get() + sr * B)) return rc;
         if (int rc = launch_forward_pw(h, lay.p32(tab, tr), lay.p64(tab, tr), lay.fb(tab))) return rc;
+        if (temps && (sr + 1 == rows || t + 1 == nsteps))
+            HIPCHK(hipMemcpyAsync(temps + ((size_t)t - sr) * B, h->temp_d.get(), (sr + 1) * trow_bytes, hipMemcpyDeviceToHost,
+                                  h->stream));
         if (trace) {
             HIPCHK(hipMemcpyAsync(h->trace_d.get() + sr * B, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
             if (sr + 1 == rows || t + 1 == nsteps)
                 HIPCHK(hipMemcpyAsync(trace + ((size_t)t - sr) * B, h->trace_d.get(), (sr + 1) * row_bytes, hipMemcpyDeviceToHost,
                                       h->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    sync.disarm();
+    return DW_OK;
+}
+
+int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace) {
+    return trace_per_world(h, nsteps, L_schedule, trace, nullptr);
+}
+
+int dw_step_n_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_schedule, int per_world, dw_world_stats* trace,
+                                dw_temp_stats* temps) {
+    NEED(h && L_schedule && temps, DW_EINVAL, "null argument");
+    static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev), "temperature record layout");
+    if (per_world) return trace_per_world(h, nsteps, L_schedule, trace, temps);
+    NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
+    if (nsteps == 0) return DW_OK;
+    NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
+    HIPCHK(hipSetDevice(h->prm.device));
+    const size_t B = (size_t)h->prm.batch, row_bytes = sizeof(StatsDev) * B, trow_bytes = sizeof(TempStatsDev) * B;
+    // rows of both series held on the device at a time: the whole run up to 32 MiB of temperature records, longer runs
+    // in chunks of that size (single steps: any number of rows will do); DW_TEST_TRACE_ROWS: that many rows instead
+    size_t rows = h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / trow_bytes;
+    rows = rows < 1 ? 1 : (rows > (size_t)nsteps ? (size_t)nsteps : rows);
+    if (int rc = alloc_group(h, "the trace buffer and the temperature reduction",
+                             {{h->trace_d, trace ? rows * row_bytes : 0}, {h->temp_part, temp_part_bytes(h)},
+                              {h->temp_d, rows * trow_bytes}})) return rc;
+    SyncOnExit sync(h->stream);                                 // the downloads below fill the caller's arrays
+    h->fused_launches = 0;
+    for (int t = 0; t < nsteps; ++t) {
+        const size_t sr = (size_t)t % rows;
+        // the field this step computes: from its input planes, in front of it
+        if (int rc = launch_temp_moments(h, true, L_schedule[t], nullptr, h->temp_d.get() + sr * B)) return rc;
+        if (int rc = launch_forward(h, L_schedule[t])) return rc;
+        if (trace) HIPCHK(hipMemcpyAsync(h->trace_d.get() + sr * B, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
+        if (sr + 1 == rows || t + 1 == nsteps) {
+            const size_t r0 = ((size_t)t - sr) * B;
+            HIPCHK(hipMemcpyAsync(temps + r0, h->temp_d.get(), (sr + 1) * trow_bytes, hipMemcpyDeviceToHost, h->stream));
+            if (trace) HIPCHK(hipMemcpyAsync(trace + r0, h->trace_d.get(), (sr + 1) * row_bytes, hipMemcpyDeviceToHost, h->stream));
         }
     }
     HIPCHK(hipStreamSynchronize(h->stream));

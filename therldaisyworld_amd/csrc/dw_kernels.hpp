@@ -16,6 +16,7 @@
 //                         (agents/greedy.py:14-36), policy_mlp (agents/mlp.py:97-116), reward/done, lifespans
 //   dw_agents_fused.hpp   agents_lookahead_patch: the agents' step between the two steps of a fused launch
 //   dw_state_io.hpp       materialise (ref self.grid :445-459 / :304-323), init_random (Philox), conversions
+//   dw_temp_moments.hpp   temp_moments_pw   per-world mean / std / min / max of the local temperature (ref :410,415)
 //
 // Wavefront = 64 lanes, 256-thread workgroups (4 waves), no MFMA.  Planes are binary16 per-mille integers: 8
 // algorithmic bytes per cell-update (2 planes read + 2 written).  Measured bounds (DESIGN.md sections 3 and 6): the
@@ -34,3 +35,4 @@
 #include "dw_agents.hpp"
 #include "dw_state_io.hpp"
 #include "dw_agents_fused.hpp"
+#include "dw_temp_moments.hpp"

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _ffi
-from ._ffi import DwParams, DwWorldStats
+from ._ffi import DwParams, DwTempStats, DwWorldStats
 
 VON_NEUMANN_MASK = 0x0BA
 MOORE_MASK = 0x1FF
@@ -191,6 +191,24 @@ class Engine:
             self._h, int(Ls.shape[0]), _ffi.ptr_d(Ls), out.ctypes.data_as(C.POINTER(DwWorldStats)) if trace else None))
         return out
 
+    def step_n_trace_temperature(self, L_schedule, trace=True):
+        """`len(L_schedule)` agent-free single steps that also record the per-world statistics of the local temperature
+        field each step computes (`dw_step_n_trace_temperature`; the reference's `env.temp` after that step).
+        `L_schedule` is 1-D (one luminosity per step, as `step_n_trace`) or (n, B) (one per step and world, as
+        `step_n_trace_per_world`, and the engine is "per-world" afterwards).  Returns `(stats, temps)`: the (n, B) records
+        of `step_n_trace` (None with `trace=False`) and (n, B) records of dtype `_ffi.TEMP_STATS_DTYPE` (mean, std, min,
+        max in kelvin; std with ddof = 0).  The state afterwards is that of the cover-only trace calls, bit for bit."""
+        Ls = np.ascontiguousarray(L_schedule, dtype=np.float64)
+        if Ls.ndim == 2 and Ls.shape[1] != self.B or Ls.ndim not in (1, 2):
+            raise ValueError(f"luminosities need shape (n,) or (n, {self.B}), got {Ls.shape}")
+        n = int(Ls.shape[0])
+        out = np.zeros((n, self.B), dtype=_ffi.STATS_DTYPE) if trace else None
+        temps = np.zeros((n, self.B), dtype=_ffi.TEMP_STATS_DTYPE)
+        self._check(self._lib.dw_step_n_trace_temperature(
+            self._h, n, _ffi.ptr_d(Ls), int(Ls.ndim == 2), out.ctypes.data_as(C.POINTER(DwWorldStats)) if trace else None,
+            temps.ctypes.data_as(C.POINTER(DwTempStats))))
+        return out, temps
+
     def last_step_n_timing(self):
         """(ms spent in the fused step-pair launches of the last step_n call, their number, plane element bytes)."""
         ms, n, eb = C.c_float(0), C.c_int32(0), C.c_int32(0)
@@ -261,6 +279,14 @@ class Engine:
     def reduce(self):
         out = np.zeros(self.B, dtype=_ffi.STATS_DTYPE)
         self._check(self._lib.dw_reduce(self._h, out.ctypes.data_as(C.POINTER(DwWorldStats))))
+        return out
+
+    def reduce_temperature(self, L):
+        """(B,) records of dtype `_ffi.TEMP_STATS_DTYPE`: mean, population std, min and max of the local temperature field
+        `download_caches(L)` would return as `temps[:, 0]` - reduced on the device (`dw_reduce_temperature`), nothing but
+        the 32 bytes per world comes down.  `L` is used as `download_caches` uses it."""
+        out = np.zeros(self.B, dtype=_ffi.TEMP_STATS_DTYPE)
+        self._check(self._lib.dw_reduce_temperature(self._h, float(L), out.ctypes.data_as(C.POINTER(DwTempStats))))
         return out
 
     def policy_greedy(self, argmin=False):

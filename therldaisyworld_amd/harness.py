@@ -226,33 +226,47 @@ def _advance_host_scalars(env, executed):
 RAMP_ALIVE_THRESHOLD = 0.005      # the notebook's test for a living biosphere: max cover > 0.005
 
 
-def _ramp_series(env, nsteps, run_trace):
+def dead_temperature(env, L):
+    """The temperature of a lifeless planet at luminosity `L` (any shape), ((S L (1 - albedo_bare)) / sigma)^(1/4) in float64
+    on the host - the reference's `dead_temp` (ref daisy_world_rl.py:407-408), the curve its figures hold the regulated
+    mean temperature against."""
+    L = np.asarray(L, dtype=np.float64)
+    return ((env.S * L * (1 - env.albedo_bare)) / env.sigma) ** (1 / 4)
+
+
+def _ramp_series(env, nsteps, run_trace, temperature=False):
     """The host side of `simulate_ramp`: the schedule of the next `nsteps` steps, ONE call `run_trace(L_schedule)` ->
     (n, B) records of dtype `_ffi.STATS_DTYPE` (the engine's `step_n_trace`), then the environment's scalars advanced as
-    `nsteps` calls of `env.step()` would have."""
+    `nsteps` calls of `env.step()` would have.  `temperature`: `run_trace` returns (records, temperature records) - the
+    engine's `step_n_trace_temperature`."""
     if env.n_agents:
         raise ValueError("simulate_ramp is for agent-free ensembles (n_agents == 0): with agents the reference's step(None) "
                          "still grazes with action 0 - use simulate_lifespan")
     n = int(nsteps)
     L = np.asarray(_luminosity_schedule(env, n), dtype=np.float64)
-    stats = run_trace(L)
+    stats, temps = run_trace(L) if temperature else (run_trace(L), None)
     _advance_host_scalars(env, n)
-    return _series_dict(env, L, stats)
+    return _series_dict(env, L, stats, temps)
 
 
-def _series_dict(env, L, stats):
-    """What `simulate_ramp` and `simulate_luminosity_sweep` return, from the (n, B) records of a run."""
+def _series_dict(env, L, stats, temps=None):
+    """What `simulate_ramp` and `simulate_luminosity_sweep` return, from the (n, B) records of a run - with the (n, B)
+    temperature records of a `temperature=True` run, also its temperature curves."""
     cells = float(env.dim) * float(env.dim)
     max_cover = stats["max_k"] / 1000.0
-    return {"L": L,
-            "mean_light": stats["sum_light_k"] / 1000.0 / cells,
-            "mean_dark": stats["sum_dark_k"] / 1000.0 / cells,
-            "max_cover": max_cover,
-            "alive": max_cover > RAMP_ALIVE_THRESHOLD,
-            "stats": stats}
+    out = {"L": L,
+           "mean_light": stats["sum_light_k"] / 1000.0 / cells,
+           "mean_dark": stats["sum_dark_k"] / 1000.0 / cells,
+           "max_cover": max_cover,
+           "alive": max_cover > RAMP_ALIVE_THRESHOLD,
+           "stats": stats}
+    if temps is not None:
+        out.update(mean_temp=temps["mean"], std_temp=temps["std"], min_temp=temps["min"], max_temp=temps["max"],
+                   dead_temp=dead_temperature(env, L))
+    return out
 
 
-def simulate_ramp(env, nsteps, obs=None):
+def simulate_ramp(env, nsteps, obs=None, temperature=False):
     """The time series of an agent-free ensemble over the next `nsteps` steps of its luminosity ramp - the curves of
     the reference's notebooks (daisy/notebook_helpers.py:50-54 appends `env.grid[:, 1].mean()` per step) without a host
     round trip per step: the per-step, per-world reductions are recorded on the device (`dw_step_n_trace`) and come
@@ -261,7 +275,13 @@ def simulate_ramp(env, nsteps, obs=None):
     Returns a dict: `L` (n,) the luminosity each step used; `mean_light`, `mean_dark` (n, B) float64; `max_cover`
     (n, B); `alive` (n, B) bool, the notebook's `max > 0.005`; `stats` the raw (n, B) records (exact per-mille
     integers).  Afterwards `env.grid`, `env.step()`, `env.L`, `env.step_count` ... continue as if the steps had been
-    taken one by one."""
+    taken one by one.
+
+    `temperature=True`: the run also records the per-world statistics of the local temperature field every step
+    computes - the reference's `env.temp.mean()` / `.std()` after each step (notebook_helpers.py:50-52, `run_q2_sims`) -
+    through `dw_step_n_trace_temperature` (single steps plus one reduction each: slower than the cover-only run, same
+    state afterwards).  The dict gains `mean_temp`, `std_temp`, `min_temp`, `max_temp` (n, B) in kelvin and `dead_temp`,
+    the lifeless temperature at each step's luminosity (ref :407-408), with the shape of `L`."""
     if env.n_agents:
         raise ValueError("simulate_ramp is for agent-free ensembles (n_agents == 0): with agents the reference's step(None) "
                          "still grazes with action 0 - use simulate_lifespan")
@@ -269,10 +289,12 @@ def simulate_ramp(env, nsteps, obs=None):
         env.reset()
     eng = env._ensure_engine()
     env._sync_to_device()
+    if temperature:
+        return _ramp_series(env, nsteps, eng.step_n_trace_temperature, temperature=True)
     return _ramp_series(env, nsteps, eng.step_n_trace)
 
 
-def simulate_luminosity_sweep(env, L_values, nsteps, obs=None):
+def simulate_luminosity_sweep(env, L_values, nsteps, obs=None, temperature=False):
     """The response of an agent-free ensemble to forcing in ONE run: world b is held at luminosity `L_values[b]` for
     `nsteps` steps (`len(L_values) == env.batch_size`) - the bifurcation diagram the reference's notebooks assemble from
     one run per luminosity (`run_q2_sims`, the `min_L` / `max_L` edits).  `L_values` may also be (nsteps, B): a schedule
@@ -281,7 +303,10 @@ def simulate_luminosity_sweep(env, L_values, nsteps, obs=None):
 
     Returns the dict of `simulate_ramp` with `L` of shape (n, B).  The reference's `env.L` is ONE number and has no
     meaning after such a run: `env.step()` and `env.grid` raise until `env.reset()` (the covers are available from
-    `env._engine.download_planes()`, the last records from the returned series)."""
+    `env._engine.download_planes()`, the last records from the returned series).
+
+    `temperature=True`: as in `simulate_ramp` - the temperature curves of every world at its own luminosity
+    (`mean_temp`, `std_temp`, `min_temp`, `max_temp`, `dead_temp`, each (n, B))."""
     if env.n_agents:
         raise ValueError("simulate_luminosity_sweep is for agent-free ensembles (n_agents == 0)")
     n = int(nsteps)
@@ -295,10 +320,10 @@ def simulate_luminosity_sweep(env, L_values, nsteps, obs=None):
         env.reset()
     eng = env._ensure_engine()
     env._sync_to_device()
-    stats = eng.step_n_trace_per_world(L)
+    stats, temps = eng.step_n_trace_temperature(L) if temperature else (eng.step_n_trace_per_world(L), None)
     env._invalidate()
     env._per_world_L = True
-    return _series_dict(env, L, stats)
+    return _series_dict(env, L, stats, temps)
 
 
 def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_chunk):
