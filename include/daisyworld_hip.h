@@ -299,6 +299,45 @@ int dw_step_n_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_sc
                                 dw_world_stats* trace /* [nsteps][B], may be NULL */,
                                 dw_temp_stats* temps  /* [nsteps][B] */);
 
+/* Per-world physics constants: the members of dw_params a world of an ensemble call may have of its own (ref
+ * daisy_world_rl.py:32-52, :65-69) - a sweep over q2, gamma, the albedos, temp_optimal or dt as ONE traced run instead of
+ * one handle and one run per value (the reference's run_q2_sims runs its ramp three times with env.q2 = 0, q/64, q/8). */
+typedef struct dw_world_params {
+    double p, g, S, sigma, gamma, q, q2, dt, albedo_bare, albedo_light, albedo_dark, temp_optimal;
+} dw_world_params;                                   /* 96 bytes */
+
+/* The handle's own set (what every world of it steps with in every other call).  DW_EINVAL: null argument. */
+int dw_world_params_of(const dw_handle* h, dw_world_params* out);
+
+/* nsteps agent-free steps, world b with the constants worlds[b] (fixed for the whole call) and step t of it at the
+ * luminosity L_schedule[t*B + b].  Afterwards the planes of world b, the retained previous state and dw_reduce are what
+ * a ONE-world handle leaves that holds world b, carries those constants (dw_set_params) and takes nsteps calls of
+ * dw_step(h1, NULL, 0, 0, L) - bit for bit, in all three precisions, from a quantised or an un-quantised state.
+ * `trace` (may be NULL) is filled exactly as dw_step_n_trace_per_world fills it; `temps` (may be NULL) exactly as
+ * dw_step_n_trace_temperature(per_world = 1) fills it, each world's field at its own constants.  dw_last_fixup_count is
+ * the sum over the worlds of what that one-world handle reports after dw_step_n_trace (dw_step_n_trace_temperature when
+ * `temps` is given) with the world's column.
+ * Without `temps`, DW_PRECISION_FAST on un-packed wave-strip shapes other than W == 1024 takes the steps from a
+ * quantised state in fused PAIRS (trace_pair_fast_pw: each strip reads its world's two coefficient sets from a device
+ * table by scalar loads), with the pairing rule of dw_step_n_trace; a step without a partner, every step with `temps`,
+ * the other precisions and every other shape take the single-step kernels of dw_step_n_trace_per_world
+ * (dw_kernel_info: "per-world constants: step pairs" / "wave strips" / "generic").  The albedo-symmetric form of the exact kernels is used only when EVERY world's albedos are exactly
+ * symmetric about the bare ground's; results do not depend on it.
+ * Checked before anything is launched or allocated (the state is untouched) - DW_EINVAL: null h, worlds or L_schedule;
+ * a luminosity that is not finite or is negative; a world whose set dw_set_params would refuse on this handle (g < 0
+ * in the float32 precisions; the message names the world and the member).  DW_ESTATE: no state.  DW_ENOMEM: a buffer
+ * could not be allocated (nothing is kept: a later call allocates again).  nsteps == 0 is a no-op.  Synchronises.
+ * The handle's own dw_params is unchanged, and the handle is "per-world" afterwards as after
+ * dw_step_n_trace_per_world: dw_download_grid, dw_get_obs and the observations of dw_run_episode* return DW_ESTATE
+ * until a shared-L step, an upload or dw_init_random - and after THIS call so do dw_download_caches and
+ * dw_reduce_temperature, which have no single constant set to evaluate the retained state with.  The snapshots save and
+ * restore that mark. */
+int dw_step_n_trace_ensemble(dw_handle* h, int32_t nsteps,
+                             const dw_world_params* worlds /* [B] */,
+                             const double* L_schedule      /* [nsteps][B] */,
+                             dw_world_stats* trace         /* [nsteps][B], may be NULL */,
+                             dw_temp_stats* temps          /* [nsteps][B], may be NULL */);
+
 /* Measurement aid (bench.py): duration of the run of fused step-pair launches issued by the LAST
  * dw_step_n call, from HIP events recorded on the handle's stream immediately before the first and after the
  * last of them (synchronises).  fused_launches = 0 (and fused_ms = 0) if that call issued none.

@@ -54,6 +54,16 @@ class DwTempStats(C.Structure):
 
 TEMP_STATS_DTYPE = np.dtype([("mean", "<f8"), ("std", "<f8"), ("min", "<f8"), ("max", "<f8")])
 
+WORLD_PARAM_NAMES = ("p", "g", "S", "sigma", "gamma", "q", "q2", "dt", "albedo_bare", "albedo_light", "albedo_dark",
+                     "temp_optimal")
+
+
+class DwWorldParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in WORLD_PARAM_NAMES]
+
+
+WORLD_PARAMS_DTYPE = np.dtype([(n, "<f8") for n in WORLD_PARAM_NAMES])
+
 _vp, _i32, _i64, _u32, _u64, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
 _pd, _pi, _pf, _pu8 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8)
 
@@ -87,6 +97,9 @@ SIGNATURES = {
     "dw_step_n_trace_per_world": (C.c_int, [_vp, _i32, _pd, C.POINTER(DwWorldStats)]),
     "dw_reduce_temperature": (C.c_int, [_vp, _dbl, C.POINTER(DwTempStats)]),
     "dw_step_n_trace_temperature": (C.c_int, [_vp, _i32, _pd, C.c_int, C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
+    "dw_world_params_of": (C.c_int, [_vp, C.POINTER(DwWorldParams)]),
+    "dw_step_n_trace_ensemble": (C.c_int, [_vp, _i32, C.POINTER(DwWorldParams), _pd, C.POINTER(DwWorldStats),
+                                           C.POINTER(DwTempStats)]),
     "dw_last_step_n_timing": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(_i32), C.POINTER(_i32)]),
     "dw_update_agents": (C.c_int, [_vp, _pi, _i32, _i32]),
     "dw_forward_f64": (C.c_int, [_vp, _pd, _pd, _dbl, _pd, _pd, _pd, _pd, _pd]),

@@ -98,6 +98,7 @@ struct dw_handle {
     bool stepped = false;             // prev/cur form a forward() pair
     double L_last = 0.0;              // luminosity of the last forward()
     bool L_per_world = false;         // ... which took one per world (dw_step_n_trace_per_world): L_last means nothing
+    bool P_per_world = false;         // ... and a set of constants per world too (dw_step_n_trace_ensemble): read with L_per_world
     DevBuf<int> idx;                  // [B][N][2]
     DevBuf<double> st;                // [B][N]
     DevBuf<int> action;               // [B][N]
@@ -148,7 +149,7 @@ struct dw_handle {
         DevBuf<plane_t> PL, PD;       // the retained previous state (observations, caches) when there is one
         bool stepped = false;
         double L_last = 0.0;
-        bool L_per_world = false;
+        bool L_per_world = false, P_per_world = false;
         UnqOwner unq = OWN_NONE;
         DevBuf<int> idx;
         DevBuf<double> st;
@@ -168,6 +169,13 @@ static inline bool lacks_shared_L(const dw_handle* h) { return h->stepped && h->
     NEED(!lacks_shared_L(h), DW_ESTATE,                                                                                 \
          "%s derives its temperature channels from the last step's luminosity, and the last step "                      \
          "(dw_step_n_trace_per_world) took a per-world luminosity: take a shared-L step or upload a state first", what)
+// ... and after dw_step_n_trace_ensemble no single set of constants either: what evaluates the retained state with the
+// caller's luminosity and the handle's constants (the caches, their temperature statistics) has nothing to evaluate with
+static inline bool lacks_shared_constants(const dw_handle* h) { return lacks_shared_L(h) && h->P_per_world; }
+#define NEED_SHARED_CONSTANTS(h, what)                                                                                  \
+    NEED(!lacks_shared_constants(h), DW_ESTATE,                                                                         \
+         "%s evaluates the last step's input state with one set of constants, and the last step "                       \
+         "(dw_step_n_trace_ensemble) took per-world constants: take a shared-L step or upload a state first", what)
 
 // ------------------------------------------------------------------------------------------------
 // runtime values -> template arguments.  Each helper instantiates `f` for every value it lists, so it is used only
@@ -459,13 +467,14 @@ static int launch_step(dw_handle* h, const StepOut& o) {
 }
 
 // A step wrote the other buffer: it holds the current state now, and the reductions swap with it.
-static void step_done(dw_handle* h, double L, bool stepped, bool per_world = false) {
+static void step_done(dw_handle* h, double L, bool stepped, bool per_world = false, bool per_world_constants = false) {
     h->cur = 1 - h->cur;
     h->sp = 1 - h->sp;
     h->unq = h->unq == OWN_CUR ? OWN_PREV : OWN_NONE;
     h->stepped = stepped;
     h->L_last = L;
     h->L_per_world = per_world;
+    h->P_per_world = per_world && per_world_constants;
     release_unquantised(h);
 }
 
@@ -497,17 +506,20 @@ static int launch_forward(dw_handle* h, double L) {
     return DW_OK;
 }
 
-// ---- per-world luminosities (dw_step_n_trace_per_world) --------------------------------------------------------------
+// ---- per-world luminosities and constants (dw_step_n_trace_per_world, dw_step_n_trace_ensemble) ----------------------
 // The constants of a chunk of steps: [rows][B] PhysF32 | [rows][B] PhysF64 | [B] FirstStepBound (the first step of a
-// call from an un-quantised state in the exact mode; otherwise unused).  One device buffer, one page-locked image, one
+// call from an un-quantised state in the exact mode; otherwise unused) | [prows][B] PairPw (the step pairs of
+// dw_step_n_trace_ensemble, dw_step_fused_pw.hpp; otherwise none).  One device buffer, one page-locked image, one
 // upload per chunk; a launch gets the addresses of its row.
 struct PwLayout {
-    size_t B, rows, o64, ofb, bytes;
-    PwLayout(size_t B_, size_t rows_) : B(B_), rows(rows_) {
+    size_t B, rows, prows, o64, ofb, opair, bytes;
+    PwLayout(size_t B_, size_t rows_, size_t prows_ = 0) : B(B_), rows(rows_), prows(prows_) {
         o64 = sizeof(PhysF32) * rows * B;
         ofb = o64 + sizeof(PhysF64) * rows * B;
-        bytes = ofb + sizeof(FirstStepBound) * B;
+        opair = ofb + sizeof(FirstStepBound) * B;
+        bytes = opair + sizeof(PairPw) * prows * B;
     }
+    PairPw* pair(unsigned char* base, size_t row) const { return reinterpret_cast<PairPw*>(base + opair) + row * B; }
     // row `row` of each part of the table that starts at `base` (the device buffer or its host image)
     PhysF32* p32(unsigned char* base, size_t row) const { return reinterpret_cast<PhysF32*>(base) + row * B; }
     PhysF64* p64(unsigned char* base, size_t row) const { return reinterpret_cast<PhysF64*>(base + o64) + row * B; }
@@ -516,7 +528,10 @@ struct PwLayout {
 
 // One step, world b with the constants row32[b] / row64[b] (device addresses): the first step from an un-quantised state
 // and every shape the per-world wave-strip kernels do not take by step_generic_pw.
-static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* row64, const FirstStepBound* rowfb) {
+// `sym`: the albedo-symmetric form of the exact wave-strip kernel (every world's set is symmetric); `constants`: the rows
+// differ in more than the luminosity (dw_step_n_trace_ensemble), which the handle remembers.
+static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* row64, const FirstStepBound* rowfb, bool sym,
+                             bool constants) {
     const dw_params& p = h->prm;
     const StepPlan& pl = h->plan;
     const StepOut o = step_out(h);                              // (its constants stay unset: the rows carry them)
@@ -536,7 +551,7 @@ static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* 
     } else if (pl.pw_stream && ex) {
         const StreamExactPwArgs A{iL, iD, o.L, o.D, pl.sgeom, row32, row64, o.stats, o.fixups, o.zero_me, o.zero_n};
         with_int<0, 1, 2>(pl.halo, [&](auto HL) {
-            with_bool(pl.sym_albedo, [&](auto SYM) {
+            with_bool(sym, [&](auto SYM) {
                 hipLaunchKernelGGL((step_stream_exact_pw<HL, SYM>), dim3((unsigned)pl.sgeom.chunk * 8u), dim3(256), 0, h->stream, A);
             });
         });
@@ -550,7 +565,25 @@ static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* 
         with_int<2, 0, 1>(prec, [&](auto PR) { generic(iL, iD, PR); });
     }
     HIPCHK(hipGetLastError());
-    step_done(h, 0.0, true, true);
+    step_done(h, 0.0, true, true, constants);
+    return DW_OK;
+}
+
+// Two steps in one launch, world b with the coefficient sets row[b] (a device address): the trace form of the float32-only
+// step pairs (launch_forward_fused2 with `trace`) on the plan's un-packed overlapped or rotating strips.  The retained
+// previous state is not valid afterwards; the caller ends with a single step.
+static int launch_forward_fused2_pw(dw_handle* h, const PairPw* row, StatsDev* trace) {
+    const StepPlan& pl = h->plan;
+    const StepOut o = step_out(h);                              // (its constants stay unset: the row carries them)
+    const FusedGeom& g = pl.fgeom;
+    const dim3 grid((unsigned)g.chunk * 8u);
+    const plane_t *inL = h->L16[h->cur].get(), *inD = h->D16[h->cur].get();
+    with_int<kFusedRot, kFusedOvl>(pl.fused_mode, [&](auto MODE) {
+        hipLaunchKernelGGL((trace_pair_fast_pw<MODE>), grid, dim3(256), 0, h->stream, inL, inD, o.L, o.D, g, row, o.zero_me,
+                           o.zero_n, trace);
+    });
+    HIPCHK(hipGetLastError());
+    step_done(h, 0.0, false, true, true);
     return DW_OK;
 }
 
@@ -1054,6 +1087,7 @@ int dw_download_caches(dw_handle* h, double L, double* temps, double* betas, dou
                        double* temp_effective) {
     NEED(h, DW_EINVAL, "null handle");
     NEED(h->have_state, DW_ESTATE, "no state");
+    NEED_SHARED_CONSTANTS(h, "dw_download_caches");
     HIPCHK(hipSetDevice(h->prm.device));
     const size_t n = h->cells;
     int rc = ensure_scratch(h, sizeof(double) * 9 * n);
@@ -1076,6 +1110,7 @@ int dw_download_caches(dw_handle* h, double L, double* temps, double* betas, dou
 int dw_reduce_temperature(dw_handle* h, double L, dw_temp_stats* per_world) {
     NEED(h && per_world, DW_EINVAL, "null argument");
     NEED(h->have_state, DW_ESTATE, "no state");
+    NEED_SHARED_CONSTANTS(h, "dw_reduce_temperature");
     static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev), "temperature record layout");
     HIPCHK(hipSetDevice(h->prm.device));
     const size_t bytes = sizeof(TempStatsDev) * (size_t)h->prm.batch;
@@ -1250,10 +1285,18 @@ int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_w
     return DW_OK;
 }
 
-// dw_step_n_trace_per_world, and the per-world form of dw_step_n_trace_temperature (`temps` != null: the temperature
-// records of every step, reduced from the step's input planes at the step's row of the table)
-static int trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace, dw_temp_stats* temps) {
-    NEED(h && L_schedule, DW_EINVAL, "null argument");
+// dw_step_n_trace_ensemble takes step pairs (trace_pair_fast_pw) on the plans dw_step_n_trace does, in the float32-only
+// mode; the exact pair kernel does not keep its row loop with constants from a table (dw_step_fused_pw.hpp)
+static bool ensemble_pairs(const dw_handle* h) { return h->plan.trace_pairs && h->prm.precision == DW_PRECISION_FAST; }
+
+// dw_step_n_trace_per_world, the per-world form of dw_step_n_trace_temperature (`temps` != null: the temperature
+// records of every step, reduced from the step's input planes at the step's row of the table) and
+// dw_step_n_trace_ensemble (`worlds` != null: world b derives its rows from the handle's params with worlds[b]'s members;
+// `ensemble`: the step pairs of dw_step_n_trace where its plan takes them, and the handle remembers that the constants
+// were per-world).
+static int trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace, dw_temp_stats* temps,
+                           const dw_world_params* worlds = nullptr, bool ensemble = false) {
+    NEED(h && L_schedule && (worlds || !ensemble), DW_EINVAL, "null argument");
     NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
     if (nsteps == 0) return DW_OK;
     NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
@@ -1263,23 +1306,58 @@ static int trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedul
     for (size_t i = 0; i < (size_t)nsteps * B; ++i)
         NEED(std::isfinite(L_schedule[i]) && L_schedule[i] >= 0.0, DW_EINVAL,
              "L_schedule[step %zu][world %zu] = %g: a luminosity is finite and not negative", i / B, i % B, L_schedule[i]);
+    // a world's params: the handle's with the world's members (check_params refuses among those only g: g < 0 in the
+    // float32 precisions)
+    std::vector<dw_params> wp(worlds ? B : 1, p);
+    for (size_t b = 0; worlds && b < B; ++b) {
+        wp[b] = with_world_params(p, worlds[b]);
+        if (check_params(&wp[b]) != DW_OK) {
+            char why[sizeof(g_err)];
+            snprintf(why, sizeof(why), "%s", g_err);
+            return fail(DW_EINVAL, "worlds[%zu].g = %g: %s", b, worlds[b].g, why);
+        }
+    }
+    auto params_of = [&](size_t b) -> const dw_params& { return wp[worlds ? b : 0]; };
+    const bool sym = worlds ? worlds_symmetric(worlds, B) && !h->sw.no_sym : h->plan.sym_albedo;
     HIPCHK(hipSetDevice(p.device));
-    // rows of the series on the device at a time: as dw_step_n_trace (no pairs here: any number of rows will do; with
-    // temperature records, 32 MiB of those)
+    // step pairs (dw_step_n_trace_ensemble without temperature records, float32-only plans with trace_pairs): where
+    // dw_step_n_trace issues one - from a quantised state, never the closing one or two steps, both rows in one chunk of
+    // the series
+    const bool pairs = ensemble && !temps && ensemble_pairs(h);
+    // rows of the series on the device at a time: as dw_step_n_trace (single steps: any number of rows will do; pairs: an
+    // even number, at least two; with temperature records, 32 MiB of those)
     const size_t trow_bytes = sizeof(TempStatsDev) * B;
     size_t rows = h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / (temps ? trow_bytes : row_bytes);
+    if (pairs) rows = (rows & ~(size_t)1) < 2 ? 2 : (rows & ~(size_t)1);
     rows = rows < 1 ? 1 : (rows > (size_t)nsteps ? (size_t)nsteps : rows);
-    // rows of the table: 8 MiB of constants (256 B per step and world), under the test hook as many as trace rows
+    std::vector<unsigned char> is_pair(pairs ? (size_t)nsteps : 0, 0);
+    size_t npairs = 0;
+    if (pairs) {
+        bool quantised = cur_quantised(h);
+        for (int t = 0; t < nsteps;) {
+            if (quantised && nsteps - t >= 3 && (size_t)t % rows + 2 <= rows) { is_pair[t] = 1; ++npairs; t += 2; }
+            else { quantised = true; t += 1; }
+        }
+    }
+    // rows of the table: 8 MiB of single-step constants (256 B per step and world) and, with pairs, 8 MiB of theirs (256 B
+    // per pair and world); under the test hook as many as trace rows hold
     size_t trows = ((size_t)8 << 20) / ((sizeof(PhysF32) + sizeof(PhysF64)) * B);
     if (h->sw.trace_rows >= 1 && trows > (size_t)h->sw.trace_rows) trows = (size_t)h->sw.trace_rows;
     trows = trows < 1 ? 1 : (trows > (size_t)nsteps ? (size_t)nsteps : trows);
-    const PwLayout lay(B, trows);
+    size_t prows = 0;
+    if (npairs) {
+        prows = ((size_t)8 << 20) / (sizeof(PairPw) * B);
+        if (h->sw.trace_rows >= 1 && prows > (size_t)h->sw.trace_rows / 2) prows = (size_t)h->sw.trace_rows / 2;
+        prows = prows < 1 ? 1 : (prows > npairs ? npairs : prows);
+    }
+    const PwLayout lay(B, trows, prows);
+    const bool want_trace_d = trace || pairs;                   // (the pair kernels always record their two rows)
     // the table and (when a series is wanted) the trace buffer: all or nothing; then the table's page-locked image
     if (temps) {
         if (int rc = alloc_group(h, "the per-world constants, the trace buffer and the temperature reduction",
                                  {{h->pw_tab, lay.bytes}, {h->trace_d, trace ? rows * row_bytes : 0},
                                   {h->temp_part, temp_part_bytes(h)}, {h->temp_d, rows * trow_bytes}})) return rc;
-    } else if (trace) {
+    } else if (want_trace_d) {
         if (int rc = alloc_group(h, "the per-world constants and the trace buffer",
                                  {{h->pw_tab, lay.bytes}, {h->trace_d, rows * row_bytes}})) return rc;
     } else if (int rc = alloc_group(h, "the per-world constants", {{h->pw_tab, lay.bytes}})) {
@@ -1297,63 +1375,103 @@ static int trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedul
     unsigned char* img = h->pw_pinned.get();
     unsigned char* tab = h->pw_tab.get();
     // a world whose luminosity did not change since its last step keeps its constants (a sweep at fixed L derives B sets,
-    // not nsteps * B)
+    // not nsteps * B); likewise a world whose two luminosities did not change since its last pair
     std::vector<double> lastL(B, -1.0);
     std::vector<PhysF32> last32(B);
     std::vector<PhysF64> last64(B);
+    std::vector<PairPw> last_pair(npairs ? B : 0);
+    std::vector<double> lastLa(npairs ? B : 0, -1.0), lastLb(npairs ? B : 0, -1.0);
     const bool first_bound = h->unq == OWN_CUR && h->plan.first_prec == 3;
-    bool image_in_flight = false;
-    // A step whose luminosities all equal the previous step's shares its row (a sweep at fixed luminosities: ONE row, one
-    // upload of B entries for the whole run); a chunk is the steps that `trows` distinct rows serve.
-    std::vector<size_t> row_of(trows ? (size_t)nsteps : 0);
+    bool image_in_flight = false, first_pair = true;
+    // A step whose luminosities all equal those of the step before it of its kind shares that step's row (a sweep at fixed
+    // luminosities: ONE row of each kind, one upload for the whole run); a chunk is the steps that `trows` distinct
+    // single-step rows and `prows` distinct pair rows serve.
+    std::vector<size_t> row_of((size_t)nsteps);
     int chunk_end = 0;                                          // the steps before it have their rows on the device
-    for (int t = 0; t < nsteps; ++t) {
+    for (int t = 0; t < nsteps;) {
         const size_t sr = (size_t)t % rows;
         if (t == chunk_end) {                                   // this chunk's constants: derived in float64, one upload
             if (image_in_flight) HIPCHK(hipEventSynchronize(uploaded));
-            size_t tn = 0;
-            for (; chunk_end < nsteps; ++chunk_end) {
+            size_t tn = 0, pn = 0;
+            const double *single_Ls = nullptr, *pair_Ls = nullptr;      // the steps the newest row of each kind was built for
+            while (chunk_end < nsteps) {
                 const double* Ls = L_schedule + (size_t)chunk_end * B;
-                if (tn && std::memcmp(Ls, Ls - B, sizeof(double) * B) == 0) { row_of[chunk_end] = tn - 1; continue; }
+                if (pairs && is_pair[chunk_end]) {
+                    if (pair_Ls && std::memcmp(Ls, pair_Ls, sizeof(double) * 2 * B) == 0) { row_of[chunk_end] = pn - 1; chunk_end += 2; continue; }
+                    if (pn == prows) break;
+                    PairPw* row = lay.pair(img, pn);
+                    for (size_t b = 0; b < B; ++b) {
+                        if (Ls[b] != lastLa[b] || Ls[B + b] != lastLb[b]) {   // the sets of launch_forward_fused2 (float32-only
+                            lastLa[b] = Ls[b];                                // mode), at this world's constants
+                            lastLb[b] = Ls[B + b];
+                            last_pair[b].P1 = derive_f32(params_of(b), lastLa[b]);
+                            last_pair[b].P2 = derive_f32(params_of(b), lastLb[b]);
+                        }
+                        row[b] = last_pair[b];
+                    }
+                    pair_Ls = Ls;
+                    row_of[chunk_end] = pn++;
+                    chunk_end += 2;
+                    continue;
+                }
+                if (single_Ls && std::memcmp(Ls, single_Ls, sizeof(double) * B) == 0) { row_of[chunk_end++] = tn - 1; continue; }
                 if (tn == trows) break;
                 PhysF32* r32 = lay.p32(img, tn);
                 PhysF64* r64 = lay.p64(img, tn);
                 for (size_t b = 0; b < B; ++b) {
                     if (Ls[b] != lastL[b]) {
                         lastL[b] = Ls[b];
-                        last32[b] = derive_f32(p, Ls[b]);
-                        last64[b] = make_f64(p, Ls[b]);
+                        last32[b] = derive_f32(params_of(b), Ls[b]);
+                        last64[b] = make_f64(params_of(b), Ls[b]);
                     }
                     r32[b] = last32[b];
                     r64[b] = last64[b];
                 }
-                row_of[chunk_end] = tn++;
+                single_Ls = Ls;
+                row_of[chunk_end++] = tn++;
             }
             if (t == 0 && first_bound)
                 for (size_t b = 0; b < B; ++b)
-                    lay.fb(img)[b] = derive_first_bound(p, L_schedule[b], lay.p32(img, 0)[b], h->unq_kind == UNQ_F64,
+                    lay.fb(img)[b] = derive_first_bound(params_of(b), L_schedule[b], lay.p32(img, 0)[b], h->unq_kind == UNQ_F64,
                                                         h->sw.first_slack);     // (row 0 of the first chunk is step 0)
-            // (the rows in use of both parts)
-            HIPCHK(hipMemcpyAsync(h->pw_tab.get(), img, sizeof(PhysF32) * tn * B, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->pw_tab.get() + lay.o64, img + lay.o64, sizeof(PhysF64) * tn * B, hipMemcpyHostToDevice, h->stream));
+            // (the rows in use of each part)
+            if (tn) {
+                HIPCHK(hipMemcpyAsync(tab, img, sizeof(PhysF32) * tn * B, hipMemcpyHostToDevice, h->stream));
+                HIPCHK(hipMemcpyAsync(tab + lay.o64, img + lay.o64, sizeof(PhysF64) * tn * B, hipMemcpyHostToDevice, h->stream));
+            }
             if (t == 0 && first_bound)
-                HIPCHK(hipMemcpyAsync(h->pw_tab.get() + lay.ofb, img + lay.ofb, sizeof(FirstStepBound) * B, hipMemcpyHostToDevice, h->stream));
+                HIPCHK(hipMemcpyAsync(tab + lay.ofb, img + lay.ofb, sizeof(FirstStepBound) * B, hipMemcpyHostToDevice, h->stream));
+            if (pn) HIPCHK(hipMemcpyAsync(tab + lay.opair, img + lay.opair, sizeof(PairPw) * pn * B, hipMemcpyHostToDevice, h->stream));
             HIPCHK(hipEventRecord(uploaded, h->stream));
             image_in_flight = true;
         }
         const size_t tr = row_of[t];
-        if (temps)
-            if (int rc = launch_temp_moments(h, true, 0.0, lay.p64(tab, tr), h->temp_d.get() + sr * B)) return rc;
-        if (int rc = launch_forward_pw(h, lay.p32(tab, tr), lay.p64(tab, tr), lay.fb(tab))) return rc;
-        if (temps && (sr + 1 == rows || t + 1 == nsteps))
-            HIPCHK(hipMemcpyAsync(temps + ((size_t)t - sr) * B, h->temp_d.get(), (sr + 1) * trow_bytes, hipMemcpyDeviceToHost,
-                                  h->stream));
-        if (trace) {
-            HIPCHK(hipMemcpyAsync(h->trace_d.get() + sr * B, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
-            if (sr + 1 == rows || t + 1 == nsteps)
-                HIPCHK(hipMemcpyAsync(trace + ((size_t)t - sr) * B, h->trace_d.get(), (sr + 1) * row_bytes, hipMemcpyDeviceToHost,
-                                      h->stream));
+        int took = 1;
+        if (pairs && sr == 0) {                                 // the pair kernels ADD their reductions into the rows
+            const size_t left = (size_t)(nsteps - t);
+            HIPCHK(hipMemsetAsync(h->trace_d.get(), 0, (left < rows ? left : rows) * row_bytes, h->stream));
         }
+        if (pairs && is_pair[t]) {
+            if (first_pair) {
+                drop_unquantised_previous(h);
+                first_pair = false;
+            }
+            if (int rc = launch_forward_fused2_pw(h, lay.pair(tab, tr), h->trace_d.get() + sr * B)) return rc;
+            took = 2;
+        } else {
+            if (temps)
+                if (int rc = launch_temp_moments(h, true, 0.0, lay.p64(tab, tr), h->temp_d.get() + sr * B)) return rc;
+            if (int rc = launch_forward_pw(h, lay.p32(tab, tr), lay.p64(tab, tr), lay.fb(tab), sym, ensemble)) return rc;
+            if (want_trace_d)
+                HIPCHK(hipMemcpyAsync(h->trace_d.get() + sr * B, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
+        }
+        const size_t filled = sr + (size_t)took;                // rows of this chunk of the series that are recorded now
+        if (filled == rows || t + took == nsteps) {
+            const size_t r0 = ((size_t)t - sr) * B;
+            if (temps) HIPCHK(hipMemcpyAsync(temps + r0, h->temp_d.get(), filled * trow_bytes, hipMemcpyDeviceToHost, h->stream));
+            if (trace) HIPCHK(hipMemcpyAsync(trace + r0, h->trace_d.get(), filled * row_bytes, hipMemcpyDeviceToHost, h->stream));
+        }
+        t += took;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     sync.disarm();
@@ -1362,6 +1480,20 @@ static int trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedul
 
 int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace) {
     return trace_per_world(h, nsteps, L_schedule, trace, nullptr);
+}
+
+int dw_world_params_of(const dw_handle* h, dw_world_params* out) {
+    NEED(h && out, DW_EINVAL, "null argument");
+    *out = world_params_of(h->prm);
+    return DW_OK;
+}
+
+int dw_step_n_trace_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params* worlds, const double* L_schedule,
+                             dw_world_stats* trace, dw_temp_stats* temps) {
+    static_assert(sizeof(dw_world_params) == 96, "dw_world_params layout");
+    static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev), "temperature record layout");
+    NEED(h && worlds && L_schedule, DW_EINVAL, "null argument");
+    return trace_per_world(h, nsteps, L_schedule, trace, temps, worlds, true);
 }
 
 int dw_step_n_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_schedule, int per_world, dw_world_stats* trace,
@@ -2220,6 +2352,7 @@ int dw_snapshot_save_slot(dw_handle* h, int32_t slot) {
     sn.stepped = h->stepped;
     sn.L_last = h->L_last;
     sn.L_per_world = h->L_per_world;
+    sn.P_per_world = h->P_per_world;
     sn.unq = h->unq;
     sn.agents = bn && h->have_agents;
     if (sn.agents) {
@@ -2260,6 +2393,7 @@ int dw_snapshot_restore_slot(dw_handle* h, int32_t slot) {
     h->stepped = sn.stepped;
     h->L_last = sn.L_last;
     h->L_per_world = sn.L_per_world;
+    h->P_per_world = sn.P_per_world;
     return DW_OK;
 }
 
@@ -2362,6 +2496,11 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     if (h->sw.text[0]) {                                        // the switches this handle was created under
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, "; switches[%s]", h->sw.text);
+    }
+    {                                                           // the form dw_step_n_trace_ensemble takes (trace_per_world)
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; per-world constants: %s",
+                 ensemble_pairs(h) ? "step pairs" : (pl.pw_stream ? "wave strips" : "generic"));
     }
     return DW_OK;
 }

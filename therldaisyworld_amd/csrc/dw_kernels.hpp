@@ -10,6 +10,7 @@
 //   dw_step_fused.hpp     step_stream_fused2[_exact]   two steps per HBM round trip (dw_step_n): the headline
 //   dw_step_first.hpp     step_first_stream  the first step of an episode (un-quantised input), W a multiple of 256
 //   dw_step_per_world.hpp step_stream_*_pw, step_generic_pw   a single step with the constants of each world's own luminosity
+//   dw_step_fused_pw.hpp  trace_pair_*_pw   the step pairs of a trace with each world's own constants (parameter ensembles)
 //   dw_episode.hpp        episode_small     K steps in one launch with the worlds in LDS (H*W <= 4096)
 //   dw_episode_wave.hpp   episode_wave      the same for H*W <= 256: one wave per world, no workgroup barrier in the step
 //   dw_agents.hpp         agents_update (ref :181-244), observe (ref get_obs :246-263), policy_greedy
@@ -30,6 +31,7 @@
 #include "dw_step_fused.hpp"
 #include "dw_step_first.hpp"
 #include "dw_step_per_world.hpp"
+#include "dw_step_fused_pw.hpp"
 #include "dw_episode.hpp"
 #include "dw_episode_wave.hpp"
 #include "dw_agents.hpp"

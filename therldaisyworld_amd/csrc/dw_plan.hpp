@@ -65,6 +65,30 @@ inline Switches read_switches() {
     return w;
 }
 
+// ---- per-world constants (dw_step_n_trace_ensemble) ----------------------------------------------------------------
+// A world of an ensemble call carries the twelve physics members of dw_params itself (dw_world_params).  Everything
+// below - make_f64, derive_f32, derive_f32_pair, derive_first_bound - takes a dw_params: a world's constants are derived
+// from the handle's params with those members replaced, by the same functions and nothing else.
+inline dw_params with_world_params(dw_params p, const dw_world_params& w) {
+    p.p = w.p; p.g = w.g; p.S = w.S; p.sigma = w.sigma; p.gamma = w.gamma; p.q = w.q; p.q2 = w.q2; p.dt = w.dt;
+    p.albedo_bare = w.albedo_bare; p.albedo_light = w.albedo_light; p.albedo_dark = w.albedo_dark;
+    p.temp_optimal = w.temp_optimal;
+    return p;
+}
+inline dw_world_params world_params_of(const dw_params& p) {
+    return dw_world_params{p.p, p.g, p.S, p.sigma, p.gamma, p.q, p.q2, p.dt, p.albedo_bare, p.albedo_light, p.albedo_dark,
+                           p.temp_optimal};
+}
+// a_dark - a_bare == -(a_light - a_bare) exactly: the two-term coefficient chain (growth_t<.., SYM>) applies
+inline bool albedo_symmetric(double bare, double light, double dark) { return (dark - bare) == -(light - bare); }
+// ... for a whole call: the kernels are instantiated once per launch, so SYM holds only if EVERY world's set is symmetric
+// (both instantiations give the same values; SYM = false costs instructions, never results)
+inline bool worlds_symmetric(const dw_world_params* worlds, size_t B) {
+    for (size_t b = 0; b < B; ++b)
+        if (!albedo_symmetric(worlds[b].albedo_bare, worlds[b].albedo_light, worlds[b].albedo_dark)) return false;
+    return true;
+}
+
 // ---- constants: float64 set and the per-step float32 set -----------------------------------------------------------
 inline PhysF64 make_f64(const dw_params& p, double L) {
     PhysF64 P;
@@ -326,7 +350,7 @@ inline int strip_rows_or_override(const Switches& sw, int cap, long groups, int 
 
 inline StepPlan plan_steps(const dw_params& p, const Switches& sw) {
     StepPlan s;
-    s.sym_albedo = (p.albedo_dark - p.albedo_bare) == -(p.albedo_light - p.albedo_bare) && !sw.no_sym;
+    s.sym_albedo = albedo_symmetric(p.albedo_bare, p.albedo_light, p.albedo_dark) && !sw.no_sym;
     s.halo = halo_form(p.width);
     // Packed mode of the wave-strip kernels: narrow worlds whose width divides 256 sit side by side in one 256-column wave
     // row (256/W worlds per wave) - only for ensembles with enough wave-strips to occupy the GPU: a lone strip is a serial

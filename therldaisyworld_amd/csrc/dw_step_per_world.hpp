@@ -27,7 +27,9 @@ __device__ __forceinline__ const T& table_entry(const T* tab, int i) {
 // The world of this wave's strip, with stream_body's own strip numbering (XCD-chunked workgroups of four strips); waves
 // past the last strip - stream_body sends them home after workgroup 0's have cleared the old reductions - read the last
 // strip's entry, so the index is always inside the table.  readfirstlane: the value is uniform, and says so.
-__device__ __forceinline__ int strip_world(const StripGeom& G) {
+// (StripGeom, and the FusedGeom of the un-packed step pairs - dw_step_fused_pw.hpp: fused2_body numbers its strips alike)
+template <class StripGeomT>
+__device__ __forceinline__ int strip_world(const StripGeomT& G) {
     const int bid = blockIdx.x;
     const int wg = (bid & 7) * G.chunk + (bid >> 3);
     const int s = __builtin_amdgcn_readfirstlane(wg * 4 + ((int)threadIdx.x >> 6));

@@ -209,6 +209,53 @@ class Engine:
             temps.ctypes.data_as(C.POINTER(DwTempStats))))
         return out, temps
 
+    def world_params(self):
+        """The engine's own physics constants as one record of dtype `_ffi.WORLD_PARAMS_DTYPE` (`dw_world_params_of`): a
+        row of the table `step_n_trace_ensemble` takes."""
+        out = np.zeros((), dtype=_ffi.WORLD_PARAMS_DTYPE)
+        self._check(self._lib.dw_world_params_of(self._h, out.ctypes.data_as(C.POINTER(_ffi.DwWorldParams))))
+        return out
+
+    def _world_table(self, worlds):
+        """`worlds` as a contiguous (B,) array of `_ffi.WORLD_PARAMS_DTYPE`: a structured array with those fields, or a
+        (B, 12) float64 array in the struct's order."""
+        w = np.asarray(worlds)
+        if w.dtype.names is not None:
+            if set(w.dtype.names) != set(_ffi.WORLD_PARAM_NAMES):
+                raise ValueError(f"per-world constants need the fields {_ffi.WORLD_PARAM_NAMES}, got {w.dtype.names}")
+            tab = np.zeros(w.shape, dtype=_ffi.WORLD_PARAMS_DTYPE)
+            for name in _ffi.WORLD_PARAM_NAMES:
+                tab[name] = w[name]
+        else:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.ndim != 2 or w.shape[1] != len(_ffi.WORLD_PARAM_NAMES):
+                raise ValueError(f"per-world constants need shape ({self.B}, {len(_ffi.WORLD_PARAM_NAMES)}), got {w.shape}")
+            tab = w.view(_ffi.WORLD_PARAMS_DTYPE).reshape(-1)
+        if tab.shape != (self.B,):
+            raise ValueError(f"per-world constants need shape ({self.B},) records or ({self.B}, "
+                             f"{len(_ffi.WORLD_PARAM_NAMES)}) values, got {np.shape(worlds)}")
+        return np.ascontiguousarray(tab)
+
+    def step_n_trace_ensemble(self, worlds, L, temperature=False, trace=True):
+        """`len(L)` agent-free steps, world b with the physics constants `worlds[b]` (a structured array of dtype
+        `_ffi.WORLD_PARAMS_DTYPE`, or (B, 12) float64 in the struct's order; `world_params()` is the engine's own row) at
+        the luminosity `L[t, b]` (`dw_step_n_trace_ensemble`): each world ends exactly where a one-world engine with those
+        constants would.  Returns the (n, B) records of `step_n_trace` (None with `trace=False`) - with
+        `temperature=True` the pair `(records, temperature records)` of `step_n_trace_temperature`.  The engine's own
+        params are unchanged; afterwards it is "per-world": `download_grid`, `get_obs`, `download_caches` and
+        `reduce_temperature` raise until a shared-L step or an upload."""
+        tab = self._world_table(worlds)
+        Ls = np.ascontiguousarray(L, dtype=np.float64)
+        if Ls.ndim != 2 or Ls.shape[1] != self.B:
+            raise ValueError(f"per-world luminosities need shape (n, {self.B}), got {Ls.shape}")
+        out = np.zeros(Ls.shape, dtype=_ffi.STATS_DTYPE) if trace else None
+        temps = np.zeros(Ls.shape, dtype=_ffi.TEMP_STATS_DTYPE) if temperature else None
+        self._check(self._lib.dw_step_n_trace_ensemble(
+            self._h, int(Ls.shape[0]), tab.ctypes.data_as(C.POINTER(_ffi.DwWorldParams)), _ffi.ptr_d(Ls),
+            out.ctypes.data_as(C.POINTER(DwWorldStats)) if trace else None,
+            temps.ctypes.data_as(C.POINTER(DwTempStats)) if temperature else None))
+        return (out, temps) if temperature else out
+
     def last_step_n_timing(self):
         """(ms spent in the fused step-pair launches of the last step_n call, their number, plane element bytes)."""
         ms, n, eb = C.c_float(0), C.c_int32(0), C.c_int32(0)

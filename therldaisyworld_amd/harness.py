@@ -326,6 +326,58 @@ def simulate_luminosity_sweep(env, L_values, nsteps, obs=None, temperature=False
     return _series_dict(env, L, stats, temps)
 
 
+def simulate_parameter_sweep(env, params, nsteps, L_values=None, obs=None, temperature=False):
+    """A sweep over physics constants in ONE run: world b steps with the constants `params` names - a dict from a member
+    of `_ffi.WORLD_PARAM_NAMES` (`q2`, `gamma`, the albedos, `temp_optimal`, `dt`, ...) to a scalar or a length-B array;
+    members not named keep the environment's attribute - the figures the reference's notebooks assemble from one run per
+    value (`run_q2_sims`: the same ramp with `env.q2 = 0, q/64, q/8`).  `L_values=None`: every world follows the
+    environment's own luminosity ramp, as `simulate_ramp` (and the environment's `L` advances with it); `(B,)` or
+    `(nsteps, B)`: as `simulate_luminosity_sweep` reads them.  Recorded on the device (`dw_step_n_trace_ensemble`), one
+    download.  `obs=None`: reset first.
+
+    Returns the dict of `simulate_luminosity_sweep` (`L` of shape (n, B)) plus `params`, the (B,) table of dtype
+    `_ffi.WORLD_PARAMS_DTYPE` the run used; with `temperature=True`, `dead_temp[:, b]` is the lifeless temperature of
+    world b from its own `S`, `sigma` and `albedo_bare`.  As after `simulate_luminosity_sweep`, `env.step()` and `env.grid`
+    raise until `env.reset()`."""
+    if env.n_agents:
+        raise ValueError("simulate_parameter_sweep is for agent-free ensembles (n_agents == 0)")
+    n, B = int(nsteps), int(env.batch_size)
+    unknown = sorted(set(params) - set(_ffi.WORLD_PARAM_NAMES))
+    if unknown:
+        raise ValueError(f"not a per-world constant: {unknown} (one of {_ffi.WORLD_PARAM_NAMES})")
+    table = np.zeros(B, dtype=_ffi.WORLD_PARAMS_DTYPE)
+    for name in _ffi.WORLD_PARAM_NAMES:
+        value = np.asarray(params.get(name, getattr(env, name)), dtype=np.float64)
+        if value.shape not in ((), (B,)):
+            raise ValueError(f"params[{name!r}] needs a scalar or shape ({B},), got {value.shape}")
+        table[name] = value
+    ramp = L_values is None
+    if not ramp:
+        L = np.asarray(L_values, dtype=np.float64)
+        if L.ndim == 1:
+            L = np.broadcast_to(L, (n, L.shape[0]))
+        if L.ndim != 2 or L.shape != (n, B):
+            raise ValueError(f"L_values needs shape ({B},) or ({n}, {B}), got {np.shape(L_values)}")
+    if obs is None:
+        env.reset()
+    if ramp:
+        L = np.repeat(np.asarray(_luminosity_schedule(env, n), dtype=np.float64)[:, None], B, axis=1)
+    L = np.ascontiguousarray(L)
+    eng = env._ensure_engine()
+    env._sync_to_device()
+    res = eng.step_n_trace_ensemble(table, L, temperature=temperature)
+    stats, temps = res if temperature else (res, None)
+    if ramp:
+        _advance_host_scalars(env, n)
+    env._invalidate()
+    env._per_world_L = True
+    out = _series_dict(env, L, stats, temps)
+    if temps is not None:
+        out["dead_temp"] = ((table["S"] * L * (1 - table["albedo_bare"])) / table["sigma"]) ** (1 / 4)
+    out["params"] = table
+    return out
+
+
 def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_chunk):
     """The step loop shared by the two fitness harnesses: chunks of steps device-resident
     (``dw_run_episode_mlp``), the reference's per-step float64 bookkeeping done by `after_chunk(rewards,
