@@ -490,6 +490,39 @@ int dw_run_episode(dw_handle* h, int32_t nsteps, const double* L_schedule, int p
                    const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
                    uint8_t* agent_ok);
 
+/* dw_run_episode with a set of physics constants and a luminosity column per WORLD: the reference's lifespan table
+ * (notebooks/greedy_longevity_abatement.ipynb: albedo settings x policies, each an ensemble run until every biosphere is
+ * dead) or a lifespan-versus-q2 / gamma / temp_optimal scan as ONE device-resident run instead of one handle
+ * configuration and one run per scenario.  World b steps with worlds[b] (fixed for the whole call; the members of
+ * dw_params that dw_world_params does not carry - agent_gamma, food_chain_penalty, obs_mask, the initial-state fields -
+ * stay the handle's and are shared) and takes step t at L_schedule[t*B + b]; policy_mode, use_table, table, threshold_k
+ * and the flags are dw_run_episode's (the per-world policy mix is the table's codes -1 / -2).
+ * Contract: take a ONE-world handle that holds world b and its agents, carries worlds[b] (dw_set_params) and is given
+ * column b of the schedule and slice [:, b] of the table.  Whatever dw_run_episode leaves on it - the planes, the
+ * retained previous state, the agents, dw_reduce, the device action buffer, its world_alive / agent_ok columns - this
+ * call leaves for world b, bit for bit, in DW_PRECISION_EXACT and DW_PRECISION_FAST; dw_last_fixup_count is the sum over
+ * the worlds.
+ * H*W <= 256 with at most 64 agents: one launch, one wave per world (episode_wave_pw, csrc/dw_episode_wave_pw.hpp: a wave
+ * stages its own world's float32 rows of a 64-step segment in LDS and takes the float64 repair set from its world's
+ * entry of a table); the rows - 136 bytes per step and world, all derived on the host in float64 by the functions that
+ * serve dw_set_params - go up in one copy from a page-locked image.  Every other shape, DW_NO_EPISODE_WAVE and
+ * DW_NO_EPISODE_KERNEL: launches per step from existing kernels (policy kernel or table slice, update_agents, the
+ * per-world single step of dw_step_n_trace_ensemble, flags), one synchronisation at the end; no fused pairs, no LDS
+ * workgroup kernel (dw_kernel_info: "; ensemble episode: one wave per world" / "launches per step").
+ * Checked before anything is launched or allocated (the state is untouched): the rules of dw_run_episode (DW_ESTATE: no
+ * state, no agents, an un-quantised current state; DW_EINVAL: DW_PRECISION_F64, collision_mode 1, nsteps outside 1..4096,
+ * the table rules), of dw_step_n_trace_ensemble (DW_EINVAL: a luminosity that is not finite or is negative; a world whose
+ * set dw_set_params would refuse - g < 0 - with a message that names the world and the member), null h, worlds or
+ * L_schedule.  Synchronises.
+ * Afterwards the handle is "per-world" in both senses, exactly as after dw_step_n_trace_ensemble: dw_get_obs,
+ * dw_download_grid, dw_download_caches, dw_reduce_temperature and the observations of dw_run_episode* return DW_ESTATE
+ * until a shared-L step, an upload or dw_init_random; the snapshots save and restore that mark. */
+int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps,
+                            const dw_world_params* worlds /* [B] */,
+                            const double* L_schedule      /* [nsteps][B] */,
+                            int policy_mode, const uint8_t* use_table, const int8_t* table,
+                            uint32_t threshold_k, uint8_t* world_alive, uint8_t* agent_ok);
+
 /* ---- plumbing ------------------------------------------------------------------------------- */
 
 /* Use an existing HIP stream (e.g. torch's current stream) instead of the handle's own. */
@@ -506,7 +539,8 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark);
 
 /* Name and geometry of the step kernel the handle dispatches for its shape, for bench/profiles:
  * writes a NUL-terminated description into buf.  Appended fragments name the forms of the other entry points:
- * "; trace: ...", "; per-world L: ...", and "; episode: F; mlp episode: F" - the form dw_run_episode and
+ * "; trace: ...", "; per-world L: ...", "; ensemble episode: ..." (dw_run_episode_ensemble) and
+ * "; episode: F; mlp episode: F" - the form dw_run_episode and
  * dw_run_episode_mlp take for the handle's shape, agent count, precision, collision mode and switches, F one of
  * "one wave per world" (H*W <= 256 and at most 64 agents, MLP: at most 4), "workgroup (LDS)" (H*W <= 4096) and
  * "launches per step" (dw_run_episode_mlp takes its first steps that way until the current and the previous state are

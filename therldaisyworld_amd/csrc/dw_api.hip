@@ -1289,6 +1289,29 @@ int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_w
 // mode; the exact pair kernel does not keep its row loop with constants from a table (dw_step_fused_pw.hpp)
 static bool ensemble_pairs(const dw_handle* h) { return h->plan.trace_pairs && h->prm.precision == DW_PRECISION_FAST; }
 
+// What the per-world calls check of their schedule before anything is launched or allocated
+static int check_luminosities(const double* L_schedule, size_t nsteps, size_t B) {
+    for (size_t i = 0; i < nsteps * B; ++i)
+        NEED(std::isfinite(L_schedule[i]) && L_schedule[i] >= 0.0, DW_EINVAL,
+             "L_schedule[step %zu][world %zu] = %g: a luminosity is finite and not negative", i / B, i % B, L_schedule[i]);
+    return DW_OK;
+}
+
+// A world's params: the handle's with the world's members (check_params refuses among those only g: g < 0 in the float32
+// precisions).  wp: one set per world, or the handle's alone without `worlds`.
+static int world_param_sets(const dw_params& p, const dw_world_params* worlds, size_t B, std::vector<dw_params>& wp) {
+    wp.assign(worlds ? B : 1, p);
+    for (size_t b = 0; worlds && b < B; ++b) {
+        wp[b] = with_world_params(p, worlds[b]);
+        if (check_params(&wp[b]) != DW_OK) {
+            char why[sizeof(g_err)];
+            snprintf(why, sizeof(why), "%s", g_err);
+            return fail(DW_EINVAL, "worlds[%zu].g = %g: %s", b, worlds[b].g, why);
+        }
+    }
+    return DW_OK;
+}
+
 // dw_step_n_trace_per_world, the per-world form of dw_step_n_trace_temperature (`temps` != null: the temperature
 // records of every step, reduced from the step's input planes at the step's row of the table) and
 // dw_step_n_trace_ensemble (`worlds` != null: world b derives its rows from the handle's params with worlds[b]'s members;
@@ -1303,20 +1326,9 @@ static int trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedul
     static_assert(sizeof(dw_world_stats) == sizeof(StatsDev), "stats layout");
     const dw_params& p = h->prm;
     const size_t B = (size_t)p.batch, row_bytes = sizeof(StatsDev) * B;
-    for (size_t i = 0; i < (size_t)nsteps * B; ++i)
-        NEED(std::isfinite(L_schedule[i]) && L_schedule[i] >= 0.0, DW_EINVAL,
-             "L_schedule[step %zu][world %zu] = %g: a luminosity is finite and not negative", i / B, i % B, L_schedule[i]);
-    // a world's params: the handle's with the world's members (check_params refuses among those only g: g < 0 in the
-    // float32 precisions)
-    std::vector<dw_params> wp(worlds ? B : 1, p);
-    for (size_t b = 0; worlds && b < B; ++b) {
-        wp[b] = with_world_params(p, worlds[b]);
-        if (check_params(&wp[b]) != DW_OK) {
-            char why[sizeof(g_err)];
-            snprintf(why, sizeof(why), "%s", g_err);
-            return fail(DW_EINVAL, "worlds[%zu].g = %g: %s", b, worlds[b].g, why);
-        }
-    }
+    if (int rc = check_luminosities(L_schedule, (size_t)nsteps, B)) return rc;
+    std::vector<dw_params> wp;
+    if (int rc = world_param_sets(p, worlds, B, wp)) return rc;
     auto params_of = [&](size_t b) -> const dw_params& { return wp[worlds ? b : 0]; };
     const bool sym = worlds ? worlds_symmetric(worlds, B) && !h->sw.no_sym : h->plan.sym_albedo;
     HIPCHK(hipSetDevice(p.device));
@@ -2161,21 +2173,28 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
     return DW_OK;
 }
 
+// What dw_run_episode and dw_run_episode_ensemble require of the handle and of their arguments
+static int check_episode_call(const dw_handle* h, int32_t nsteps, int policy_mode, const uint8_t* use_table, const int8_t* table) {
+    const dw_params& p = h->prm;
+    NEED(nsteps >= 1 && nsteps <= 4096, DW_EINVAL, "nsteps must be in 1..4096");
+    NEED(p.precision != DW_PRECISION_F64, DW_EINVAL, "dw_run_episode supports exact and fast precision");
+    NEED(p.collision_mode == 0, DW_EINVAL, "collision_mode=1 is not implemented on the device");
+    NEED(h->have_state, DW_ESTATE, "no state uploaded");
+    NEED(p.n_agents == 0 || h->have_agents, DW_ESTATE, "no agents uploaded");
+    NEED(cur_quantised(h), DW_ESTATE, "the current state is not quantised yet; take the first step with dw_step");
+    NEED(policy_mode != DW_POLICY_TABLE || table, DW_EINVAL, "DW_POLICY_TABLE needs a table");
+    if (use_table && !table)
+        for (int t = 0; t < nsteps; ++t) NEED(!use_table[t], DW_EINVAL, "use_table set but no table given");
+    return DW_OK;
+}
+
 static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                             const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
                             uint8_t* world_alive, uint8_t* agent_ok) {
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
-    NEED(nsteps >= 1 && nsteps <= 4096, DW_EINVAL, "nsteps must be in 1..4096");
-    NEED(p.precision != DW_PRECISION_F64, DW_EINVAL, "dw_run_episode supports exact and fast precision");
-    NEED(p.collision_mode == 0, DW_EINVAL, "collision_mode=1 is not implemented on the device");
+    if (int rc = check_episode_call(h, nsteps, policy_mode, use_table, table)) return rc;
     const int C = p.height * p.width, N = p.n_agents, B = p.batch;
-    NEED(h->have_state, DW_ESTATE, "no state uploaded");
-    NEED(N == 0 || h->have_agents, DW_ESTATE, "no agents uploaded");
-    NEED(cur_quantised(h), DW_ESTATE, "the current state is not quantised yet; take the first step with dw_step");
-    NEED(policy_mode != DW_POLICY_TABLE || table, DW_EINVAL, "DW_POLICY_TABLE needs a table");
-    if (use_table && !table)
-        for (int t = 0; t < nsteps; ++t) NEED(!use_table[t], DW_EINVAL, "use_table set but no table given");
     const EpisodeForm form = episode_form(h);                  // (F64 / collision_mode 1 were rejected above)
     if (form == EPISODE_STEPWISE)
         return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
@@ -2276,6 +2295,212 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
         if (world_alive) std::memcpy(world_alive, h->ep_pinned.get() + o_wa, K * B);
         if (want_ok) std::memcpy(agent_ok, h->ep_pinned.get() + o_ok, K * bn);
     }
+    return DW_OK;
+}
+
+// ---- dw_run_episode_ensemble: dw_run_episode with a set of physics constants and a luminosity column per world --------
+// The form the call takes: one wave per world (episode_wave_pw) wherever dw_run_episode takes episode_wave; every other
+// shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step
+static bool ensemble_episode_wave(const dw_handle* h) { return episode_form(h) == EPISODE_WAVE; }
+
+// twin[b]: world b's set equals world b - 1's (a scenario's block of worlds in a sweep): at the same luminosity it takes
+// that world's rows instead of a derivation of its own - S derivations per step for S scenarios, not B
+static std::vector<unsigned char> twin_worlds(const dw_world_params* worlds, size_t B) {
+    std::vector<unsigned char> twin(B, 0);
+    for (size_t b = 1; b < B; ++b) twin[b] = std::memcmp(&worlds[b], &worlds[b - 1], sizeof(dw_world_params)) == 0;
+    return twin;
+}
+
+// Launches per step from existing kernels - policy kernel or table slice, launch_agents, launch_forward_pw (the per-world
+// single step of dw_step_n_trace_ensemble), episode_flags - with one synchronisation at the end; no fused pairs and no
+// LDS workgroup kernel.  The rows of a chunk of steps (PwLayout) go up in one copy per part from the page-locked image.
+static int run_episode_ensemble_stepwise(dw_handle* h, int32_t nsteps, const std::vector<dw_params>& wp,
+                                         const std::vector<unsigned char>& twin, bool sym, const double* L_schedule, int policy_mode, const uint8_t* use_table, const int8_t* table,
+                                         uint32_t threshold_k, uint8_t* world_alive, uint8_t* agent_ok) {
+    const dw_params& p = h->prm;
+    const int N = p.n_agents, B = p.batch;
+    const size_t K = (size_t)nsteps, bn = (size_t)B * N, Bz = (size_t)B;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_tab = 0, o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * Bz), total = up(o_ok + K * bn) + 256;
+    size_t trows = ((size_t)8 << 20) / ((sizeof(PhysF32) + sizeof(PhysF64)) * Bz);
+    trows = trows < 1 ? 1 : (trows > K ? K : trows);
+    const PwLayout lay(Bz, trows);
+    if (int rc = ensure_ep_buf(h, total)) return rc;
+    if (int rc = alloc_group(h, "the per-world constants", {{h->pw_tab, lay.bytes}})) return rc;
+    if (int rc = reserve(h->pw_pinned, "the page-locked image of the per-world constants", lay.bytes)) {
+        h->pw_tab.reset();
+        return rc;
+    }
+    hipEvent_t uploaded = nullptr;                              // the image may be written again once its upload has run
+    HIPCHK(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+    struct EventGuard { hipEvent_t e; ~EventGuard() { (void)hipEventDestroy(e); } } event_guard{uploaded};
+    SyncOnExit guard(h->stream);                                // `table` and the flag arrays are the caller's
+    if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
+    unsigned char* img = h->pw_pinned.get();
+    unsigned char* tab = h->pw_tab.get();
+    std::vector<double> lastL(Bz, -1.0);                        // a world whose luminosity did not change keeps its rows
+    std::vector<PhysF32> last32(Bz);
+    std::vector<PhysF64> last64(Bz);
+    const int nflag = B > (int)bn ? B : (int)bn;
+    size_t chunk_begin = 0, chunk_end = 0;
+    for (size_t t = 0; t < K; ++t) {
+        if (t == chunk_end) {
+            if (t) HIPCHK(hipEventSynchronize(uploaded));
+            chunk_begin = t;
+            chunk_end = t + trows < K ? t + trows : K;
+            for (size_t tt = chunk_begin; tt < chunk_end; ++tt) {
+                const double* Ls = L_schedule + tt * Bz;
+                PhysF32* r32 = lay.p32(img, tt - chunk_begin);
+                PhysF64* r64 = lay.p64(img, tt - chunk_begin);
+                for (size_t b = 0; b < Bz; ++b) {
+                    if (Ls[b] != lastL[b]) {
+                        lastL[b] = Ls[b];
+                        if (twin[b] && lastL[b - 1] == Ls[b]) {
+                            last32[b] = last32[b - 1];
+                            last64[b] = last64[b - 1];
+                        } else {
+                            last32[b] = derive_f32(wp[b], Ls[b]);
+                            last64[b] = make_f64(wp[b], Ls[b]);
+                        }
+                    }
+                    r32[b] = last32[b];
+                    r64[b] = last64[b];
+                }
+            }
+            const size_t tn = chunk_end - chunk_begin;
+            HIPCHK(hipMemcpyAsync(tab, img, sizeof(PhysF32) * tn * Bz, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(tab + lay.o64, img + lay.o64, sizeof(PhysF64) * tn * Bz, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipEventRecord(uploaded, h->stream));
+        }
+        if (bn) {
+            const bool from_table = policy_mode == DW_POLICY_TABLE || (policy_mode != DW_POLICY_ZEROS && use_table && use_table[t]);
+            if (from_table) {
+                hipLaunchKernelGGL(actions_from_table, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, h->stream,
+                                   reinterpret_cast<const signed char*>(h->ep_buf.get() + o_tab + t * bn), (int)bn, h->action.get());
+                if (int rc = launch_policy_greedy(h, 0, nullptr, 1)) return rc;   // codes -1 / -2: greedy / anti-greedy
+            } else if (policy_mode == DW_POLICY_ZEROS) {
+                HIPCHK(hipMemsetAsync(h->action.get(), 0, sizeof(int) * bn, h->stream));
+            } else if (int rc = launch_policy_greedy(h, policy_mode == DW_POLICY_ARGMIN ? 1 : 0, nullptr, 0)) {
+                return rc;
+            }
+            HIPCHK(hipGetLastError());
+            if (int rc = launch_agents(h, h->action.get(), B, N)) return rc;
+        }
+        const size_t tr = t - chunk_begin;
+        if (int rc = launch_forward_pw(h, lay.p32(tab, tr), lay.p64(tab, tr), lay.fb(tab), sym, true)) return rc;
+        hipLaunchKernelGGL(episode_flags, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, h->stream, h->stats2[h->sp].get(),
+                           h->st.get(), B, N, threshold_k, h->ep_buf.get() + o_wa + t * Bz, h->ep_buf.get() + o_ok + t * bn);
+        HIPCHK(hipGetLastError());
+    }
+    if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * Bz, hipMemcpyDeviceToHost, h->stream));
+    if (agent_ok && bn) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    guard.disarm();
+    return DW_OK;
+}
+
+int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params* worlds, const double* L_schedule, int policy_mode,
+                            const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
+                            uint8_t* agent_ok) {
+    NEED(h && worlds && L_schedule, DW_EINVAL, "null argument");
+    NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
+    const dw_params& p = h->prm;
+    HIPCHK(hipSetDevice(p.device));
+    // every check before anything is launched or allocated: the rules of dw_run_episode, of the per-world schedules, and
+    // of dw_set_params for each world's set
+    if (int rc = check_episode_call(h, nsteps, policy_mode, use_table, table)) return rc;
+    const int C = p.height * p.width, N = p.n_agents, B = p.batch;
+    const size_t K = (size_t)nsteps, Bz = (size_t)B, bn = Bz * N;
+    if (int rc = check_luminosities(L_schedule, K, Bz)) return rc;
+    std::vector<dw_params> wp;
+    if (int rc = world_param_sets(p, worlds, Bz, wp)) return rc;
+    const std::vector<unsigned char> twin = twin_worlds(worlds, Bz);
+    if (!ensemble_episode_wave(h))
+        return run_episode_ensemble_stepwise(h, nsteps, wp, twin, worlds_symmetric(worlds, Bz) && !h->sw.no_sym, L_schedule, policy_mode,
+                                             use_table, table, threshold_k, world_alive, agent_ok);
+    const size_t lds = episode_wave_pw_shared_bytes() + episode_wave_pw_world_bytes(C, N) * 4;
+    NEED(lds <= 160 * 1024, DW_EINVAL, "too many agents for the LDS-resident episode kernel");
+    // The kernel keeps a world in LDS for a whole launch; a call is one launch unless its table of rows (136 B per step and
+    // world) would pass 32 MiB: then launches of `rows` steps (a multiple of the 64-step segment), each continuing from the
+    // planes and agents the one before it wrote back - the same states, step for step.
+    const size_t row_bytes = (sizeof(PhysF32) + sizeof(double)) * Bz;
+    size_t rows = ((size_t)32 << 20) / row_bytes / kEwSeg * kEwSeg;
+    rows = rows < (size_t)kEwSeg ? (size_t)kEwSeg : rows;
+    rows = rows > K ? K : rows;
+    // staging, device and page-locked image alike: [P32 rows*B][Ls rows*B] | [P64 B][use_table K][table K*B*N] |
+    // [world_alive K*B][agent_ok K*B*N]: the inputs of the first launch go up in ONE copy, a later launch's rows in one
+    // more, the flags of the whole call come back in one
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_p32 = 0, o_ls = up(o_p32 + sizeof(PhysF32) * rows * Bz), o_p64 = up(o_ls + sizeof(double) * rows * Bz);
+    const size_t o_ut = up(o_p64 + sizeof(PhysF64) * Bz), o_tab = up(o_ut + K), o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * Bz);
+    const size_t total = up(o_ok + K * bn);
+    if (int rc = ensure_ep_buf(h, total)) return rc;
+    if (int rc = reserve(h->ep_pinned, "the page-locked episode staging", total, (size_t)1 << 20)) return rc;
+    unsigned char* img = h->ep_pinned.get();
+    unsigned char* dev = h->ep_buf.get();
+    SyncOnExit guard(h->stream);                                // the image
+    PhysF64* p64 = reinterpret_cast<PhysF64*>(img + o_p64);
+    for (size_t b = 0; b < Bz; ++b) p64[b] = make_f64(wp[b], 0.0);          // (L: replaced by the step's, from the Ls rows)
+    if (use_table) std::memcpy(img + o_ut, use_table, K); else std::memset(img + o_ut, 0, K);
+    const bool have_table = table && bn;
+    if (have_table) std::memcpy(img + o_tab, table, K * bn);
+    EpisodeIO io;
+    const int cur = h->cur, prev = 1 - h->cur;
+    StatsDev* stats = h->stats2[h->sp].get();                   // (every world's whole record is assigned by the kernel)
+    io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
+    io.idx = h->idx.get(); io.st = h->st.get();
+    io.P32 = reinterpret_cast<const PhysF32*>(dev + o_p32);
+    io.Ls = reinterpret_cast<const double*>(dev + o_ls);
+    io.stats = stats;
+    io.fixups = &stats[B].sum_l;
+    io.action = (N > 0) ? h->action.get() : nullptr;
+    const bool ex = p.precision == DW_PRECISION_EXACT;
+    auto kern = ex ? episode_wave_pw<true> : episode_wave_pw<false>;
+    if (int rc = set_lds_limit(h, kern, lds)) return rc;
+    std::vector<double> lastL(Bz, -1.0);                        // a world whose luminosity did not change keeps its row
+    std::vector<PhysF32> last32(Bz);
+    PhysF32* r32 = reinterpret_cast<PhysF32*>(img + o_p32);
+    double* rls = reinterpret_cast<double*>(img + o_ls);
+    for (size_t t0 = 0; t0 < K; t0 += rows) {
+        const size_t kk = K - t0 < rows ? K - t0 : rows;
+        if (t0) HIPCHK(hipStreamSynchronize(h->stream));        // the image's rows are free again
+        for (size_t t = 0; t < kk; ++t) {
+            const double* Ls = L_schedule + (t0 + t) * Bz;
+            for (size_t b = 0; b < Bz; ++b) {
+                if (Ls[b] != lastL[b]) {
+                    lastL[b] = Ls[b];
+                    last32[b] = (twin[b] && lastL[b - 1] == Ls[b]) ? last32[b - 1] : derive_f32(wp[b], Ls[b]);
+                }
+                r32[t * Bz + b] = last32[b];
+            }
+            std::memcpy(rls + t * Bz, Ls, sizeof(double) * Bz);
+        }
+        const size_t upto = t0 ? o_ls + sizeof(double) * kk * Bz : (have_table ? o_tab + K * bn : o_ut + K);
+        HIPCHK(hipMemcpyAsync(dev, img, upto, hipMemcpyHostToDevice, h->stream));
+        io.use_table = use_table ? dev + o_ut + t0 : nullptr;
+        io.table = have_table ? reinterpret_cast<const signed char*>(dev + o_tab + t0 * bn) : nullptr;
+        io.world_alive = dev + o_wa + t0 * Bz;
+        io.agent_ok = dev + o_ok + t0 * bn;
+        const EpisodeWavePwArgs A{io, reinterpret_cast<const PhysF64*>(dev + o_p64), B, N, p.height, p.width, (int)kk, policy_mode,
+                                  p.obs_mask, threshold_k, p.agent_gamma};
+        hipLaunchKernelGGL(kern, dim3((unsigned)((B + 3) / 4)), dim3(256), lds, h->stream, A);
+        HIPCHK(hipGetLastError());
+        h->unq = OWN_NONE;                                      // the handle as after dw_step_n_trace_ensemble: per-world in
+        h->stepped = true;                                      // both senses, luminosity and constants
+        h->L_last = 0.0;
+        h->L_per_world = true;
+        h->P_per_world = true;
+    }
+    release_unquantised(h);
+    const bool want_ok = agent_ok && bn;
+    if (world_alive || want_ok) {
+        const size_t lo = world_alive ? o_wa : o_ok, hi = want_ok ? o_ok + K * bn : o_wa + K * Bz;
+        HIPCHK(hipMemcpyAsync(img + lo, dev + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));                    // flags are returned
+    guard.disarm();
+    if (world_alive) std::memcpy(world_alive, img + o_wa, K * Bz);
+    if (want_ok) std::memcpy(agent_ok, img + o_ok, K * bn);
     return DW_OK;
 }
 
@@ -2488,6 +2713,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
         static const char* const form_name[] = {"launches per step", "workgroup (LDS)", "one wave per world"};   // by EpisodeForm
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, "; episode: %s; mlp episode: %s", form_name[episode_form(h)], form_name[episode_mlp_form(h)]);
+    }
+    {                                                           // the form dw_run_episode_ensemble takes
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; ensemble episode: %s", ensemble_episode_wave(h) ? "one wave per world" : "launches per step");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

@@ -421,6 +421,32 @@ class Engine:
             _ffi.ptr_u8(ok) if self.N else None))
         return (None if alive is None else alive.view(np.bool_)), ok.view(np.bool_)
 
+    def run_episode_ensemble(self, worlds, Ls, mode, use_table=None, table=None, threshold_k=5):
+        """`run_episode` with the physics constants `worlds[b]` (as `step_n_trace_ensemble` takes them) and the luminosity
+        column `Ls[:, b]` of world b (`dw_run_episode_ensemble`): `Ls` is (K, B).  Each world ends, and reports the flags,
+        exactly as a one-world engine with those constants, that column and slice `[:, b]` of the table would after
+        `run_episode`.  Returns (world_alive (K,B) bool, agent_ok (K,B,N) bool).  The engine's own params are unchanged;
+        afterwards it is "per-world" as after `step_n_trace_ensemble`: `download_grid`, `get_obs`, `download_caches` and
+        `reduce_temperature` raise until a shared-L step or an upload."""
+        tab = self._world_table(worlds)
+        L = np.ascontiguousarray(Ls, dtype=np.float64)
+        if L.ndim != 2 or L.shape[1] != self.B:
+            raise ValueError(f"per-world luminosities need shape (K, {self.B}), got {L.shape}")
+        K = L.shape[0]
+        ut = None if use_table is None else np.ascontiguousarray(use_table, dtype=np.uint8)
+        tb = None if table is None else np.ascontiguousarray(table, dtype=np.int8)
+        if ut is not None and ut.shape != (K,):
+            raise ValueError("use_table must have shape (K,)")
+        if tb is not None and tb.shape != (K, self.B, self.N):
+            raise ValueError(f"table must have shape {(K, self.B, self.N)}")
+        alive = np.empty((K, self.B), dtype=np.uint8)
+        ok = np.empty((K, self.B, self.N), dtype=np.uint8)
+        self._check(self._lib.dw_run_episode_ensemble(
+            self._h, K, tab.ctypes.data_as(C.POINTER(_ffi.DwWorldParams)), _ffi.ptr_d(L), int(mode), _ffi.ptr_u8(ut),
+            None if tb is None else tb.ctypes.data_as(C.POINTER(C.c_int8)), int(threshold_k), _ffi.ptr_u8(alive),
+            _ffi.ptr_u8(ok) if self.N else None))
+        return alive.view(np.bool_), ok.view(np.bool_)
+
     def run_episode_mlp(self, L_schedule, params, member_a=None, member_b=None, split=None, L_init=0.75,
                         reuse_buffers=False, n_members=None):
         """K device-resident steps with MLP policies: agents [0, split) of world b use parameter set

@@ -378,6 +378,132 @@ def simulate_parameter_sweep(env, params, nsteps, L_values=None, obs=None, tempe
     return out
 
 
+def _sweep_param_table(env, scenarios, worlds_per_scenario):
+    """The (S * Bs,) table of dtype `_ffi.WORLD_PARAMS_DTYPE` of a scenario list: scenario s owns the contiguous block of
+    worlds [s * Bs, (s + 1) * Bs); a member its `params` does not name keeps the environment's attribute."""
+    Bs = int(worlds_per_scenario)
+    table = np.zeros(len(scenarios) * Bs, dtype=_ffi.WORLD_PARAMS_DTYPE)
+    for s, sc in enumerate(scenarios):
+        params = sc.get("params") or {}
+        unknown = sorted(set(params) - set(_ffi.WORLD_PARAM_NAMES))
+        if unknown:
+            raise ValueError(f"scenario {s}: not a per-world constant: {unknown} (one of {_ffi.WORLD_PARAM_NAMES})")
+        for name in _ffi.WORLD_PARAM_NAMES:
+            value = np.asarray(params.get(name, getattr(env, name)), dtype=np.float64)
+            if value.shape not in ((), (Bs,)):
+                raise ValueError(f"scenario {s}: params[{name!r}] needs a scalar or shape ({Bs},), got {value.shape}")
+            table[name][s * Bs:(s + 1) * Bs] = value
+    return table
+
+
+def _sweep_action_table(scenarios, running, K, Bs, N):
+    """The (K, S * Bs, N) int8 action table of one chunk, filled per block: -1 / -2 for the worlds of a greedy /
+    anti-greedy scenario (the device takes that agent's choice), 0 for `agent=None` (ref step(None): action 0), and on a
+    step at which an epsilon-greedy scenario's coin takes the random branch, that block's host-drawn codes 0..8.  The
+    draws come from `np.random` in this order: step-major, within a step scenario-major, for each scenario with
+    epsilon > 0 that is still running one `rand()` and, on the random branch, one `randint(9)` for the block
+    (`Greedy.draw_branch` / `draw_random_actions`); a scenario with epsilon = 0, or one that has ended, draws nothing."""
+    S = len(scenarios)
+    table = np.zeros((K, S * Bs, N), dtype=np.int8)
+    drawing = []
+    for s, sc in enumerate(scenarios):
+        agent = sc.get("agent")
+        if agent is not None:
+            table[:, s * Bs:(s + 1) * Bs] = -1 if agent.greedy else -2
+            if agent.epsilon > 0.0 and running[s]:
+                drawing.append((s, agent))
+    for t in range(K if drawing else 0):
+        for s, agent in drawing:
+            if not agent.draw_branch():
+                table[t, s * Bs:(s + 1) * Bs] = agent.draw_random_actions(Bs, N)[..., 0]
+    return table
+
+
+def _sweep_account(done_at, agents_done_at, running, alive_k, ok_k):
+    """The notebook's counting and stopping rule (cell 2:46-57) applied per scenario to the flags of a chunk: alive_k
+    (K, S * Bs) and ok_k (K, S * Bs, N) are added to done_at (S, Bs) and agents_done_at (S, Bs, N, 1) for the steps up to
+    and including the one at which all of the SCENARIO's worlds are dead; from then on the scenario's counts are frozen
+    (`running[s]` False, in place), whatever its worlds do while the other scenarios finish."""
+    S, Bs = done_at.shape
+    K = alive_k.shape[0]
+    alive = np.asarray(alive_k, dtype=bool).reshape(K, S, Bs)
+    all_dead = ~alive.any(axis=2)                                                  # (K, S)
+    earlier = np.zeros((K, S), dtype=bool)
+    earlier[1:] = np.logical_or.accumulate(all_dead, axis=0)[:-1]
+    counted = running[None, :] & ~earlier                                          # the scenario still counts step t
+    done_at += np.count_nonzero(alive & counted[:, :, None], axis=0)
+    if agents_done_at.size:
+        ok = np.asarray(ok_k, dtype=bool).reshape(K, S, Bs, -1)
+        agents_done_at += np.count_nonzero(ok & counted[:, :, None, None], axis=0)[..., None]
+    running &= ~all_dead.any(axis=0)
+
+
+def simulate_lifespan_sweep(env, scenarios, worlds_per_scenario, chunk=32, obs=None):
+    """The reference's lifespan table (notebooks/greedy_longevity_abatement.ipynb: policies x albedo settings, each an
+    ensemble run until every biosphere is dead) - or a lifespan-versus-q2 / gamma / temp_optimal scan - as ONE
+    device-resident run instead of one `reset()`, one configuration and one `simulate_lifespan` per scenario.
+
+    `scenarios` is a list of `{"params": {member: value}, "agent": Greedy | None}`: `params` names members of
+    `_ffi.WORLD_PARAM_NAMES` (a scalar, or one value per world of the block; members not named keep the environment's
+    attribute), `agent` is a `Greedy` in any of its modes or None (ref step(None): action 0).  Scenario s owns the
+    contiguous block of worlds [s * worlds_per_scenario, (s + 1) * worlds_per_scenario), and
+    `env.batch_size == len(scenarios) * worlds_per_scenario`.  Every world follows the environment's own luminosity
+    ramp; `agent_gamma`, the observation mask and the initial-state fields are the environment's and shared.
+    `obs=None`: reset the environment first; or pass the observations of a reset already done (`reset_synthetic`).
+
+    The first step starts from the un-quantised state: the policies' actions from the reset observations (block by
+    block), `dw_update_agents`, one step of `dw_step_n_trace_ensemble`, `dw_get_reward_done`.  Then chunks of `chunk`
+    steps of `dw_run_episode_ensemble` with the action table filled per block (`_sweep_action_table`).  A scenario's
+    counts stop at the step at which all of ITS worlds are dead (the notebook's rule, per scenario); the run ends when
+    every scenario has ended.
+
+    Returns `(done_at (S, Bs), agents_done_at (S, Bs, N, 1), params)`, `params` the (S * Bs,) table of constants the run
+    used.  A scenario with epsilon = 0 (or no agent) gets exactly the counts `simulate_lifespan` gives for its block of
+    worlds with those constants set on the environment; a scenario with epsilon > 0 draws from `np.random` in the order
+    `_sweep_action_table` documents, not in the order of a separate run: statistically equivalent, not bit-equal.
+    The caller gets lifespans only: the worlds stop at the end of the last chunk and have no common luminosity or
+    constants, so `env.step()` and `env.grid` raise until `env.reset()` (as `simulate_lifespan(final_state=False)`
+    leaves an environment that is of no further use)."""
+    S, Bs = len(scenarios), int(worlds_per_scenario)
+    if S < 1 or Bs < 1 or int(env.batch_size) != S * Bs:
+        raise ValueError(f"env.batch_size ({int(env.batch_size)}) must be len(scenarios) * worlds_per_scenario ({S} * {Bs})")
+    for s, sc in enumerate(scenarios):
+        if sc.get("agent") is not None and type(sc["agent"]) is not Greedy:
+            raise ValueError(f"scenario {s}: the agent must be a Greedy or None")
+    if env.precision == "f64" or env.collision_mode != 0:
+        raise ValueError("simulate_lifespan_sweep runs device-resident: precision 'exact' or 'fast', collision_mode 0")
+    table = _sweep_param_table(env, scenarios, Bs)
+    if obs is None:
+        obs = env.reset()
+    B, N = S * Bs, int(env.n_agents)
+    done_at = np.zeros((S, Bs), dtype=int)
+    agents_done_at = np.zeros((S, Bs, N, 1), dtype=int)
+    running = np.ones(S, dtype=bool)
+    eng = env._ensure_engine()
+    env._sync_to_device()
+    # step 1: the initial state is not quantised (ref initialize_grid)
+    if N:
+        action = np.zeros((B, N, 1), dtype=np.int64)
+        for s, sc in enumerate(scenarios):
+            if sc.get("agent") is not None:
+                action[s * Bs:(s + 1) * Bs] = sc["agent"](obs[s * Bs:(s + 1) * Bs])
+        eng.update_agents(action)
+    L1 = np.full((1, B), _luminosity_schedule(env, 1)[0], dtype=np.float64)
+    stats = eng.step_n_trace_ensemble(table, L1)
+    _, done = eng.reward_done()
+    _advance_host_scalars(env, 1)
+    env._per_world_L = True
+    _sweep_account(done_at, agents_done_at, running, stats["max_k"] > LIFESPAN_THRESHOLD_K, ~done[None, ..., 0])
+    K = int(chunk)
+    while running.any():
+        Ls = np.repeat(np.asarray(_luminosity_schedule(env, K), dtype=np.float64)[:, None], B, axis=1)
+        actions = _sweep_action_table(scenarios, running, K, Bs, N)
+        alive_k, ok_k = eng.run_episode_ensemble(table, Ls, _ffi.POLICY_TABLE, None, actions, LIFESPAN_THRESHOLD_K)
+        _sweep_account(done_at, agents_done_at, running, alive_k, ok_k)
+        _advance_host_scalars(env, K)
+    return done_at, agents_done_at, table
+
+
 def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_chunk):
     """The step loop shared by the two fitness harnesses: chunks of steps device-resident
     (``dw_run_episode_mlp``), the reference's per-step float64 bookkeeping done by `after_chunk(rewards,
