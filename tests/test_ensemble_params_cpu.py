@@ -131,7 +131,7 @@ def test_a_worlds_constants_are_those_of_params_that_carry_its_members(driver_ou
     for fn in ("PhysF32 derive_f32(", "void derive_f32_pair(", "PhysF64 make_f64(", "FirstStepBound derive_first_bound("):
         assert sources.count("inline " + fn) == 1, fn
     api = open(os.path.join(CSRC, "dw_api.hip")).read()
-    assert "with_world_params(p, worlds[b])" in api and "worlds_symmetric(worlds, B)" in api
+    assert "with_world_params(p, worlds[b])" in sources and "worlds_symmetric(worlds, B)" in api
 
 
 def test_the_sym_decision_is_call_wide(driver_output):

@@ -163,6 +163,12 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint64)
 
 
+def _hold_rows(monkeypatch, trace_rows):
+    """Handles created from now on hold `trace_rows` rows of the series (and of the tables) on the device at a time."""
+    monkeypatch.setenv("DW_TEST_HOOKS", "1")
+    monkeypatch.setenv("DW_TEST_TRACE_ROWS", trace_rows)
+
+
 @pytest.mark.parametrize("trace_rows", [None, "4"], ids=["one-chunk", "rows=4"])
 @pytest.mark.parametrize("precision", ("exact", "fast"))
 @pytest.mark.parametrize("B,H,W", SHAPES)
@@ -172,8 +178,7 @@ def test_own_constants_are_the_per_world_luminosity_run(amd, monkeypatch, B, H, 
     of the series (and of the tables) on the device at a time."""
     from therldaisyworld_amd import _ffi
     if trace_rows:
-        monkeypatch.setenv("DW_TEST_HOOKS", "1")
-        monkeypatch.setenv("DW_TEST_TRACE_ROWS", trace_rows)
+        _hold_rows(monkeypatch, trace_rows)
     L = _schedule(13, B)
     what = f"{(B, H, W)} {precision}"
     for temperature in (False, True):
@@ -200,6 +205,48 @@ def test_own_constants_are_the_per_world_luminosity_run(amd, monkeypatch, B, H, 
         assert a.step_n_trace_ensemble(tab, L[:3], trace=False) is None
         a.close()
         b.close()
+
+
+@pytest.mark.parametrize("how", ["philox_q", "philox"])
+def test_chunks_of_the_table_and_of_the_series_drift_apart(amd, monkeypatch, how):
+    """The rows=4 run of the test above on the smallest shape that takes step pairs, 11 steps, constant luminosities for
+    steps 0-4 and distinct ones afterwards: steps at equal luminosities share a table row, so the chunks of the table
+    (4 single-step rows, 2 pair rows) end elsewhere than those of the series (4 rows).  Trace and planes equal the one-chunk
+    run's bit for bit, with the mixed table and with the handle's own set in every row; the latter with equal columns is
+    dw_step_n_trace."""
+    from therldaisyworld_amd import _ffi
+    shapes = []
+    for shape in sorted(SHAPES, key=lambda s: s[0] * s[1] * s[2]):
+        probe = _engine(amd, *shape, "fast")
+        if probe.kernel_info().endswith("; per-world constants: step pairs"):
+            shapes.append(shape)
+        probe.close()
+    B, H, W = shapes[0]
+    L = _schedule(11, B)
+    L[:5] = L[0]
+    assert len({row.tobytes() for row in L}) == 7
+    shared = np.repeat(L[:, :1], B, axis=1)
+    whole = [_engine(amd, B, H, W, "fast") for _ in range(3)]          # mixed table | own set | dw_step_n_trace
+    _hold_rows(monkeypatch, "4")
+    chunked = [_engine(amd, B, H, W, "fast") for _ in range(3)]
+    assert all("DW_TEST_TRACE_ROWS=4" in e.kernel_info() for e in chunked)
+    assert not any("DW_TEST_TRACE_ROWS" in e.kernel_info() for e in whole)
+    for e in whole + chunked:
+        _init(e, how, 11)
+    own = np.repeat(whole[0].world_params()[None], B)
+    traces = [[e[0].step_n_trace_ensemble(_table(e[0], B, 1), L), e[1].step_n_trace_ensemble(own, shared),
+               e[2].step_n_trace(shared[:, 0])] for e in (whole, chunked)]
+    for i, what in enumerate(("mixed table", "own set", "dw_step_n_trace")):
+        _assert_rows_equal(traces[1][i], traces[0][i], f"{what}: rows=4 against one chunk")
+        for which in (_ffi.STATE_CURRENT, _ffi.STATE_PREVIOUS):
+            for x, y in zip(chunked[i].download_planes(which), whole[i].download_planes(which)):
+                assert np.array_equal(x, y), (what, which)
+    for run, engines in zip(traces, (whole, chunked)):
+        _assert_rows_equal(run[1], run[2], "own set, equal columns: dw_step_n_trace")
+        for x, y in zip(engines[1].download_planes(), engines[2].download_planes()):
+            assert np.array_equal(x, y)
+    for e in whole + chunked:
+        e.close()
 
 
 def _k(x):

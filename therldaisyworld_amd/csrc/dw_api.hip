@@ -20,6 +20,7 @@
 #include "dw_kernels.hpp"
 #include "dw_host_util.hpp"
 #include "dw_plan.hpp"
+#include "dw_series.hpp"
 
 using namespace dw;
 
@@ -478,6 +479,16 @@ static void step_done(dw_handle* h, double L, bool stepped, bool per_world = fal
     release_unquantised(h);
 }
 
+// An episode kernel stepped the current buffer in place and left the state before its last step in the other one: a
+// forward() pair at L_last, or (`per_world`: episode_wave_pw) per-world in both senses, as after dw_step_n_trace_ensemble.
+static void episode_done(dw_handle* h, double L_last, bool per_world) {
+    h->unq = OWN_NONE;
+    h->stepped = true;
+    h->L_last = per_world ? 0.0 : L_last;
+    h->L_per_world = per_world;
+    h->P_per_world = per_world;
+}
+
 // forward(): cur -> other buffer, swap.  Assumes agents were already updated.
 static int launch_forward(dw_handle* h, double L) {
     const dw_params& p = h->prm;
@@ -507,25 +518,6 @@ static int launch_forward(dw_handle* h, double L) {
 }
 
 // ---- per-world luminosities and constants (dw_step_n_trace_per_world, dw_step_n_trace_ensemble) ----------------------
-// The constants of a chunk of steps: [rows][B] PhysF32 | [rows][B] PhysF64 | [B] FirstStepBound (the first step of a
-// call from an un-quantised state in the exact mode; otherwise unused) | [prows][B] PairPw (the step pairs of
-// dw_step_n_trace_ensemble, dw_step_fused_pw.hpp; otherwise none).  One device buffer, one page-locked image, one
-// upload per chunk; a launch gets the addresses of its row.
-struct PwLayout {
-    size_t B, rows, prows, o64, ofb, opair, bytes;
-    PwLayout(size_t B_, size_t rows_, size_t prows_ = 0) : B(B_), rows(rows_), prows(prows_) {
-        o64 = sizeof(PhysF32) * rows * B;
-        ofb = o64 + sizeof(PhysF64) * rows * B;
-        opair = ofb + sizeof(FirstStepBound) * B;
-        bytes = opair + sizeof(PairPw) * prows * B;
-    }
-    PairPw* pair(unsigned char* base, size_t row) const { return reinterpret_cast<PairPw*>(base + opair) + row * B; }
-    // row `row` of each part of the table that starts at `base` (the device buffer or its host image)
-    PhysF32* p32(unsigned char* base, size_t row) const { return reinterpret_cast<PhysF32*>(base) + row * B; }
-    PhysF64* p64(unsigned char* base, size_t row) const { return reinterpret_cast<PhysF64*>(base + o64) + row * B; }
-    FirstStepBound* fb(unsigned char* base) const { return reinterpret_cast<FirstStepBound*>(base + ofb); }
-};
-
 // One step, world b with the constants row32[b] / row64[b] (device addresses): the first step from an un-quantised state
 // and every shape the per-world wave-strip kernels do not take by step_generic_pw.
 // `sym`: the albedo-symmetric form of the exact wave-strip kernel (every world's set is symmetric); `constants`: the rows
@@ -1239,71 +1231,20 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
     return DW_OK;
 }
 
-int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace) {
-    NEED(h && L_schedule && trace, DW_EINVAL, "null argument");
-    NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
-    if (nsteps == 0) return DW_OK;
-    NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
-    static_assert(sizeof(dw_world_stats) == sizeof(StatsDev), "stats layout");
-    HIPCHK(hipSetDevice(h->prm.device));
-    const size_t B = (size_t)h->prm.batch, row_bytes = sizeof(StatsDev) * B;
-    // rows of the series held on the device at a time: the whole run up to 32 MiB (512 steps of 1024 worlds: 12 MiB),
-    // longer runs in chunks of that size (an even number of rows, at least two: a step pair fills two);
-    // DW_TEST_TRACE_ROWS: that many rows instead (tests: runs of several chunks with a handful of worlds)
-    size_t rows = (h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / row_bytes) & ~(size_t)1;
-    rows = rows < 2 ? 2 : rows;
-    rows = rows > (size_t)nsteps ? (size_t)nsteps : rows;
-    if (int rc = alloc_group(h, "the trace buffer", {{h->trace_d, rows * row_bytes}})) return rc;
-    SyncOnExit sync(h->stream);                                 // the downloads below fill the caller's array
-    h->fused_launches = 0;
-    bool first_pair = true;
-    for (int c0 = 0; c0 < nsteps; c0 += (int)rows) {
-        const int cn = nsteps - c0 < (int)rows ? nsteps - c0 : (int)rows;
-        HIPCHK(hipMemsetAsync(h->trace_d.get(), 0, (size_t)cn * row_bytes, h->stream));
-        for (int t = c0; t < c0 + cn;) {
-            StatsDev* row = h->trace_d.get() + (size_t)(t - c0) * B;
-            // a pair where dw_step_n would issue one (the closing one or two steps stay ordinary launches: the retained
-            // previous state is the true predecessor) and both rows lie in this chunk
-            if (h->plan.trace_pairs && cur_quantised(h) && nsteps - t >= 3 && t + 2 <= c0 + cn) {
-                if (first_pair) {
-                    drop_unquantised_previous(h);
-                    first_pair = false;
-                }
-                if (int rc = launch_forward_fused2(h, L_schedule[t], L_schedule[t + 1], nullptr, 0.f, row)) return rc;
-                t += 2;
-            } else {
-                if (int rc = launch_forward(h, L_schedule[t])) return rc;
-                HIPCHK(hipMemcpyAsync(row, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
-                t += 1;
-            }
-        }
-        HIPCHK(hipMemcpyAsync(trace + (size_t)c0 * B, h->trace_d.get(), (size_t)cn * row_bytes, hipMemcpyDeviceToHost,
-                              h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    sync.disarm();
-    return DW_OK;
-}
-
+// ---- the step series: dw_step_n_trace and its temperature, per-world and ensemble forms -----------------------------
 // dw_step_n_trace_ensemble takes step pairs (trace_pair_fast_pw) on the plans dw_step_n_trace does, in the float32-only
 // mode; the exact pair kernel does not keep its row loop with constants from a table (dw_step_fused_pw.hpp)
 static bool ensemble_pairs(const dw_handle* h) { return h->plan.trace_pairs && h->prm.precision == DW_PRECISION_FAST; }
 
-// What the per-world calls check of their schedule before anything is launched or allocated
-static int check_luminosities(const double* L_schedule, size_t nsteps, size_t B) {
+// What the per-world calls check before anything is launched or allocated: their schedule, and their worlds - a world's
+// params as `rows` derives from them, the handle's with the world's members (check_params refuses among those only g:
+// g < 0 in the float32 precisions)
+static int check_per_world(const WorldRows& rows, const dw_world_params* worlds, const double* L_schedule, size_t nsteps, size_t B) {
     for (size_t i = 0; i < nsteps * B; ++i)
         NEED(std::isfinite(L_schedule[i]) && L_schedule[i] >= 0.0, DW_EINVAL,
              "L_schedule[step %zu][world %zu] = %g: a luminosity is finite and not negative", i / B, i % B, L_schedule[i]);
-    return DW_OK;
-}
-
-// A world's params: the handle's with the world's members (check_params refuses among those only g: g < 0 in the float32
-// precisions).  wp: one set per world, or the handle's alone without `worlds`.
-static int world_param_sets(const dw_params& p, const dw_world_params* worlds, size_t B, std::vector<dw_params>& wp) {
-    wp.assign(worlds ? B : 1, p);
     for (size_t b = 0; worlds && b < B; ++b) {
-        wp[b] = with_world_params(p, worlds[b]);
-        if (check_params(&wp[b]) != DW_OK) {
+        if (check_params(&rows.params(b)) != DW_OK) {
             char why[sizeof(g_err)];
             snprintf(why, sizeof(why), "%s", g_err);
             return fail(DW_EINVAL, "worlds[%zu].g = %g: %s", b, worlds[b].g, why);
@@ -1312,186 +1253,153 @@ static int world_param_sets(const dw_params& p, const dw_world_params* worlds, s
     return DW_OK;
 }
 
-// dw_step_n_trace_per_world, the per-world form of dw_step_n_trace_temperature (`temps` != null: the temperature
-// records of every step, reduced from the step's input planes at the step's row of the table) and
-// dw_step_n_trace_ensemble (`worlds` != null: world b derives its rows from the handle's params with worlds[b]'s members;
-// `ensemble`: the step pairs of dw_step_n_trace where its plan takes them, and the handle remembers that the constants
-// were per-world).
-static int trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace, dw_temp_stats* temps,
-                           const dw_world_params* worlds = nullptr, bool ensemble = false) {
-    NEED(h && L_schedule && (worlds || !ensemble), DW_EINVAL, "null argument");
+// The device side of the per-world table (PwLayout): the handle's buffer and its page-locked image, and the event after
+// which the image may be written again.
+struct PwTable {
+    dw_handle* h;
+    const PwLayout lay;
+    hipEvent_t uploaded = nullptr;
+    bool in_flight = false;
+    PwTable(dw_handle* h_, const PwLayout& lay_) : h(h_), lay(lay_) {}
+    PwTable(const PwTable&) = delete;
+    ~PwTable() { if (uploaded) (void)hipEventDestroy(uploaded); }
+    unsigned char* img() const { return h->pw_pinned.get(); }
+    unsigned char* dev() const { return h->pw_tab.get(); }
+    GroupItem<DeviceMem> item() const { return {h->pw_tab, lay.bytes}; }
+    // `group`: item() and what the call uses with the table, all or nothing; then the image
+    int alloc(const char* what, std::initializer_list<GroupItem<DeviceMem>> group) {
+        if (int rc = alloc_group(h, what, group)) return rc;
+        if (int rc = reserve(h->pw_pinned, "the page-locked image of the per-world constants", lay.bytes)) {
+            h->pw_tab.reset();
+            return rc;
+        }
+        HIPCHK(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
+        return DW_OK;
+    }
+    // chunk c of a schedule: derived in float64 into the image once it is free; the rows in use of each part go up in one
+    // copy each (`first_bound`: row 0 of the first chunk is step 0, from an un-quantised state in the exact mode)
+    int next_chunk(const SeriesSchedule& q, size_t c, const double* Ls, WorldRows& worlds, bool first_bound = false) {
+        if (in_flight) HIPCHK(hipEventSynchronize(uploaded));
+        fill_chunk(q, c, Ls, worlds, lay, img());
+        if (first_bound) worlds.first_bound(Ls, lay.p32(img(), 0), h->unq_kind == UNQ_F64, h->sw.first_slack, lay.fb(img()));
+        auto part = [&](size_t off, size_t bytes) { return hipMemcpyAsync(dev() + off, img() + off, bytes, hipMemcpyHostToDevice, h->stream); };
+        const size_t singles = q.chunks[c].singles, pairs = q.chunks[c].pairs;
+        if (singles) {
+            HIPCHK(part(0, sizeof(PhysF32) * singles * lay.B));
+            HIPCHK(part(lay.o64, sizeof(PhysF64) * singles * lay.B));
+        }
+        if (first_bound) HIPCHK(part(lay.ofb, sizeof(FirstStepBound) * lay.B));
+        if (pairs) HIPCHK(part(lay.opair, sizeof(PairPw) * pairs * lay.B));
+        HIPCHK(hipEventRecord(uploaded, h->stream));
+        in_flight = true;
+        return DW_OK;
+    }
+};
+
+// One series call in flight.  The constants of its steps have two sources: the handle's own at the shared luminosity
+// Ls[t], or (`table`) rows of the per-world table derived from Ls[t][B].
+struct SeriesRun {
+    dw_handle* h;
+    const SeriesSchedule& q;
+    const double* Ls;
+    dw_world_stats* trace;            // what the caller wants of each series (either may be null)
+    dw_temp_stats* temps;
+    PwTable* table;
+    bool sym, constants;              // (table) what launch_forward_pw takes besides its rows
+    size_t B, row_bytes, trow_bytes;
+    bool first_pair = true;
+    // the reductions of every step go to a row of trace_d: a series is wanted, or pair kernels add theirs there
+    bool keep_rows() const { return trace || q.even; }
+
+    int alloc() {
+        const GroupItem<DeviceMem> tr{h->trace_d, keep_rows() ? q.rows * row_bytes : 0}, part{h->temp_part, temp_part_bytes(h)},
+            td{h->temp_d, q.rows * trow_bytes};
+        if (!table) return temps ? alloc_group(h, "the trace buffer and the temperature reduction", {tr, part, td})
+                                 : alloc_group(h, "the trace buffer", {tr});
+        if (temps) return table->alloc("the per-world constants, the trace buffer and the temperature reduction", {table->item(), tr, part, td});
+        return keep_rows() ? table->alloc("the per-world constants and the trace buffer", {table->item(), tr})
+                           : table->alloc("the per-world constants", {table->item()});
+    }
+    // step t, or the pair that starts there; the field a step computes is reduced from its input planes, in front of it
+    int step(int t) {
+        const size_t sr = (size_t)t % q.rows, tr = table ? q.row_of[(size_t)t] : 0;
+        StatsDev* row = keep_rows() ? h->trace_d.get() + sr * B : nullptr;
+        unsigned char* tab = table ? table->dev() : nullptr;
+        if (q.is_pair[(size_t)t]) {
+            if (first_pair) drop_unquantised_previous(h);
+            first_pair = false;
+            return table ? launch_forward_fused2_pw(h, table->lay.pair(tab, tr), row)
+                         : launch_forward_fused2(h, Ls[t], Ls[t + 1], nullptr, 0.f, row);
+        }
+        const PhysF64* r64 = table ? table->lay.p64(tab, tr) : nullptr;
+        if (temps)
+            if (int rc = launch_temp_moments(h, true, table ? 0.0 : Ls[t], r64, h->temp_d.get() + sr * B)) return rc;
+        if (int rc = table ? launch_forward_pw(h, table->lay.p32(tab, tr), r64, table->lay.fb(tab), sym, constants)
+                           : launch_forward(h, Ls[t])) return rc;
+        if (row) HIPCHK(hipMemcpyAsync(row, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
+        return DW_OK;
+    }
+    int run(WorldRows* worlds) {
+        const int nsteps = (int)q.is_pair.size();
+        const bool first_bound = h->unq == OWN_CUR && h->plan.first_prec == 3;
+        size_t c = 0;                                           // the table chunk that starts next
+        for (int t = 0; t < nsteps; t += q.took(t)) {
+            const size_t sr = (size_t)t % q.rows, left = (size_t)(nsteps - t), filled = sr + (size_t)q.took(t);
+            if (table && t == (c ? q.chunks[c - 1].end : 0)) {
+                if (int rc = table->next_chunk(q, c, Ls, *worlds, c == 0 && first_bound)) return rc;
+                ++c;
+            }
+            if (q.even && sr == 0)                              // the pair kernels ADD their reductions into the rows
+                HIPCHK(hipMemsetAsync(h->trace_d.get(), 0, (left < q.rows ? left : q.rows) * row_bytes, h->stream));
+            if (int rc = step(t)) return rc;
+            if (filled != q.rows && t + q.took(t) != nsteps) continue;
+            const size_t r0 = ((size_t)t - sr) * B;             // the chunk of the series is full or the run is over
+            if (temps) HIPCHK(hipMemcpyAsync(temps + r0, h->temp_d.get(), filled * trow_bytes, hipMemcpyDeviceToHost, h->stream));
+            if (trace) HIPCHK(hipMemcpyAsync(trace + r0, h->trace_d.get(), filled * row_bytes, hipMemcpyDeviceToHost, h->stream));
+        }
+        return DW_OK;
+    }
+};
+
+// The five dw_step_n_trace* calls after their null checks.  The per-world forms take L_schedule[nsteps][B], world b's rows
+// from the handle's params with worlds[b]'s members when there are `worlds`; after PER_WORLD_CONSTANTS the handle remembers
+// that the constants were per-world.  `always_even`, `may_pair`: plan_series.
+enum SeriesForm { SHARED_L, PER_WORLD_L, PER_WORLD_CONSTANTS };
+static int run_series(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace, dw_temp_stats* temps,
+                      bool always_even, bool may_pair, SeriesForm form = SHARED_L, const dw_world_params* worlds = nullptr) {
+    const bool pw = form != SHARED_L;
     NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
     if (nsteps == 0) return DW_OK;
     NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
     static_assert(sizeof(dw_world_stats) == sizeof(StatsDev), "stats layout");
+    static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev), "temperature record layout");
     const dw_params& p = h->prm;
-    const size_t B = (size_t)p.batch, row_bytes = sizeof(StatsDev) * B;
-    if (int rc = check_luminosities(L_schedule, (size_t)nsteps, B)) return rc;
-    std::vector<dw_params> wp;
-    if (int rc = world_param_sets(p, worlds, B, wp)) return rc;
-    auto params_of = [&](size_t b) -> const dw_params& { return wp[worlds ? b : 0]; };
+    const size_t B = (size_t)p.batch;
+    std::unique_ptr<WorldRows> rows(pw ? new WorldRows(p, worlds, B) : nullptr);
+    if (int rc = pw ? check_per_world(*rows, worlds, L_schedule, (size_t)nsteps, B) : DW_OK) return rc;
     const bool sym = worlds ? worlds_symmetric(worlds, B) && !h->sw.no_sym : h->plan.sym_albedo;
     HIPCHK(hipSetDevice(p.device));
-    // step pairs (dw_step_n_trace_ensemble without temperature records, float32-only plans with trace_pairs): where
-    // dw_step_n_trace issues one - from a quantised state, never the closing one or two steps, both rows in one chunk of
-    // the series
-    const bool pairs = ensemble && !temps && ensemble_pairs(h);
-    // rows of the series on the device at a time: as dw_step_n_trace (single steps: any number of rows will do; pairs: an
-    // even number, at least two; with temperature records, 32 MiB of those)
-    const size_t trow_bytes = sizeof(TempStatsDev) * B;
-    size_t rows = h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / (temps ? trow_bytes : row_bytes);
-    if (pairs) rows = (rows & ~(size_t)1) < 2 ? 2 : (rows & ~(size_t)1);
-    rows = rows < 1 ? 1 : (rows > (size_t)nsteps ? (size_t)nsteps : rows);
-    std::vector<unsigned char> is_pair(pairs ? (size_t)nsteps : 0, 0);
-    size_t npairs = 0;
-    if (pairs) {
-        bool quantised = cur_quantised(h);
-        for (int t = 0; t < nsteps;) {
-            if (quantised && nsteps - t >= 3 && (size_t)t % rows + 2 <= rows) { is_pair[t] = 1; ++npairs; t += 2; }
-            else { quantised = true; t += 1; }
-        }
-    }
-    // rows of the table: 8 MiB of single-step constants (256 B per step and world) and, with pairs, 8 MiB of theirs (256 B
-    // per pair and world); under the test hook as many as trace rows hold
-    size_t trows = ((size_t)8 << 20) / ((sizeof(PhysF32) + sizeof(PhysF64)) * B);
-    if (h->sw.trace_rows >= 1 && trows > (size_t)h->sw.trace_rows) trows = (size_t)h->sw.trace_rows;
-    trows = trows < 1 ? 1 : (trows > (size_t)nsteps ? (size_t)nsteps : trows);
-    size_t prows = 0;
-    if (npairs) {
-        prows = ((size_t)8 << 20) / (sizeof(PairPw) * B);
-        if (h->sw.trace_rows >= 1 && prows > (size_t)h->sw.trace_rows / 2) prows = (size_t)h->sw.trace_rows / 2;
-        prows = prows < 1 ? 1 : (prows > npairs ? npairs : prows);
-    }
-    const PwLayout lay(B, trows, prows);
-    const bool want_trace_d = trace || pairs;                   // (the pair kernels always record their two rows)
-    // the table and (when a series is wanted) the trace buffer: all or nothing; then the table's page-locked image
-    if (temps) {
-        if (int rc = alloc_group(h, "the per-world constants, the trace buffer and the temperature reduction",
-                                 {{h->pw_tab, lay.bytes}, {h->trace_d, trace ? rows * row_bytes : 0},
-                                  {h->temp_part, temp_part_bytes(h)}, {h->temp_d, rows * trow_bytes}})) return rc;
-    } else if (want_trace_d) {
-        if (int rc = alloc_group(h, "the per-world constants and the trace buffer",
-                                 {{h->pw_tab, lay.bytes}, {h->trace_d, rows * row_bytes}})) return rc;
-    } else if (int rc = alloc_group(h, "the per-world constants", {{h->pw_tab, lay.bytes}})) {
-        return rc;
-    }
-    if (int rc = reserve(h->pw_pinned, "the page-locked image of the per-world constants", lay.bytes)) {
-        h->pw_tab.reset();
-        return rc;
-    }
-    hipEvent_t uploaded = nullptr;                              // the image may be written again once its upload has run
-    HIPCHK(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
-    struct EventGuard { hipEvent_t e; ~EventGuard() { (void)hipEventDestroy(e); } } event_guard{uploaded};
-    SyncOnExit sync(h->stream);                                 // the downloads below fill the caller's array
+    const SeriesSchedule q = plan_series(SeriesSpec{nsteps, B, sizeof(StatsDev), sizeof(TempStatsDev), h->sw.trace_rows, always_even,
+                                                    may_pair, cur_quantised(h), temps != nullptr, pw ? L_schedule : nullptr});
+    std::unique_ptr<PwTable> table(pw ? new PwTable(h, PwLayout(B, q.trows, q.prows)) : nullptr);
+    SeriesRun run{h, q, L_schedule, trace, temps, table.get(), sym, form == PER_WORLD_CONSTANTS, B, sizeof(StatsDev) * B, sizeof(TempStatsDev) * B};
+    if (int rc = run.alloc()) return rc;
+    SyncOnExit sync(h->stream);                                 // the downloads fill the caller's arrays
     h->fused_launches = 0;
-    unsigned char* img = h->pw_pinned.get();
-    unsigned char* tab = h->pw_tab.get();
-    // a world whose luminosity did not change since its last step keeps its constants (a sweep at fixed L derives B sets,
-    // not nsteps * B); likewise a world whose two luminosities did not change since its last pair
-    std::vector<double> lastL(B, -1.0);
-    std::vector<PhysF32> last32(B);
-    std::vector<PhysF64> last64(B);
-    std::vector<PairPw> last_pair(npairs ? B : 0);
-    std::vector<double> lastLa(npairs ? B : 0, -1.0), lastLb(npairs ? B : 0, -1.0);
-    const bool first_bound = h->unq == OWN_CUR && h->plan.first_prec == 3;
-    bool image_in_flight = false, first_pair = true;
-    // A step whose luminosities all equal those of the step before it of its kind shares that step's row (a sweep at fixed
-    // luminosities: ONE row of each kind, one upload for the whole run); a chunk is the steps that `trows` distinct
-    // single-step rows and `prows` distinct pair rows serve.
-    std::vector<size_t> row_of((size_t)nsteps);
-    int chunk_end = 0;                                          // the steps before it have their rows on the device
-    for (int t = 0; t < nsteps;) {
-        const size_t sr = (size_t)t % rows;
-        if (t == chunk_end) {                                   // this chunk's constants: derived in float64, one upload
-            if (image_in_flight) HIPCHK(hipEventSynchronize(uploaded));
-            size_t tn = 0, pn = 0;
-            const double *single_Ls = nullptr, *pair_Ls = nullptr;      // the steps the newest row of each kind was built for
-            while (chunk_end < nsteps) {
-                const double* Ls = L_schedule + (size_t)chunk_end * B;
-                if (pairs && is_pair[chunk_end]) {
-                    if (pair_Ls && std::memcmp(Ls, pair_Ls, sizeof(double) * 2 * B) == 0) { row_of[chunk_end] = pn - 1; chunk_end += 2; continue; }
-                    if (pn == prows) break;
-                    PairPw* row = lay.pair(img, pn);
-                    for (size_t b = 0; b < B; ++b) {
-                        if (Ls[b] != lastLa[b] || Ls[B + b] != lastLb[b]) {   // the sets of launch_forward_fused2 (float32-only
-                            lastLa[b] = Ls[b];                                // mode), at this world's constants
-                            lastLb[b] = Ls[B + b];
-                            last_pair[b].P1 = derive_f32(params_of(b), lastLa[b]);
-                            last_pair[b].P2 = derive_f32(params_of(b), lastLb[b]);
-                        }
-                        row[b] = last_pair[b];
-                    }
-                    pair_Ls = Ls;
-                    row_of[chunk_end] = pn++;
-                    chunk_end += 2;
-                    continue;
-                }
-                if (single_Ls && std::memcmp(Ls, single_Ls, sizeof(double) * B) == 0) { row_of[chunk_end++] = tn - 1; continue; }
-                if (tn == trows) break;
-                PhysF32* r32 = lay.p32(img, tn);
-                PhysF64* r64 = lay.p64(img, tn);
-                for (size_t b = 0; b < B; ++b) {
-                    if (Ls[b] != lastL[b]) {
-                        lastL[b] = Ls[b];
-                        last32[b] = derive_f32(params_of(b), Ls[b]);
-                        last64[b] = make_f64(params_of(b), Ls[b]);
-                    }
-                    r32[b] = last32[b];
-                    r64[b] = last64[b];
-                }
-                single_Ls = Ls;
-                row_of[chunk_end++] = tn++;
-            }
-            if (t == 0 && first_bound)
-                for (size_t b = 0; b < B; ++b)
-                    lay.fb(img)[b] = derive_first_bound(params_of(b), L_schedule[b], lay.p32(img, 0)[b], h->unq_kind == UNQ_F64,
-                                                        h->sw.first_slack);     // (row 0 of the first chunk is step 0)
-            // (the rows in use of each part)
-            if (tn) {
-                HIPCHK(hipMemcpyAsync(tab, img, sizeof(PhysF32) * tn * B, hipMemcpyHostToDevice, h->stream));
-                HIPCHK(hipMemcpyAsync(tab + lay.o64, img + lay.o64, sizeof(PhysF64) * tn * B, hipMemcpyHostToDevice, h->stream));
-            }
-            if (t == 0 && first_bound)
-                HIPCHK(hipMemcpyAsync(tab + lay.ofb, img + lay.ofb, sizeof(FirstStepBound) * B, hipMemcpyHostToDevice, h->stream));
-            if (pn) HIPCHK(hipMemcpyAsync(tab + lay.opair, img + lay.opair, sizeof(PairPw) * pn * B, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipEventRecord(uploaded, h->stream));
-            image_in_flight = true;
-        }
-        const size_t tr = row_of[t];
-        int took = 1;
-        if (pairs && sr == 0) {                                 // the pair kernels ADD their reductions into the rows
-            const size_t left = (size_t)(nsteps - t);
-            HIPCHK(hipMemsetAsync(h->trace_d.get(), 0, (left < rows ? left : rows) * row_bytes, h->stream));
-        }
-        if (pairs && is_pair[t]) {
-            if (first_pair) {
-                drop_unquantised_previous(h);
-                first_pair = false;
-            }
-            if (int rc = launch_forward_fused2_pw(h, lay.pair(tab, tr), h->trace_d.get() + sr * B)) return rc;
-            took = 2;
-        } else {
-            if (temps)
-                if (int rc = launch_temp_moments(h, true, 0.0, lay.p64(tab, tr), h->temp_d.get() + sr * B)) return rc;
-            if (int rc = launch_forward_pw(h, lay.p32(tab, tr), lay.p64(tab, tr), lay.fb(tab), sym, ensemble)) return rc;
-            if (want_trace_d)
-                HIPCHK(hipMemcpyAsync(h->trace_d.get() + sr * B, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
-        }
-        const size_t filled = sr + (size_t)took;                // rows of this chunk of the series that are recorded now
-        if (filled == rows || t + took == nsteps) {
-            const size_t r0 = ((size_t)t - sr) * B;
-            if (temps) HIPCHK(hipMemcpyAsync(temps + r0, h->temp_d.get(), filled * trow_bytes, hipMemcpyDeviceToHost, h->stream));
-            if (trace) HIPCHK(hipMemcpyAsync(trace + r0, h->trace_d.get(), filled * row_bytes, hipMemcpyDeviceToHost, h->stream));
-        }
-        t += took;
-    }
+    if (int rc = run.run(rows.get())) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     sync.disarm();
     return DW_OK;
 }
 
+int dw_step_n_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace) {
+    NEED(h && L_schedule && trace, DW_EINVAL, "null argument");
+    return run_series(h, nsteps, L_schedule, trace, nullptr, true, h->plan.trace_pairs);
+}
+
 int dw_step_n_trace_per_world(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace) {
-    return trace_per_world(h, nsteps, L_schedule, trace, nullptr);
+    NEED(h && L_schedule, DW_EINVAL, "null argument");
+    return run_series(h, nsteps, L_schedule, trace, nullptr, false, false, PER_WORLD_L);
 }
 
 int dw_world_params_of(const dw_handle* h, dw_world_params* out) {
@@ -1503,45 +1411,14 @@ int dw_world_params_of(const dw_handle* h, dw_world_params* out) {
 int dw_step_n_trace_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params* worlds, const double* L_schedule,
                              dw_world_stats* trace, dw_temp_stats* temps) {
     static_assert(sizeof(dw_world_params) == 96, "dw_world_params layout");
-    static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev), "temperature record layout");
     NEED(h && worlds && L_schedule, DW_EINVAL, "null argument");
-    return trace_per_world(h, nsteps, L_schedule, trace, temps, worlds, true);
+    return run_series(h, nsteps, L_schedule, trace, temps, false, ensemble_pairs(h), PER_WORLD_CONSTANTS, worlds);
 }
 
 int dw_step_n_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_schedule, int per_world, dw_world_stats* trace,
                                 dw_temp_stats* temps) {
     NEED(h && L_schedule && temps, DW_EINVAL, "null argument");
-    static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev), "temperature record layout");
-    if (per_world) return trace_per_world(h, nsteps, L_schedule, trace, temps);
-    NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
-    if (nsteps == 0) return DW_OK;
-    NEED(h->have_state, DW_ESTATE, "no state uploaded (call dw_upload_state_* or dw_init_random)");
-    HIPCHK(hipSetDevice(h->prm.device));
-    const size_t B = (size_t)h->prm.batch, row_bytes = sizeof(StatsDev) * B, trow_bytes = sizeof(TempStatsDev) * B;
-    // rows of both series held on the device at a time: the whole run up to 32 MiB of temperature records, longer runs
-    // in chunks of that size (single steps: any number of rows will do); DW_TEST_TRACE_ROWS: that many rows instead
-    size_t rows = h->sw.trace_rows >= 1 ? (size_t)h->sw.trace_rows : ((size_t)32 << 20) / trow_bytes;
-    rows = rows < 1 ? 1 : (rows > (size_t)nsteps ? (size_t)nsteps : rows);
-    if (int rc = alloc_group(h, "the trace buffer and the temperature reduction",
-                             {{h->trace_d, trace ? rows * row_bytes : 0}, {h->temp_part, temp_part_bytes(h)},
-                              {h->temp_d, rows * trow_bytes}})) return rc;
-    SyncOnExit sync(h->stream);                                 // the downloads below fill the caller's arrays
-    h->fused_launches = 0;
-    for (int t = 0; t < nsteps; ++t) {
-        const size_t sr = (size_t)t % rows;
-        // the field this step computes: from its input planes, in front of it
-        if (int rc = launch_temp_moments(h, true, L_schedule[t], nullptr, h->temp_d.get() + sr * B)) return rc;
-        if (int rc = launch_forward(h, L_schedule[t])) return rc;
-        if (trace) HIPCHK(hipMemcpyAsync(h->trace_d.get() + sr * B, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
-        if (sr + 1 == rows || t + 1 == nsteps) {
-            const size_t r0 = ((size_t)t - sr) * B;
-            HIPCHK(hipMemcpyAsync(temps + r0, h->temp_d.get(), (sr + 1) * trow_bytes, hipMemcpyDeviceToHost, h->stream));
-            if (trace) HIPCHK(hipMemcpyAsync(trace + r0, h->trace_d.get(), (sr + 1) * row_bytes, hipMemcpyDeviceToHost, h->stream));
-        }
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    sync.disarm();
-    return DW_OK;
+    return run_series(h, nsteps, L_schedule, trace, temps, false, false, per_world ? PER_WORLD_L : SHARED_L);
 }
 
 int dw_last_step_n_timing(dw_handle* h, float* fused_ms, int32_t* fused_launches, int32_t* plane_elem_bytes) {
@@ -2067,6 +1944,38 @@ static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes) {
 
 static bool episode_kernel_applies(const dw_handle* h) { return episode_form(h) != EPISODE_STEPWISE && cur_quantised(h); }
 
+// The agents' part of a step of the stepwise episode loops: the actions of policy_mode - or, `from_table`, the caller's
+// slice `codes` [B*N] (-1 / -2: greedy / anti-greedy) - into h->action, then grazing (d_ok: the ok flags straight from it)
+static int launch_policy(dw_handle* h, int policy_mode, bool from_table, const unsigned char* codes, unsigned char* d_ok = nullptr) {
+    const size_t bn = (size_t)h->prm.batch * h->prm.n_agents;
+    if (policy_mode == DW_POLICY_TABLE || from_table) {
+        hipLaunchKernelGGL(actions_from_table, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, h->stream,
+                           reinterpret_cast<const signed char*>(codes), (int)bn, h->action.get());
+        if (int rc = launch_policy_greedy(h, 0, nullptr, 1)) return rc;
+    } else if (policy_mode == DW_POLICY_ZEROS) {
+        HIPCHK(hipMemsetAsync(h->action.get(), 0, sizeof(int) * bn, h->stream));
+    } else if (int rc = launch_policy_greedy(h, policy_mode == DW_POLICY_ARGMIN ? 1 : 0, nullptr, 0)) {
+        return rc;
+    }
+    HIPCHK(hipGetLastError());
+    return launch_agents(h, h->action.get(), h->prm.batch, h->prm.n_agents, false, nullptr, nullptr, d_ok);
+}
+
+// What both LDS-resident episode launches pass alike: the planes in place, the agents, the reductions of the current
+// state, and the float32 sets and luminosities of the steps at offsets of the staging buffer
+static EpisodeIO episode_io(const dw_handle* h, int policy_mode, size_t o_p32, size_t o_ls) {
+    EpisodeIO io{};
+    const int cur = h->cur, prev = 1 - h->cur;
+    io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
+    io.idx = h->idx.get(); io.st = h->st.get();
+    io.P32 = reinterpret_cast<const PhysF32*>(h->ep_buf.get() + o_p32);
+    io.Ls = reinterpret_cast<const double*>(h->ep_buf.get() + o_ls);
+    io.stats = h->stats2[h->sp].get();
+    io.fixups = &io.stats[h->prm.batch].sum_l;
+    io.action = (h->prm.n_agents > 0 && policy_mode != kPolicySkipAgents) ? h->action.get() : nullptr;
+    return io;
+}
+
 // dw_run_episode for worlds that do not fit LDS: the same K steps as K x (policy, dw_step) issued
 // back-to-back on the handle's stream - policy kernel or table slice -> update_agents -> step kernel ->
 // flags from the step's reductions - with no host round trip in between; one synchronisation at the end.
@@ -2098,7 +2007,6 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
     const int uniform_code = policy_mode == DW_POLICY_ZEROS ? 0 : (policy_mode == DW_POLICY_ARGMIN ? 0xFE : 0xFF);
     if (may_pair && policy_mode != DW_POLICY_TABLE)
         HIPCHK(hipMemsetAsync(h->ep_buf.get() + o_code, uniform_code, bn, h->stream));
-    auto greedy = [&](int argmin, int codes) { return launch_policy_greedy(h, argmin, nullptr, codes); };
     // policy + update_agents of the step after a pair run inside that pair's patch kernel (phase E) while the chunk
     // continues: two launches per pair instead of four (DW_NO_AGENT_PREAPPLY: experiments)
     const bool no_preapply = h->sw.no_agent_preapply;
@@ -2108,20 +2016,9 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
         if (pre_applied) {
             pre_applied = false;                             // step t's policy and grazing were done by the last patch
         } else if (bn && policy_mode != kPolicySkipAgents) {
-            const bool from_table = policy_mode == DW_POLICY_TABLE || (use_table && use_table[t]);
-            if (from_table) {
-                hipLaunchKernelGGL(actions_from_table, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, h->stream,
-                                   reinterpret_cast<const signed char*>(h->ep_buf.get() + o_tab + t * bn), (int)bn, h->action.get());
-                if (int prc = greedy(0, 1)) return prc;                      // codes -1 / -2: greedy / anti-greedy
-            } else if (policy_mode == DW_POLICY_ZEROS) {
-                HIPCHK(hipMemsetAsync(h->action.get(), 0, sizeof(int) * bn, h->stream));
-            } else {
-                if (int prc = greedy(policy_mode == DW_POLICY_ARGMIN ? 1 : 0, 0)) return prc;
-            }
-            HIPCHK(hipGetLastError());
             // a pair's first step: the agents' ok flags straight from the grazing kernel
-            int rc = launch_agents(h, h->action.get(), B, N, false, nullptr, nullptr, pair ? h->ep_buf.get() + o_ok + t * bn : nullptr);
-            if (rc) return rc;
+            if (int rc = launch_policy(h, policy_mode, use_table && use_table[t], h->ep_buf.get() + o_tab + t * bn,
+                                       pair ? h->ep_buf.get() + o_ok + t * bn : nullptr)) return rc;
         }
         if (pair) {
             const double L1 = L_schedule[t], L2 = L_schedule[t + 1];
@@ -2244,19 +2141,11 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     // episode_wave ASSIGNS every world's whole record (its float64 count in `reserved`) and the counter record behind them:
     // nothing to clear; episode_small accumulates: cleared as before
     if (!wave_kernel) HIPCHK(hipMemsetAsync(stats, 0, sizeof(StatsDev) * (B + 1), h->stream));
-    EpisodeIO io;
-    const int cur = h->cur, prev = 1 - h->cur;
-    io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
-    io.idx = h->idx.get(); io.st = h->st.get();
-    io.P32 = reinterpret_cast<const PhysF32*>(h->ep_buf.get() + o_p32);
-    io.Ls = reinterpret_cast<const double*>(h->ep_buf.get() + o_ls);
+    EpisodeIO io = episode_io(h, policy_mode, o_p32, o_ls);
     io.use_table = h->ep_buf.get() + o_ut;
     io.table = reinterpret_cast<const signed char*>(h->ep_buf.get() + o_tab);
     io.world_alive = h->ep_buf.get() + o_wa;
     io.agent_ok = h->ep_buf.get() + o_ok;
-    io.stats = stats;
-    io.fixups = &stats[B].sum_l;
-    io.action = (N > 0 && policy_mode != kPolicySkipAgents) ? h->action.get() : nullptr;
     const PhysF64 P64 = make_f64(p, L_schedule[0]);
     const dim3 grid((unsigned)((B + wpb - 1) / wpb));
     const bool ex = p.precision == DW_PRECISION_EXACT;
@@ -2284,10 +2173,7 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
         if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * B, hipMemcpyDeviceToHost, h->stream));
         if (want_ok) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
     }
-    h->unq = OWN_NONE;
-    h->stepped = true;
-    h->L_last = L_schedule[K - 1];
-    h->L_per_world = false;
+    episode_done(h, L_schedule[K - 1], false);
     release_unquantised(h);
     HIPCHK(hipStreamSynchronize(h->stream));      // flags are returned
     guard.disarm();
@@ -2303,91 +2189,35 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
 // shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step
 static bool ensemble_episode_wave(const dw_handle* h) { return episode_form(h) == EPISODE_WAVE; }
 
-// twin[b]: world b's set equals world b - 1's (a scenario's block of worlds in a sweep): at the same luminosity it takes
-// that world's rows instead of a derivation of its own - S derivations per step for S scenarios, not B
-static std::vector<unsigned char> twin_worlds(const dw_world_params* worlds, size_t B) {
-    std::vector<unsigned char> twin(B, 0);
-    for (size_t b = 1; b < B; ++b) twin[b] = std::memcmp(&worlds[b], &worlds[b - 1], sizeof(dw_world_params)) == 0;
-    return twin;
-}
-
-// Launches per step from existing kernels - policy kernel or table slice, launch_agents, launch_forward_pw (the per-world
-// single step of dw_step_n_trace_ensemble), episode_flags - with one synchronisation at the end; no fused pairs and no
-// LDS workgroup kernel.  The rows of a chunk of steps (PwLayout) go up in one copy per part from the page-locked image.
-static int run_episode_ensemble_stepwise(dw_handle* h, int32_t nsteps, const std::vector<dw_params>& wp,
-                                         const std::vector<unsigned char>& twin, bool sym, const double* L_schedule, int policy_mode, const uint8_t* use_table, const int8_t* table,
-                                         uint32_t threshold_k, uint8_t* world_alive, uint8_t* agent_ok) {
+// Launches per step from existing kernels - launch_policy, launch_forward_pw (the per-world single step of
+// dw_step_n_trace_ensemble), episode_flags - with one synchronisation at the end; no fused pairs and no LDS workgroup
+// kernel.  The rows go up as in the trace calls (PwTable, the table chunks of plan_series without the test hook).
+static int run_episode_ensemble_stepwise(dw_handle* h, int32_t nsteps, WorldRows& worlds, bool sym, const double* L_schedule,
+                                         int policy_mode, const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
+                                         uint8_t* world_alive, uint8_t* agent_ok) {
     const dw_params& p = h->prm;
     const int N = p.n_agents, B = p.batch;
     const size_t K = (size_t)nsteps, bn = (size_t)B * N, Bz = (size_t)B;
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t o_tab = 0, o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * Bz), total = up(o_ok + K * bn) + 256;
-    size_t trows = ((size_t)8 << 20) / ((sizeof(PhysF32) + sizeof(PhysF64)) * Bz);
-    trows = trows < 1 ? 1 : (trows > K ? K : trows);
-    const PwLayout lay(Bz, trows);
+    const SeriesSchedule q = plan_series(SeriesSpec{nsteps, Bz, sizeof(StatsDev), 0, 0, false, false, true, false, L_schedule});   // (single steps, no hook)
+    PwTable tab(h, PwLayout(Bz, q.trows));
     if (int rc = ensure_ep_buf(h, total)) return rc;
-    if (int rc = alloc_group(h, "the per-world constants", {{h->pw_tab, lay.bytes}})) return rc;
-    if (int rc = reserve(h->pw_pinned, "the page-locked image of the per-world constants", lay.bytes)) {
-        h->pw_tab.reset();
-        return rc;
-    }
-    hipEvent_t uploaded = nullptr;                              // the image may be written again once its upload has run
-    HIPCHK(hipEventCreateWithFlags(&uploaded, hipEventDisableTiming));
-    struct EventGuard { hipEvent_t e; ~EventGuard() { (void)hipEventDestroy(e); } } event_guard{uploaded};
+    if (int rc = tab.alloc("the per-world constants", {tab.item()})) return rc;
     SyncOnExit guard(h->stream);                                // `table` and the flag arrays are the caller's
     if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
-    unsigned char* img = h->pw_pinned.get();
-    unsigned char* tab = h->pw_tab.get();
-    std::vector<double> lastL(Bz, -1.0);                        // a world whose luminosity did not change keeps its rows
-    std::vector<PhysF32> last32(Bz);
-    std::vector<PhysF64> last64(Bz);
     const int nflag = B > (int)bn ? B : (int)bn;
-    size_t chunk_begin = 0, chunk_end = 0;
+    size_t c = 0;                                               // the table chunk that starts next
     for (size_t t = 0; t < K; ++t) {
-        if (t == chunk_end) {
-            if (t) HIPCHK(hipEventSynchronize(uploaded));
-            chunk_begin = t;
-            chunk_end = t + trows < K ? t + trows : K;
-            for (size_t tt = chunk_begin; tt < chunk_end; ++tt) {
-                const double* Ls = L_schedule + tt * Bz;
-                PhysF32* r32 = lay.p32(img, tt - chunk_begin);
-                PhysF64* r64 = lay.p64(img, tt - chunk_begin);
-                for (size_t b = 0; b < Bz; ++b) {
-                    if (Ls[b] != lastL[b]) {
-                        lastL[b] = Ls[b];
-                        if (twin[b] && lastL[b - 1] == Ls[b]) {
-                            last32[b] = last32[b - 1];
-                            last64[b] = last64[b - 1];
-                        } else {
-                            last32[b] = derive_f32(wp[b], Ls[b]);
-                            last64[b] = make_f64(wp[b], Ls[b]);
-                        }
-                    }
-                    r32[b] = last32[b];
-                    r64[b] = last64[b];
-                }
-            }
-            const size_t tn = chunk_end - chunk_begin;
-            HIPCHK(hipMemcpyAsync(tab, img, sizeof(PhysF32) * tn * Bz, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(tab + lay.o64, img + lay.o64, sizeof(PhysF64) * tn * Bz, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipEventRecord(uploaded, h->stream));
+        if ((int)t == (c ? q.chunks[c - 1].end : 0)) {
+            if (int rc = tab.next_chunk(q, c, L_schedule, worlds)) return rc;
+            ++c;
         }
-        if (bn) {
-            const bool from_table = policy_mode == DW_POLICY_TABLE || (policy_mode != DW_POLICY_ZEROS && use_table && use_table[t]);
-            if (from_table) {
-                hipLaunchKernelGGL(actions_from_table, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, h->stream,
-                                   reinterpret_cast<const signed char*>(h->ep_buf.get() + o_tab + t * bn), (int)bn, h->action.get());
-                if (int rc = launch_policy_greedy(h, 0, nullptr, 1)) return rc;   // codes -1 / -2: greedy / anti-greedy
-            } else if (policy_mode == DW_POLICY_ZEROS) {
-                HIPCHK(hipMemsetAsync(h->action.get(), 0, sizeof(int) * bn, h->stream));
-            } else if (int rc = launch_policy_greedy(h, policy_mode == DW_POLICY_ARGMIN ? 1 : 0, nullptr, 0)) {
-                return rc;
-            }
-            HIPCHK(hipGetLastError());
-            if (int rc = launch_agents(h, h->action.get(), B, N)) return rc;
-        }
-        const size_t tr = t - chunk_begin;
-        if (int rc = launch_forward_pw(h, lay.p32(tab, tr), lay.p64(tab, tr), lay.fb(tab), sym, true)) return rc;
+        if (bn)
+            if (int rc = launch_policy(h, policy_mode, policy_mode != DW_POLICY_ZEROS && use_table && use_table[t],
+                                       h->ep_buf.get() + o_tab + t * bn)) return rc;
+        const size_t tr = q.row_of[t];
+        if (int rc = launch_forward_pw(h, tab.lay.p32(tab.dev(), tr), tab.lay.p64(tab.dev(), tr), tab.lay.fb(tab.dev()), sym, true)) return rc;
         hipLaunchKernelGGL(episode_flags, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, h->stream, h->stats2[h->sp].get(),
                            h->st.get(), B, N, threshold_k, h->ep_buf.get() + o_wa + t * Bz, h->ep_buf.get() + o_ok + t * bn);
         HIPCHK(hipGetLastError());
@@ -2411,12 +2241,10 @@ int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params*
     if (int rc = check_episode_call(h, nsteps, policy_mode, use_table, table)) return rc;
     const int C = p.height * p.width, N = p.n_agents, B = p.batch;
     const size_t K = (size_t)nsteps, Bz = (size_t)B, bn = Bz * N;
-    if (int rc = check_luminosities(L_schedule, K, Bz)) return rc;
-    std::vector<dw_params> wp;
-    if (int rc = world_param_sets(p, worlds, Bz, wp)) return rc;
-    const std::vector<unsigned char> twin = twin_worlds(worlds, Bz);
+    WorldRows rows_of(p, worlds, Bz, !ensemble_episode_wave(h));
+    if (int rc = check_per_world(rows_of, worlds, L_schedule, K, Bz)) return rc;
     if (!ensemble_episode_wave(h))
-        return run_episode_ensemble_stepwise(h, nsteps, wp, twin, worlds_symmetric(worlds, Bz) && !h->sw.no_sym, L_schedule, policy_mode,
+        return run_episode_ensemble_stepwise(h, nsteps, rows_of, worlds_symmetric(worlds, Bz) && !h->sw.no_sym, L_schedule, policy_mode,
                                              use_table, table, threshold_k, world_alive, agent_ok);
     const size_t lds = episode_wave_pw_shared_bytes() + episode_wave_pw_world_bytes(C, N) * 4;
     NEED(lds <= 160 * 1024, DW_EINVAL, "too many agents for the LDS-resident episode kernel");
@@ -2440,41 +2268,21 @@ int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params*
     unsigned char* dev = h->ep_buf.get();
     SyncOnExit guard(h->stream);                                // the image
     PhysF64* p64 = reinterpret_cast<PhysF64*>(img + o_p64);
-    for (size_t b = 0; b < Bz; ++b) p64[b] = make_f64(wp[b], 0.0);          // (L: replaced by the step's, from the Ls rows)
+    for (size_t b = 0; b < Bz; ++b) p64[b] = make_f64(rows_of.params(b), 0.0);   // (L: replaced by the step's, from the Ls rows)
     if (use_table) std::memcpy(img + o_ut, use_table, K); else std::memset(img + o_ut, 0, K);
     const bool have_table = table && bn;
     if (have_table) std::memcpy(img + o_tab, table, K * bn);
-    EpisodeIO io;
-    const int cur = h->cur, prev = 1 - h->cur;
-    StatsDev* stats = h->stats2[h->sp].get();                   // (every world's whole record is assigned by the kernel)
-    io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
-    io.idx = h->idx.get(); io.st = h->st.get();
-    io.P32 = reinterpret_cast<const PhysF32*>(dev + o_p32);
-    io.Ls = reinterpret_cast<const double*>(dev + o_ls);
-    io.stats = stats;
-    io.fixups = &stats[B].sum_l;
-    io.action = (N > 0) ? h->action.get() : nullptr;
+    EpisodeIO io = episode_io(h, policy_mode, o_p32, o_ls);     // (every world's whole record is assigned by the kernel)
     const bool ex = p.precision == DW_PRECISION_EXACT;
     auto kern = ex ? episode_wave_pw<true> : episode_wave_pw<false>;
     if (int rc = set_lds_limit(h, kern, lds)) return rc;
-    std::vector<double> lastL(Bz, -1.0);                        // a world whose luminosity did not change keeps its row
-    std::vector<PhysF32> last32(Bz);
     PhysF32* r32 = reinterpret_cast<PhysF32*>(img + o_p32);
     double* rls = reinterpret_cast<double*>(img + o_ls);
     for (size_t t0 = 0; t0 < K; t0 += rows) {
         const size_t kk = K - t0 < rows ? K - t0 : rows;
         if (t0) HIPCHK(hipStreamSynchronize(h->stream));        // the image's rows are free again
-        for (size_t t = 0; t < kk; ++t) {
-            const double* Ls = L_schedule + (t0 + t) * Bz;
-            for (size_t b = 0; b < Bz; ++b) {
-                if (Ls[b] != lastL[b]) {
-                    lastL[b] = Ls[b];
-                    last32[b] = (twin[b] && lastL[b - 1] == Ls[b]) ? last32[b - 1] : derive_f32(wp[b], Ls[b]);
-                }
-                r32[t * Bz + b] = last32[b];
-            }
-            std::memcpy(rls + t * Bz, Ls, sizeof(double) * Bz);
-        }
+        for (size_t t = 0; t < kk; ++t) rows_of.single(L_schedule + (t0 + t) * Bz, r32 + t * Bz, nullptr);
+        std::memcpy(rls, L_schedule + t0 * Bz, sizeof(double) * kk * Bz);
         const size_t upto = t0 ? o_ls + sizeof(double) * kk * Bz : (have_table ? o_tab + K * bn : o_ut + K);
         HIPCHK(hipMemcpyAsync(dev, img, upto, hipMemcpyHostToDevice, h->stream));
         io.use_table = use_table ? dev + o_ut + t0 : nullptr;
@@ -2485,11 +2293,7 @@ int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params*
                                   p.obs_mask, threshold_k, p.agent_gamma};
         hipLaunchKernelGGL(kern, dim3((unsigned)((B + 3) / 4)), dim3(256), lds, h->stream, A);
         HIPCHK(hipGetLastError());
-        h->unq = OWN_NONE;                                      // the handle as after dw_step_n_trace_ensemble: per-world in
-        h->stepped = true;                                      // both senses, luminosity and constants
-        h->L_last = 0.0;
-        h->L_per_world = true;
-        h->P_per_world = true;
+        episode_done(h, 0.0, true);
     }
     release_unquantised(h);
     const bool want_ok = agent_ok && bn;

@@ -18,11 +18,6 @@
 
 namespace dw {
 
-struct PairPw {
-    PhysF32 P1, P2;              // the sets of step 1 and step 2
-};
-static_assert(sizeof(PairPw) == 2 * sizeof(PhysF32), "PairPw layout");
-
 // The world of this wave's strip (strip_world: fused2_body numbers its un-packed strips as stream_body does), in a scalar
 // register (the division by the strips per world runs on the vector unit).
 __device__ __forceinline__ int pair_world(const FusedGeom& G) { return __builtin_amdgcn_readfirstlane(strip_world(G)); }

@@ -56,6 +56,11 @@ struct FirstStepBound {
     float eK0, eK1, cW, eA, cS, slack;
 };
 
+struct PairPw {               // the constants of a step pair of one world (dw_step_fused_pw.hpp)
+    PhysF32 P1, P2;              // the sets of step 1 and step 2
+};
+static_assert(sizeof(PairPw) == 2 * sizeof(PhysF32), "PairPw layout");
+
 struct StatsDev {             // mirrors dw_world_stats
     unsigned int max_k;
     unsigned int reserved;    // the one-wave-per-world episode kernels: float64 re-evaluations of the world's last step
