@@ -523,6 +523,33 @@ int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps,
                             int policy_mode, const uint8_t* use_table, const int8_t* table,
                             uint32_t threshold_k, uint8_t* world_alive, uint8_t* agent_ok);
 
+/* dw_run_episode that also records, for every step and world, what dw_reduce would report after that step: the daisy
+ * populations of an ensemble with grazing agents in it as ONE device-resident run - the curves of the reference's
+ * animations with an agent (daisy/notebook_helpers.py:218-223 `update_fig_agent`, notebooks/rl_daisy_world.ipynb cells
+ * 12-16, notebooks/greedy_longevity_abatement.ipynb cells 10-15: env.grid[:,1].mean() and env.grid[:,2].mean() appended
+ * after every env.step(action)) - instead of one dw_step + dw_reduce round trip per step.
+ * Contract: everything dw_run_episode leaves on the handle and in world_alive / agent_ok for the same arguments - the
+ * planes, the retained previous state, the agents, dw_reduce, the device action buffer, dw_last_fixup_count, the flags -
+ * this call leaves too, bit for bit, in DW_PRECISION_EXACT and DW_PRECISION_FAST (n_agents == 0 allowed).
+ *   trace[t*B + b]  {max_k, sum_light_k, sum_dark_k} of world b after step t: the record dw_reduce returns after t + 1
+ *                   single-step calls, written with reserved = 0.  Hence world_alive[t][b] == (trace[t*B+b].max_k >
+ *                   threshold_k), and the last row equals dw_reduce after the call.  Required.
+ * H*W <= 256 with at most 64 agents: one launch, one wave per world (episode_wave_stats_pw,
+ * csrc/dw_episode_wave_stats_pw.hpp: the forward pass returns each lane's sums and maximum, combined across the wave with
+ * DPP operations per step; the records of a 64-step segment wait in LDS and are written next to the segment's flags).
+ * Every other shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step from existing kernels (policy kernel
+ * or table slice, update_agents, the step kernel, flags) plus one that copies the step's reductions into the trace - no
+ * fused step pairs (the step-1 sums of a pair would have to include the patch kernel's corrections) and no LDS workgroup
+ * kernel: the price of the records there (dw_kernel_info: "; episode trace: one wave per world" / "launches per step").
+ * Flags and records come down through the staging buffer's page-locked image in one copy.
+ * Checked before anything is launched or allocated (the state is untouched): the rules of dw_run_episode (DW_ESTATE: no
+ * state, no agents, an un-quantised current state; DW_EINVAL: DW_PRECISION_F64, collision_mode 1, nsteps outside 1..4096,
+ * the table rules), and DW_EINVAL for a null trace.  Synchronises. */
+int dw_run_episode_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
+                         const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
+                         uint8_t* world_alive /* [K][B], may be NULL */, uint8_t* agent_ok /* [K][B][N], may be NULL */,
+                         dw_world_stats* trace /* [K][B], required */);
+
 /* ---- plumbing ------------------------------------------------------------------------------- */
 
 /* Use an existing HIP stream (e.g. torch's current stream) instead of the handle's own. */
@@ -539,7 +566,8 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark);
 
 /* Name and geometry of the step kernel the handle dispatches for its shape, for bench/profiles:
  * writes a NUL-terminated description into buf.  Appended fragments name the forms of the other entry points:
- * "; trace: ...", "; per-world L: ...", "; ensemble episode: ..." (dw_run_episode_ensemble) and
+ * "; trace: ...", "; per-world L: ...", "; ensemble episode: ..." (dw_run_episode_ensemble), "; episode trace: ..."
+ * (dw_run_episode_trace) and
  * "; episode: F; mlp episode: F" - the form dw_run_episode and
  * dw_run_episode_mlp take for the handle's shape, agent count, precision, collision mode and switches, F one of
  * "one wave per world" (H*W <= 256 and at most 64 agents, MLP: at most 4), "workgroup (LDS)" (H*W <= 4096) and

@@ -295,12 +295,15 @@ static int ensure_f64(dw_handle* h) {
 
 static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                             const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
-                            uint8_t* world_alive, uint8_t* agent_ok);
+                            uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace = nullptr);
 static bool episode_kernel_applies(const dw_handle* h);
 // The form a handle's episode calls take: a pure function of its parameters and switches.  The dispatch of
 // run_episode_impl / dw_run_episode_mlp and the text of dw_kernel_info both read these two predicates.
 enum EpisodeForm { EPISODE_STEPWISE, EPISODE_WORKGROUP, EPISODE_WAVE };   // launches per step | episode_small / episode_mlp | one wave per world
 static EpisodeForm episode_form(const dw_handle* h);
+static int run_episode_trace_stepwise(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
+                                      const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
+                                      uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace);
 static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes = nullptr);
 // worlds a workgroup of the LDS-resident episode kernels holds (dw_episode.hpp: 256 / wpb threads per world)
 static int worlds_per_block(int cells) { return cells <= 256 ? 4 : (cells <= 1024 ? 2 : 1); }
@@ -2085,27 +2088,34 @@ static int check_episode_call(const dw_handle* h, int32_t nsteps, int policy_mod
     return DW_OK;
 }
 
+// `trace` (dw_run_episode_trace): also the records of every step, [K][B]; the one-wave-per-world form takes
+// episode_wave_stats_pw, every other form launches per step (run_episode_trace_stepwise).
 static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                             const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
-                            uint8_t* world_alive, uint8_t* agent_ok) {
+                            uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace) {
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
     if (int rc = check_episode_call(h, nsteps, policy_mode, use_table, table)) return rc;
     const int C = p.height * p.width, N = p.n_agents, B = p.batch;
     const EpisodeForm form = episode_form(h);                  // (F64 / collision_mode 1 were rejected above)
+    if (trace && form != EPISODE_WAVE)
+        return run_episode_trace_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
+                                          agent_ok, trace);
     if (form == EPISODE_STEPWISE)
         return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
                                     agent_ok);
     const bool wave_kernel = form == EPISODE_WAVE;
     const int wpb = worlds_per_block(C);
     const size_t world_bytes = wave_kernel ? episode_wave_world_bytes(C, N) : episode_world_bytes(C, N);
-    const size_t lds = world_bytes * wpb + (wave_kernel ? episode_wave_shared_bytes() : 0);
+    const size_t lds = trace ? episode_wave_stats_lds_bytes(C, N)     // (<= 64 KB for every shape of the form: static_assert there)
+                             : world_bytes * wpb + (wave_kernel ? episode_wave_shared_bytes() : 0);
     NEED(lds <= 160 * 1024, DW_EINVAL, "too many agents for the LDS-resident episode kernel");
-    // device staging: [P32 K][Ls K][use_table K][table K*B*N] | [world_alive K*B][agent_ok K*B*N]
+    // device staging: [P32 K][Ls K][use_table K][table K*B*N] | [world_alive K*B][agent_ok K*B*N][trace K*B records]
     const size_t K = (size_t)nsteps, bn = (size_t)B * N;
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t o_p32 = 0, o_ls = up(o_p32 + sizeof(PhysF32) * K), o_ut = up(o_ls + sizeof(double) * K);
-    const size_t o_tab = up(o_ut + K), o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * B), total = up(o_ok + K * bn);
+    const size_t o_tab = up(o_ut + K), o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * B), o_tr = up(o_ok + K * bn);
+    const size_t tr_bytes = trace ? sizeof(StatsDev) * K * B : 0, total = up(o_tr + tr_bytes);
     if (int erc = ensure_ep_buf(h, total)) return erc;
     // The inputs are assembled in a page-locked image of the staging buffer and go up in ONE copy; the flags come back
     // in ONE copy (round 3: four pageable uploads, a memset and two pageable downloads per chunk - 88 us of host time
@@ -2149,7 +2159,14 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     const PhysF64 P64 = make_f64(p, L_schedule[0]);
     const dim3 grid((unsigned)((B + wpb - 1) / wpb));
     const bool ex = p.precision == DW_PRECISION_EXACT;
-    if (wave_kernel) {
+    if (trace) {
+        io.use_table = use_table ? h->ep_buf.get() + o_ut : nullptr;
+        io.table = (table && bn) ? io.table : nullptr;
+        auto kern = ex ? episode_wave_stats_pw<true> : episode_wave_stats_pw<false>;
+        const EpisodeWaveStatsArgs A{io, reinterpret_cast<StatsDev*>(h->ep_buf.get() + o_tr), B, N, p.height, p.width, nsteps,
+                                     policy_mode, p.obs_mask, threshold_k, p.agent_gamma, P64};
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, h->stream, A);
+    } else if (wave_kernel) {
         io.use_table = use_table ? h->ep_buf.get() + o_ut : nullptr;
         io.table = (table && bn) ? io.table : nullptr;
         auto kern = ex ? episode_wave<true> : episode_wave<false>;
@@ -2165,13 +2182,15 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     HIPCHK(hipGetLastError());
     const bool want_ok = agent_ok && bn;
     if (staged) {
-        if (world_alive || want_ok) {
-            const size_t lo = world_alive ? o_wa : o_ok, hi = want_ok ? o_ok + K * bn : o_wa + K * B;
+        if (world_alive || want_ok || trace) {                  // flags and records: ONE download
+            const size_t lo = world_alive ? o_wa : (want_ok ? o_ok : o_tr);
+            const size_t hi = trace ? o_tr + tr_bytes : (want_ok ? o_ok + K * bn : o_wa + K * B);
             HIPCHK(hipMemcpyAsync(h->ep_pinned.get() + lo, h->ep_buf.get() + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
         }
     } else {
         if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * B, hipMemcpyDeviceToHost, h->stream));
         if (want_ok) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
+        if (trace) HIPCHK(hipMemcpyAsync(trace, h->ep_buf.get() + o_tr, tr_bytes, hipMemcpyDeviceToHost, h->stream));
     }
     episode_done(h, L_schedule[K - 1], false);
     release_unquantised(h);
@@ -2180,8 +2199,59 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     if (staged) {
         if (world_alive) std::memcpy(world_alive, h->ep_pinned.get() + o_wa, K * B);
         if (want_ok) std::memcpy(agent_ok, h->ep_pinned.get() + o_ok, K * bn);
+        if (trace) std::memcpy(trace, h->ep_pinned.get() + o_tr, tr_bytes);
     }
     return DW_OK;
+}
+
+// ---- dw_run_episode_trace: dw_run_episode with the records of every step ------------------------------------------
+// The form the call takes: one wave per world (episode_wave_stats_pw) wherever dw_run_episode takes episode_wave; every
+// other shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step
+static bool episode_trace_wave(const dw_handle* h) { return episode_form(h) == EPISODE_WAVE; }
+
+// Launches per step from existing kernels, exactly as run_episode_stepwise issues them with pairing off - policy kernel
+// or table slice, update_agents, launch_forward, episode_flags - plus episode_stats_row_pw, which copies the step's
+// reductions into row t of the trace; one synchronisation at the end.  No fused step pairs (the step-1 sums of a pair
+// would have to include the patch kernel's corrections) and no LDS workgroup kernel: the stated price of the records.
+static int run_episode_trace_stepwise(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
+                                      const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
+                                      uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace) {
+    const dw_params& p = h->prm;
+    const int N = p.n_agents, B = p.batch;
+    const size_t K = (size_t)nsteps, bn = (size_t)B * N, Bz = (size_t)B;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t o_tab = 0, o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * Bz), o_tr = up(o_ok + K * bn);
+    const size_t total = up(o_tr + sizeof(StatsDev) * K * Bz) + 256;
+    if (int erc = ensure_ep_buf(h, total)) return erc;
+    SyncOnExit guard(h->stream);                                // `table`, the flag arrays and `trace` are the caller's
+    if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
+    const int nflag = B > (int)bn ? B : (int)bn;
+    StatsDev* const rows = reinterpret_cast<StatsDev*>(h->ep_buf.get() + o_tr);
+    for (size_t t = 0; t < K; ++t) {
+        if (bn && policy_mode != kPolicySkipAgents)
+            if (int rc = launch_policy(h, policy_mode, use_table && use_table[t], h->ep_buf.get() + o_tab + t * bn)) return rc;
+        if (int rc = launch_forward(h, L_schedule[t])) return rc;
+        hipLaunchKernelGGL(episode_flags, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, h->stream, h->stats2[h->sp].get(),
+                           h->st.get(), B, N, threshold_k, h->ep_buf.get() + o_wa + t * Bz, h->ep_buf.get() + o_ok + t * bn);
+        hipLaunchKernelGGL(episode_stats_row_pw, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream,
+                           h->stats2[h->sp].get(), B, rows + t * Bz);
+        HIPCHK(hipGetLastError());
+    }
+    if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * Bz, hipMemcpyDeviceToHost, h->stream));
+    if (agent_ok && bn) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(trace, rows, sizeof(StatsDev) * K * Bz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    guard.disarm();
+    return DW_OK;
+}
+
+int dw_run_episode_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
+                         const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
+                         uint8_t* agent_ok, dw_world_stats* trace) {
+    NEED(h && L_schedule, DW_EINVAL, "null argument");
+    NEED(trace, DW_EINVAL, "dw_run_episode_trace needs a trace array");
+    NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
+    return run_episode_impl(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace);
 }
 
 // ---- dw_run_episode_ensemble: dw_run_episode with a set of physics constants and a luminosity column per world --------
@@ -2521,6 +2591,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_run_episode_ensemble takes
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, "; ensemble episode: %s", ensemble_episode_wave(h) ? "one wave per world" : "launches per step");
+    }
+    {                                                           // the form dw_run_episode_trace takes
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; episode trace: %s", episode_trace_wave(h) ? "one wave per world" : "launches per step");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

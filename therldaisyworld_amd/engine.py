@@ -421,6 +421,29 @@ class Engine:
             _ffi.ptr_u8(ok) if self.N else None))
         return (None if alive is None else alive.view(np.bool_)), ok.view(np.bool_)
 
+    def run_episode_trace(self, L_schedule, policy_mode, use_table=None, table=None, threshold_k=5):
+        """`run_episode` that also records what `reduce()` would return after every step (`dw_run_episode_trace`): the
+        daisy populations of an ensemble with grazing agents, in one device-resident run.  Returns (stats (K,B) of dtype
+        `_ffi.STATS_DTYPE` with `reserved` 0, world_alive (K,B) bool, agent_ok (K,B,N) bool); flags, state and agents are
+        `run_episode`'s for the same arguments, `world_alive == (stats["max_k"] > threshold_k)`, and the last row is
+        `reduce()` after the call."""
+        Ls = np.ascontiguousarray(L_schedule, dtype=np.float64)
+        K = Ls.shape[0]
+        ut = None if use_table is None else np.ascontiguousarray(use_table, dtype=np.uint8)
+        tb = None if table is None else np.ascontiguousarray(table, dtype=np.int8)
+        if ut is not None and ut.shape != (K,):
+            raise ValueError("use_table must have shape (K,)")
+        if tb is not None and tb.shape != (K, self.B, self.N):
+            raise ValueError(f"table must have shape {(K, self.B, self.N)}")
+        stats = np.zeros((K, self.B), dtype=_ffi.STATS_DTYPE)
+        alive = np.empty((K, self.B), dtype=np.uint8)
+        ok = np.empty((K, self.B, self.N), dtype=np.uint8)
+        self._check(self._lib.dw_run_episode_trace(
+            self._h, K, _ffi.ptr_d(Ls), int(policy_mode), _ffi.ptr_u8(ut),
+            None if tb is None else tb.ctypes.data_as(C.POINTER(C.c_int8)), int(threshold_k), _ffi.ptr_u8(alive),
+            _ffi.ptr_u8(ok) if self.N else None, stats.ctypes.data_as(C.POINTER(DwWorldStats))))
+        return stats, alive.view(np.bool_), ok.view(np.bool_)
+
     def run_episode_ensemble(self, worlds, Ls, mode, use_table=None, table=None, threshold_k=5):
         """`run_episode` with the physics constants `worlds[b]` (as `step_n_trace_ensemble` takes them) and the luminosity
         column `Ls[:, b]` of world b (`dw_run_episode_ensemble`): `Ls` is (K, B).  Each world ends, and reports the flags,

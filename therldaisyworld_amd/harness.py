@@ -284,7 +284,7 @@ def simulate_ramp(env, nsteps, obs=None, temperature=False):
     the lifeless temperature at each step's luminosity (ref :407-408), with the shape of `L`."""
     if env.n_agents:
         raise ValueError("simulate_ramp is for agent-free ensembles (n_agents == 0): with agents the reference's step(None) "
-                         "still grazes with action 0 - use simulate_lifespan")
+                         "still grazes with action 0 - use simulate_grazing (the curves) or simulate_lifespan")
     if obs is None:
         env.reset()
     eng = env._ensure_engine()
@@ -292,6 +292,78 @@ def simulate_ramp(env, nsteps, obs=None, temperature=False):
     if temperature:
         return _ramp_series(env, nsteps, eng.step_n_trace_temperature, temperature=True)
     return _ramp_series(env, nsteps, eng.step_n_trace)
+
+
+def simulate_grazing(env, agent, nsteps, chunk=64, obs=None):
+    """The `simulate_ramp` of an ensemble WITH agents: the time series of the daisy populations over the next `nsteps`
+    steps while the agents graze - the curves of the reference's animations with an agent (daisy/notebook_helpers.py:
+    218-223 `update_fig_agent`, rl_daisy_world.ipynb cells 12-16, greedy_longevity_abatement.ipynb cells 10-15 append
+    `env.grid[:, 1].mean()` and `env.grid[:, 2].mean()` after every `env.step(action)`) - without a host round trip per
+    step.  `agent`: `None` (the reference's `step(None)`: action 0) or a `Greedy` in any mode or epsilon.  `obs=None`:
+    reset the environment first.
+
+    The first step goes through `env.step` (the initial state is un-quantised); the remaining `nsteps - 1` run
+    device-resident in chunks of `chunk` steps (`dw_run_episode_trace`: policy, grazing, physics, flags and the per-step,
+    per-world reductions).  An epsilon-greedy policy's draws are taken from the legacy NumPy stream in the reference's
+    order, for exactly `nsteps` steps: the generator ends where the reference's loop leaves it.
+
+    Returns the dict of `simulate_ramp` (`L`, `mean_light`, `mean_dark`, `max_cover`, `alive`, `stats`) plus `agent_ok`
+    (n, B, N) bool - reward >= 0.1 after the step - and `agents_alive` (n, B) int, their number per world.  Afterwards
+    `env.grid`, `env.step()`, `env.L`, `env.step_count` continue as if `nsteps` calls of `env.step(agent(obs))` had been
+    made.  Precision "f64", `collision_mode == 1` and any other callable agent: the same dict from a host loop, one
+    `env.step` and one `reduce()` per step."""
+    n = int(nsteps)
+    if n < 1:
+        raise ValueError("nsteps must be at least 1")
+    K = int(chunk)
+    if K < 1:
+        raise ValueError("chunk must be at least 1")
+    if obs is None:
+        obs = env.reset()
+    B, N = int(env.batch_size), int(env.n_agents)
+    L = np.zeros(n, dtype=np.float64)
+    stats = np.zeros((n, B), dtype=_ffi.STATS_DTYPE)
+    ok = np.zeros((n, B, N), dtype=bool)
+
+    def host_step(t, obs):
+        """Step t as the notebook takes it; its row from `reduce()` and `done`."""
+        action = agent(obs) if agent is not None else None
+        L[t] = env.L
+        obs, _, done, _ = env.step(action)
+        row = env._engine.reduce()
+        for f in ("max_k", "sum_light_k", "sum_dark_k"):
+            stats[f][t] = row[f]
+        if N:
+            ok[t] = ~np.asarray(done).reshape(B, N)
+        return obs
+
+    mode = _policy_mode(agent)
+    on_device = env.precision != "f64" and env.collision_mode == 0 and mode is not None
+    obs = host_step(0, obs)
+    if not on_device:
+        for t in range(1, n):
+            obs = host_step(t, obs)
+    else:
+        eng = env._engine
+        t = 1
+        while t < n:
+            k = min(K, n - t)
+            use_table = np.zeros(k, dtype=np.uint8)
+            table = np.zeros((k, B, N), dtype=np.int8)
+            if agent is not None:                              # the reference's order: one coin per call, then the batch's actions
+                for i in range(k):
+                    if not agent.draw_branch():
+                        use_table[i] = 1
+                        table[i] = agent.draw_random_actions(B, N)[..., 0]
+            Ls = np.asarray(_luminosity_schedule(env, k), dtype=np.float64)
+            L[t:t + k] = Ls
+            stats[t:t + k], _, ok[t:t + k] = eng.run_episode_trace(Ls, mode, use_table, table, LIFESPAN_THRESHOLD_K)
+            _advance_host_scalars(env, k)
+            t += k
+    out = _series_dict(env, L, stats)
+    out["agent_ok"] = ok
+    out["agents_alive"] = ok.sum(axis=2)
+    return out
 
 
 def simulate_luminosity_sweep(env, L_values, nsteps, obs=None, temperature=False):
