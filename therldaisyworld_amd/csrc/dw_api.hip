@@ -651,6 +651,13 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
             hipLaunchKernelGGL((trace_pair_fast<MODE>), grid, dim3(256), 0, h->stream, inL, inD, o.L, o.D, g, P1, P2, o.zero_me,
                                o.zero_n, trace);
         });
+    } else if (pl.seam_strips && !pstats && !exact) {
+        const FusedGeom &gs = pl.seam_geom, &gl = pl.left_geom;
+        hipLaunchKernelGGL(step_stream_fused2_seam_pw, dim3((unsigned)gs.chunk * 8u), dim3(256), 0, h->stream, inL, inD, o.L, o.D,
+                           gs, P1, P2, o.zero_me, o.zero_n);
+        if (gl.nstrips)
+            hipLaunchKernelGGL(step_stream_fused2_left_pw, dim3((unsigned)gl.chunk * 8u), dim3(256), 0, h->stream, inL, inD, o.L,
+                               o.D, gl, P1, P2, o.zero_me, 0);
     } else if (pl.fmt_planes && !pstats && !exact) {
         hipLaunchKernelGGL((step_stream_fused2_fmt_pw<kFusedOvl>), grid, dim3(256), 0, h->stream, inL, inD, o.L, o.D, g, P1, P2,
                            o.zero_me, o.zero_n);
@@ -2562,8 +2569,16 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
                  g.chunk * 8);
         if (pl.allow_fuse) {
             const size_t n = std::strlen(buf);
-            snprintf(buf + n, buflen - n, "; dw_step_n fuses step pairs (step_stream_fused2%s%s)",
-                     p.precision == DW_PRECISION_EXACT ? "_exact" : "", pl.fmt_planes ? "_fmt_pw, format buffer accesses" : "");
+            snprintf(buf + n, buflen - n, "; dw_step_n fuses step pairs (step_stream_fused2%s%s",
+                     p.precision == DW_PRECISION_EXACT ? "_exact" : "",
+                     pl.seam_strips ? "_seam_pw, format buffer accesses" : (pl.fmt_planes ? "_fmt_pw, format buffer accesses" : ""));
+            if (pl.seam_strips) {
+                const size_t m = std::strlen(buf);
+                snprintf(buf + m, buflen - m, ", seam strips: %d x %d columns + %d columns of %d row bands per wave", pl.seam_geom.ncs,
+                         kSeamCols, pl.left_geom.cols_per_strip, pl.left_geom.wpr);
+            }
+            const size_t m = std::strlen(buf);
+            snprintf(buf + m, buflen - m, ")");
         }
     } else if (pl.kind == STEP_TILED) {
         const int TR = (256 / pl.tcq) * pl.rpt;

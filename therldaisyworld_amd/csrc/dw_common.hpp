@@ -69,6 +69,7 @@ __device__ __forceinline__ void stream_store4(plane_t* p, const float4& v) {
 typedef float dw_fmt_f32x4 __attribute__((ext_vector_type(4)));
 typedef int dw_i32x4 __attribute__((ext_vector_type(4)));
 __device__ dw_fmt_f32x4 dw_buf_load_fmt4(dw_i32x4 rsrc, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.load.format.v4f32");
+__device__ dw_f32x2 dw_buf_load_fmt2(dw_i32x4 rsrc, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.load.format.v2f32");
 __device__ void dw_buf_store_fmt4(dw_fmt_f32x4 v, dw_i32x4 rsrc, int voff, int soff, int aux) __asm("llvm.amdgcn.raw.buffer.store.format.v4f32");
 constexpr int kBufAuxNonTemporal = 2;                           // the `nt` bit of a buffer access (as stream_store4's stores)
 // The descriptor of ONE world's plane; `world` and `world_bytes` (H * W * 2 < 2^31) must be wave-uniform.  The base is a
@@ -77,18 +78,26 @@ constexpr int kBufAuxNonTemporal = 2;                           // the `nt` bit 
 //   word 3  dst_sel x/y/z/w = 4/5/6/7 [11:0] | num_format FLOAT (7) [14:12] | data_format 16_16_16_16 (12) [18:15]
 // An access whose VECTOR offset leaves the world reads zero / is dropped (the scalar offset takes no part in the
 // range check: the callers' rows are wrapped onto the torus before they become one).
-__device__ __forceinline__ dw_i32x4 fmt_plane_rsrc(const plane_t* plane, int world, unsigned int world_bytes) {
+// kFmtRsrcPairs: data_format 16_16 (5) instead - an element is TWO cells, for the 2-component loads (fmt_load2x2).
+constexpr int kFmtRsrcQuads = 0x00067FAC, kFmtRsrcPairs = 0x0002FFAC;
+__device__ __forceinline__ dw_i32x4 fmt_plane_rsrc(const plane_t* plane, int world, unsigned int world_bytes,
+                                                   int word3 = kFmtRsrcQuads) {
     const unsigned long long base = (unsigned long long)plane + (unsigned long long)world * world_bytes;
     dw_i32x4 r;
     r.x = __builtin_amdgcn_readfirstlane((int)(unsigned int)base);
     r.y = __builtin_amdgcn_readfirstlane((int)(unsigned int)(base >> 32)) & 0xffff;
     r.z = __builtin_amdgcn_readfirstlane((int)world_bytes);
-    r.w = 0x00067FAC;
+    r.w = word3;
     return r;
 }
 __device__ __forceinline__ float4 fmt_load4(const dw_i32x4& rsrc, int voff, int soff) {
     const dw_fmt_f32x4 v = dw_buf_load_fmt4(rsrc, voff, soff, 0);
     return make_float4(v.x, v.y, v.z, v.w);
+}
+// four cells as two pairs at byte offsets of their own (a kFmtRsrcPairs descriptor)
+__device__ __forceinline__ float4 fmt_load2x2(const dw_i32x4& rsrc, int voff_a, int voff_b, int soff) {
+    const dw_f32x2 a = dw_buf_load_fmt2(rsrc, voff_a, soff, 0), c = dw_buf_load_fmt2(rsrc, voff_b, soff, 0);
+    return make_float4(a.x, a.y, c.x, c.y);
 }
 __device__ __forceinline__ void fmt_store4(const dw_i32x4& rsrc, int voff, int soff, const float4& v) {
     dw_buf_store_fmt4(dw_fmt_f32x4{v.x, v.y, v.z, v.w}, rsrc, voff, soff, kBufAuxNonTemporal);

@@ -25,10 +25,13 @@ namespace dw {
 //                          choice (the first-step kernel: at most 64, the height its float32 partial sums stay exact at)
 //   DW_NO_FMT_PLANES=1     the plain overlapped-strip step pairs read and write their rows with ordinary global accesses
 //                          instead of format buffer accesses (StepPlan::fmt_planes): an A/B in one process
+//   DW_NO_SEAM_STRIPS=1    the format-access step pairs keep their overlapped 248-column strips instead of seam strips with
+//                          packed leftover columns (StepPlan::seam_strips): an A/B in one process
 //   DW_TEST_TRACE_ROWS=n   (test hook) dw_step_n_trace holds n rows of the series on the device at a time (rounded down to
 //                          even, at least 2) instead of 32 MiB of them: multi-chunk runs with a handful of worlds
 struct Switches {
-    bool no_sym = false, no_pack = false, no_fuse = false, no_ring = false, no_fmt_planes = false, no_episode_kernel = false,
+    bool no_sym = false, no_pack = false, no_fuse = false, no_ring = false, no_fmt_planes = false, no_seam_strips = false,
+         no_episode_kernel = false,
          no_episode_wave = false, no_agent_fuse = false, no_agent_preapply = false, first_f64 = false,
          first_generic = false, force_rescan = false, test_hooks = false;
     int pack_min_strips = -1, strip_rows = 0, tile_rpt = 0, queue_cap = -1, mismatch_cap = -1, trace_rows = 0;
@@ -51,7 +54,7 @@ inline Switches read_switches() {
     };
     w.test_hooks = std::getenv("DW_TEST_HOOKS") != nullptr;
     flag("DW_NO_SYM", w.no_sym); flag("DW_NO_PACK", w.no_pack); flag("DW_NO_FUSE", w.no_fuse); flag("DW_NO_RING", w.no_ring);
-    flag("DW_NO_FMT_PLANES", w.no_fmt_planes);
+    flag("DW_NO_FMT_PLANES", w.no_fmt_planes); flag("DW_NO_SEAM_STRIPS", w.no_seam_strips);
     flag("DW_NO_EPISODE_KERNEL", w.no_episode_kernel); flag("DW_NO_EPISODE_WAVE", w.no_episode_wave);
     flag("DW_NO_AGENT_FUSE", w.no_agent_fuse); flag("DW_NO_AGENT_PREAPPLY", w.no_agent_preapply);
     flag("DW_FIRST_STEP_F64", w.first_f64); flag("DW_FIRST_GENERIC", w.first_generic);
@@ -310,6 +313,9 @@ struct StepPlan {
     int fused_mode = kFusedOvl;       // ... with this strip layout (packed worlds: kFusedRot)
     bool fmt_planes = false;          // ... whose plain (no STATS, no trace) float32 launches on overlapped strips take the
                                       // format buffer access kernel (step_stream_fused2_fmt_pw)
+    bool seam_strips = false;         // ... in the seam-strip layout where that takes fewer waves (seam_layout): the launches
+    FusedGeom seam_geom{}, left_geom{};   // of step_stream_fused2_seam_pw and, if columns are left over (left_geom.nstrips
+                                      // != 0), of step_stream_fused2_left_pw
     bool trace_pairs = false;         // dw_step_n_trace records step pairs (trace_pair_fast / trace_pair_exact: un-packed
                                       // overlapped or rotating strips); otherwise single steps, a copy of B records each
     bool sym_albedo = false;          // a_dark - a_bare == -(a_light - a_bare) exactly: the exact wave-strip kernels use
@@ -346,6 +352,35 @@ inline int strip_rows_or_override(const Switches& sw, int cap, long groups, int 
     if (sw.strip_rows < 1) return strip_rows(groups, H, target);
     const int want = sw.strip_rows < cap ? sw.strip_rows : cap;
     return H < want ? H : want;
+}
+
+// The seam-strip layout of a plan with format-access step pairs (un-packed float32 pairs on overlapped strips): whole
+// strips of 252 output columns (the two halo columns on either side share ONE lane), and the L = W % 252 columns they leave
+// as overlapped strips of L / 4 + 2 lanes, G = 64 / (L / 4 + 2) row bands of a world to a wave.  Taken where it needs fewer
+// waves than the overlapped 248-column strips of f (W = 4096, 64 row bands: 64 * 16 + 22 = 1046 against 1088).
+inline long seam_waves_per_world(int W, int nrs) {
+    const int n_full = W / kSeamCols, L = W - kSeamCols * n_full;
+    const int G = L ? 64 / (L / 4 + 2) : 1;
+    return (long)nrs * n_full + (L ? (nrs + G - 1) / G : 0);
+}
+inline bool seam_layout(const FusedGeom& f, FusedGeom* seam, FusedGeom* left) {
+    const int n_full = f.W / kSeamCols, L = f.W - kSeamCols * n_full;
+    if (n_full < 1 || seam_waves_per_world(f.W, f.nrs) >= (long)f.nrs * f.ncs) return false;
+    auto launch = [](FusedGeom& g, long nstrips) {
+        g.nstrips = (int)nstrips;
+        g.nwg = (g.nstrips + 3) / 4;
+        g.chunk = (g.nwg + 7) / 8;
+    };
+    *seam = f;
+    seam->cols_per_strip = kSeamCols;
+    seam->ncs = n_full;
+    launch(*seam, (long)f.B * f.nrs * n_full);
+    *left = *seam;
+    left->cols_per_strip = L;
+    left->lpw = L ? L / 4 + 2 : 64;
+    left->wpr = 64 / left->lpw;
+    launch(*left, L ? (long)f.B * ((f.nrs + left->wpr - 1) / left->wpr) : 0);
+    return true;
 }
 
 inline StepPlan plan_steps(const dw_params& p, const Switches& sw) {
@@ -404,6 +439,7 @@ inline StepPlan plan_steps(const dw_params& p, const Switches& sw) {
         // (a world's plane is addressed by 32-bit byte offsets there)
         s.fmt_planes = p.precision == DW_PRECISION_FAST && s.allow_fuse && !s.packed && s.fused_mode == kFusedOvl && !sw.no_fmt_planes &&
                        (size_t)p.height * p.width * sizeof(plane_t) < ((size_t)1 << 31);
+        s.seam_strips = s.fmt_planes && !sw.no_seam_strips && seam_layout(f, &s.seam_geom, &s.left_geom);
     } else if (quads && p.width >= 64) {
         s.kind = STEP_TILED;
         const int Wq = p.width / 4;

@@ -118,8 +118,23 @@ __device__ inline void exact2_cell(const TI* __restrict__ pL, const TI* __restri
 // FMT (step_stream_fused2_fmt_pw below: the plain float32 kernel on overlapped strips): the rows of the row
 // loop travel through format buffer accesses (dw_common.hpp) - loaded as float32, stored from float32, their row offset
 // in a scalar register.  The repairs' scattered patches and gathers stay plain global accesses (cold).
+// SEAM (with FMT; dw_types.hpp): the two strip forms that replace the overlapped 248-column strips where they take fewer
+// waves (seam_layout, dw_plan.hpp).  Neither adds an instruction to a row map, exchanges anything between waves or
+// changes a cell's arithmetic.
+//   kSeamStrip  strip cs outputs columns 252 cs .. 252 cs + 251.  Lanes 0..62 own four columns each and write; lane 63 is
+//               the seam lane: its .x .y are the two columns right of the strip, its .z .w the two columns left of it (both
+//               wrapped onto the torus).  The horizontal neighbours come by the ROTATING moves of the W = 256 kernels, so
+//               lane 62's right neighbour is the seam lane's .x and lane 0's left neighbour its .w; the seam lane's step-1
+//               values at .x and .w are right (their outer neighbours are its own .y / .z, their inner ones lane 62's .w /
+//               lane 0's .x), its .y and .z results feed nothing that is stored.  The seam lane's halves are not adjacent
+//               in memory: a row arrives as two 2-component format loads per plane (for lanes 0..62: two columns apart).
+//   kSeamLeft   the columns that whole seam strips leave, as an overlapped strip of G.lpw lanes (a halo lane on each side,
+//               plain shifts: a move across a group's boundary lands in a halo lane's outer cell, which is unused as at
+//               lanes 0 / 63 of a whole wave) - G.wpr row bands of the same world side by side in the wave.  A lane has
+//               its band's first row, clamp and wrap of the row index and byte offsets; the row WITHIN the band is
+//               wave-uniform.  Lanes of a missing band shadow the world's last one and do not write.
 template <int MODE, bool EXACT, bool PACK = false, bool STATS = false, bool SYM = false, typename TI = plane_t,
-          typename TO = plane_t, bool TRACE = false, bool FMT = false>
+          typename TO = plane_t, bool TRACE = false, bool FMT = false, int SEAM = kSeamNone>
 __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI* __restrict__ inD,
                                             TO* __restrict__ outL, TO* __restrict__ outD, const FusedGeom& G,
                                             const PhysF32& P1_, const PhysF32& P2_, const PhysF64& P64,
@@ -130,6 +145,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     constexpr bool ROT = MODE == kFusedRot, RING = MODE == kFusedRing;
     static_assert(!RING || !PACK, "the ring exchange is written for un-packed worlds");
     static_assert(!TRACE || (!PACK && !STATS && !RING), "the trace form exists for un-packed overlapped / rotating strips");
+    static_assert(SEAM == kSeamNone || FMT, "the seam strips exist for the format-access kernel");
     static_assert(!FMT || (MODE == kFusedOvl && !EXACT && !PACK && !STATS && !TRACE), "the format-access form exists for the plain float32 kernel on overlapped strips");
     __shared__ float s_edge[RING ? 2 * 4 * 8 : 1];               // RING: [parity][wave][.w of lane 63 x4 | .x of lane 0 x4]
     __shared__ uint4 s_queue[EXACT ? 4 * kWaveQueueCap * 3 : 1];
@@ -145,12 +161,20 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     if (!RING && s >= G.nstrips) return;
     uint4* q = s_queue + (EXACT ? wv * kWaveQueueCap * 3 : 0);
     unsigned int* mm = s_mm + (EXACT ? wv * kMismatchCap : 0);
-    const int spw = G.nrs * G.ncs;
+    // (kSeamLeft: a world's strips are its groups of G.wpr row bands; r0 / nr are those of the wave's FIRST band, whose
+    // height no other band of the wave exceeds)
+    const int spw = SEAM == kSeamLeft ? (G.nrs + G.wpr - 1) / G.wpr : G.nrs * G.ncs;
     const int b = s / spw;
     const int sw = s - b * spw;
-    const int rs = sw / G.ncs, cs = sw - rs * G.ncs;
+    const int rs = SEAM == kSeamLeft ? sw * G.wpr : sw / G.ncs, cs = SEAM == kSeamLeft ? G.ncs : sw - rs * G.ncs;
     const int r0 = rs * G.SR;
     const int nr = min(G.SR, G.H - r0);
+    // kSeamLeft: the lane's place in its group, its own band (first row r0 + band_dr, band_nr rows)
+    const int band_g = SEAM == kSeamLeft ? min(lane / G.lpw, G.wpr - 1) : 0;
+    const int band_j = SEAM == kSeamLeft ? min(lane - band_g * G.lpw, G.lpw - 1) : 0;
+    const int band_rs = SEAM == kSeamLeft ? min(rs + band_g, G.nrs - 1) : 0;
+    const int band_dr = SEAM == kSeamLeft ? (band_rs - rs) * G.SR : 0;
+    const int band_nr = SEAM == kSeamLeft ? min(G.SR, G.H - band_rs * G.SR) : 0;
     const int pw = PACK ? lane / G.lpw : 0, pj = PACK ? lane - pw * G.lpw : 0;
     const int lsrc = PACK ? (pj == 0 ? lane + G.lpw - 1 : lane - 1) : 0;
     const int rsrc = PACK ? (pj == G.lpw - 1 ? lane - (G.lpw - 1) : lane + 1) : 0;
@@ -159,11 +183,17 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
         return (size_t)(PACK ? min(b * G.wpr + min((lc >> 2) / G.lpw, G.wpr - 1), G.B - 1) : b) * G.H * G.W;
     };
     const size_t woff = world_off(4 * lane);
-    const int c00 = ROT ? 0 : (RING ? 256 * __builtin_amdgcn_readfirstlane(wv) : cs * 248 - 4);   // grid column of local column 0 (OVL: may be -4)
-    int col = PACK ? 4 * pj : c00 + 4 * lane;
+    const int c00 = ROT ? 0 : (RING ? 256 * __builtin_amdgcn_readfirstlane(wv)
+                                    : (SEAM == kSeamStrip ? cs * kSeamCols : (SEAM == kSeamLeft ? cs * kSeamCols - 4 : cs * 248 - 4)));   // grid column of local column 0 (OVL: may be -4)
+    int col = PACK ? 4 * pj : c00 + 4 * (SEAM == kSeamLeft ? band_j : lane);
     col = col < 0 ? col + G.W : col;
     col = col >= G.W ? col - G.W : col;                         // W >= 256 > 252: one wrap suffices
-    const bool writes = PACK ? (pw < G.wpr && b * G.wpr + pw < G.B)
+    // kSeamStrip: the lane's second pair of columns - two further on, the seam lane's: the two left of the strip
+    int col_b = col + 2;
+    if (SEAM == kSeamStrip && lane == 63) col_b = c00 == 0 ? G.W - 2 : c00 - 2;
+    const bool writes = SEAM == kSeamStrip ? lane < 63
+                      : SEAM == kSeamLeft ? (lane < G.wpr * G.lpw && rs + band_g < G.nrs && band_j >= 1 && band_j <= G.lpw - 2)
+                      : PACK ? (pw < G.wpr && b * G.wpr + pw < G.B)
                              : ((ROT || RING) ? true : (lane >= 1 && lane <= 62 && cs * 248 + 4 * (lane - 1) < G.W));
     // which of my four step-1 cells feed an output cell of this wave (exact mode: only their ties matter)
     bool need1[4] = {true, true, true, true};
@@ -193,24 +223,36 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
 
     // FMT: one descriptor per plane of this wave's world; a lane's byte offset within a row, a row's within the world
     dw_i32x4 fmt_inL, fmt_inD, fmt_outL, fmt_outD;
-    int fmt_col = 0, fmt_row = 0;
+    int fmt_col = 0, fmt_row = 0, fmt_col_b = 0;
     if constexpr (FMT) {
         const unsigned int world_bytes = (unsigned int)(G.H * G.W) * 2u;
-        fmt_inL = fmt_plane_rsrc(inL, b, world_bytes);
-        fmt_inD = fmt_plane_rsrc(inD, b, world_bytes);
+        fmt_inL = fmt_plane_rsrc(inL, b, world_bytes, SEAM == kSeamStrip ? kFmtRsrcPairs : kFmtRsrcQuads);
+        fmt_inD = fmt_plane_rsrc(inD, b, world_bytes, SEAM == kSeamStrip ? kFmtRsrcPairs : kFmtRsrcQuads);
         fmt_outL = fmt_plane_rsrc(outL, b, world_bytes);
         fmt_outD = fmt_plane_rsrc(outD, b, world_bytes);
         fmt_col = col * 2;
+        fmt_col_b = col_b * 2;
         fmt_row = G.W * 2;
     }
     // one row of both planes as loaded (4 x binary16 each; FMT: already float32)
     struct RawIn { std::conditional_t<FMT, float4, dw_f16x4> l, d; };
     auto load_raw = [&](int rr) -> RawIn {                      // rr in [r0-2, r0+nr+1], clamped + wrapped
+        RawIn w;
+        if constexpr (SEAM == kSeamLeft) {                      // the same row of the lane's own band
+            int lr = min(rr + band_dr, r0 + band_dr + band_nr + 1);
+            lr = lr < 0 ? lr + G.H : lr;
+            lr = lr >= G.H ? lr - G.H : lr;
+            w.l = fmt_load4(fmt_inL, fmt_col + lr * fmt_row, 0);
+            w.d = fmt_load4(fmt_inD, fmt_col + lr * fmt_row, 0);
+            return w;
+        }
         rr = min(rr, r0 + nr + 1);
         rr = rr < 0 ? rr + G.H : rr;
         rr = rr >= G.H ? rr - G.H : rr;
-        RawIn w;
-        if constexpr (FMT) {
+        if constexpr (SEAM == kSeamStrip) {
+            w.l = fmt_load2x2(fmt_inL, fmt_col, fmt_col_b, rr * fmt_row);
+            w.d = fmt_load2x2(fmt_inD, fmt_col, fmt_col_b, rr * fmt_row);
+        } else if constexpr (FMT) {
             w.l = fmt_load4(fmt_inL, fmt_col, rr * fmt_row);
             w.d = fmt_load4(fmt_inD, fmt_col, rr * fmt_row);
         } else {
@@ -228,7 +270,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     };
     auto nbrs = [&](const float4& v, float& a, float& c) {
         if (PACK) { a = __shfl(v.w, lsrc, 64); c = __shfl(v.x, rsrc, 64); }
-        else if (ROT) { a = dpp_mov_nb<kDppWaveRor1>(v.w); c = dpp_mov_nb<kDppWaveRol1>(v.x); }
+        else if (ROT || SEAM == kSeamStrip) { a = dpp_mov_nb<kDppWaveRor1>(v.w); c = dpp_mov_nb<kDppWaveRol1>(v.x); }
         else { a = dpp_mov_nb<kDppWaveShr1>(v.w); c = dpp_mov_nb<kDppWaveShl1>(v.x); }   // lanes 0/63: unused
     };
     auto to_rows4 = [&](const float4& l, const float4& d, Row4& L, Row4& D) {
@@ -536,7 +578,13 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
                       j - 2);
             if (st_on) stats_step2(sm2);
             if constexpr (TRACE) trace_step2(l2, d2);
-            if constexpr (FMT) {
+            if constexpr (SEAM == kSeamLeft) {                  // (a band of fewer rows than the wave's first: no such row)
+                if (writes && j - 4 < band_nr) {
+                    const int voff = fmt_col + (r0 + band_dr + j - 4) * fmt_row;
+                    fmt_store4(fmt_outL, voff, 0, make_float4(l2[0], l2[1], l2[2], l2[3]));
+                    fmt_store4(fmt_outD, voff, 0, make_float4(d2[0], d2[1], d2[2], d2[3]));
+                }
+            } else if constexpr (FMT) {
                 if (writes) {
                     fmt_store4(fmt_outL, fmt_col, (r0 + j - 4) * fmt_row, make_float4(l2[0], l2[1], l2[2], l2[3]));
                     fmt_store4(fmt_outD, fmt_col, (r0 + j - 4) * fmt_row, make_float4(d2[0], d2[1], d2[2], d2[3]));
@@ -874,6 +922,27 @@ void step_stream_fused2_fmt_pw(const plane_t* __restrict__ inL, const plane_t* _
     const double zero = 0.0;
     fused2_body<MODE, false, false, false, false, plane_t, plane_t, false, true>(inL, inD, outL, outD, G, P1, P2, dummy, zero,
                                                                                   zero, zero_me, zero_n);
+}
+
+// The seam-strip layout of the same kernel (fused2_body, SEAM): whole 252-column strips, and the columns they leave.  One
+// launch each per step pair (the second only where columns are left; it clears nothing: zero_n = 0).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DW_FUSED_FAST_WAVES, DW_FUSED_FAST_WAVES)))
+void step_stream_fused2_seam_pw(const plane_t* __restrict__ inL, const plane_t* __restrict__ inD,
+                                plane_t* __restrict__ outL, plane_t* __restrict__ outD, FusedGeom G, PhysF32 P1, PhysF32 P2,
+                                unsigned long long* __restrict__ zero_me, int zero_n) {
+    const PhysF64 dummy{};
+    const double zero = 0.0;
+    fused2_body<kFusedOvl, false, false, false, false, plane_t, plane_t, false, true, kSeamStrip>(inL, inD, outL, outD, G, P1, P2, dummy,
+                                                                                                 zero, zero, zero_me, zero_n);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DW_FUSED_FAST_WAVES, DW_FUSED_FAST_WAVES)))
+void step_stream_fused2_left_pw(const plane_t* __restrict__ inL, const plane_t* __restrict__ inD,
+                                plane_t* __restrict__ outL, plane_t* __restrict__ outD, FusedGeom G, PhysF32 P1, PhysF32 P2,
+                                unsigned long long* __restrict__ zero_me, int zero_n) {
+    const PhysF64 dummy{};
+    const double zero = 0.0;
+    fused2_body<kFusedOvl, false, false, false, false, plane_t, plane_t, false, true, kSeamLeft>(inL, inD, outL, outD, G, P1, P2, dummy,
+                                                                                                zero, zero, zero_me, zero_n);
 }
 
 // Waves per SIMD of the exact kernels: the plain variants fit 3 waves/SIMD (151-161 VGPRs), and since the constant

@@ -112,6 +112,14 @@ struct FirstGeom {
 };
 
 enum { kFusedOvl = 0, kFusedRot = 1, kFusedRing = 2 };   // strip layout of the step pairs (dw_step_fused.hpp)
+// ... and, on overlapped strips, the strip form of the plain float32 format-access kernels (fused2_body, SEAM):
+// kSeamStrip  252 output columns per wave: lanes 0..62 own four columns each, lane 63 holds the two halo columns on either
+//             side of the strip (a FusedGeom with cols_per_strip = 252 and ncs = W / 252 whole strips)
+// kSeamLeft   the W % 252 columns that whole seam strips leave: overlapped strips of W % 252 / 4 + 2 lanes, the same columns
+//             of several row bands of one world side by side in a wave (a FusedGeom with lpw = lanes per row band, wpr = row
+//             bands per wave, ncs = W / 252, nstrips = B * ceil(nrs / wpr))
+enum { kSeamNone = 0, kSeamStrip = 1, kSeamLeft = 2 };
+constexpr int kSeamCols = 252;              // output columns of a seam strip
 constexpr int kWaveQueueCap = 256;          // near-tie entries per wave-strip held in LDS (48 B each)
 constexpr int kMismatchCap = 64;            // float32 step-1 mismatches per wave-strip held in LDS
 constexpr int kMaxFix = 1024;     // per-workgroup LDS queue of near-tie cells

@@ -33,6 +33,12 @@ def bench_line(path):
     raise SystemExit(f"no JSON line in {path}")
 
 
+def pair_kernels(names):
+    """The seam-strip layout takes a step pair in TWO launches (step_stream_fused2_seam_pw, then ..._left_pw for the columns
+    that whole strips leave): their per-launch figures add up to the pair's."""
+    return sorted(k for k in names if "fused2_seam_pw" in k or "fused2_left_pw" in k)
+
+
 def counter_avg(path, want):
     per = {}
     for r in csv.DictReader(open(path)):
@@ -62,9 +68,14 @@ for prec in ("exact", "fast"):
                                 ("single", [k for k in fetch if "step_stream" in k and "fused2" not in k], 1)):
         if not names:
             continue
-        k = max(names, key=lambda n: fetch[n][1])
-        f_kb, n = fetch[k]
-        w_kb = write[k][0]
+        both = pair_kernels(names) if label == "fused" else []
+        if both:
+            k = " + ".join(x.split("(")[0] for x in both)
+            f_kb, n, w_kb = sum(fetch[x][0] for x in both), fetch[both[0]][1], sum(write[x][0] for x in both)
+        else:
+            k = max(names, key=lambda n: fetch[n][1])
+            f_kb, n = fetch[k]
+            w_kb = write[k][0]
         hbm = (2.0 * f_kb + w_kb) * 1024.0
         entry = {"kernel": k.split("(")[0], "steps_per_launch": steps, "dispatches": n, "FETCH_SIZE_KB_avg": f_kb,
                  "WRITE_SIZE_KB_avg": w_kb, "hbm_bytes_per_launch": hbm,
@@ -72,7 +83,10 @@ for prec in ("exact", "fast"):
                  "hbm_bytes_per_cell_update": hbm / (cells * steps),
                  "read_bytes_per_cell_update": 2.0 * f_kb * 1024.0 / (cells * steps),
                  "write_bytes_per_cell_update": w_kb * 1024.0 / (cells * steps)}
-        if k in stats:
+        if both and all(x in stats for x in both):
+            entry["rocprofv3_kernel_avg_ns"] = sum(float(stats[x]["AverageNs"]) for x in both)
+            entry["rocprofv3_kernel_calls"] = int(stats[both[0]]["Calls"])
+        elif k in stats:
             entry["rocprofv3_kernel_avg_ns"] = float(stats[k]["AverageNs"])
             entry["rocprofv3_kernel_calls"] = int(stats[k]["Calls"])
         out[label] = entry
@@ -104,11 +118,13 @@ for prec in ("exact", "fast"):
         per = {}
         for r in csv.DictReader(open(path)):
             if "fused2" in r["Kernel_Name"]:
-                kernel = r["Kernel_Name"].split("(")[0]
-                per.setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
-        for k, v in per.items():
-            vals[k] = sum(v) / len(v)
-            vals[k + "_dispatches"] = len(v)
+                per.setdefault(r["Counter_Name"], {}).setdefault(r["Kernel_Name"], []).append(float(r["Counter_Value"]))
+        for k, by_kernel in per.items():
+            both = pair_kernels(by_kernel)
+            kernel = " + ".join(x.split("(")[0] for x in both) if both else next(iter(by_kernel)).split("(")[0]
+            use = both if both else list(by_kernel)[:1]
+            vals[k] = sum(sum(by_kernel[x]) / len(by_kernel[x]) for x in use)
+            vals[k + "_dispatches"] = len(by_kernel[use[0]])
     if vals:
         wave_evals = 2.0 * cells / 64.0
         d = {}
@@ -122,7 +138,7 @@ for prec in ("exact", "fast"):
         if "GRBM_GUI_ACTIVE" in vals and kernel:
             # effective clock under this load (MI355X_MICROARCH.md, DVFS give-back): GRBM_GUI_ACTIVE is summed over the 8
             # XCDs; the kernel's wall time from the --stats pass - a different run of the same command, so +-5 %
-            ns = next((float(r["AverageNs"]) for n_, r in stats.items() if n_.split("(")[0] == kernel), None)
+            ns = sum(float(r["AverageNs"]) for n_, r in stats.items() if n_.split("(")[0] in kernel.split(" + ")) or None
             if ns:
                 d["effective_clock_ghz"] = vals["GRBM_GUI_ACTIVE"] / XCDS / ns
         valu_out[prec] = {"kernel": kernel, **vals, "derived": d}
