@@ -246,6 +246,37 @@ def test_launches_per_step_run_every_world_as_if_alone(amd, monkeypatch, shape, 
     _independence(amd, monkeypatch, shape, precision, 5, switch, STEPWISE)
 
 
+def test_wave_kernel_continues_in_a_second_launch(amd, monkeypatch):
+    """The wave path keeps at most 32 MiB of rows (136 B per step and world) on the device, in whole 64-step segments: 2000
+    worlds leave 123 -> 64 steps per launch, so K = 70 takes a second launch of 6 steps that continues from the planes and
+    agents the first wrote back, with its own slices of use_table, the table and the flags.  Reference: the same call as
+    launches per step (DW_NO_EPISODE_WAVE), the form held world by world to one-world handles above; everything but the
+    count of float64 re-evaluations (a property of the kernel family) is equal bit for bit."""
+    from therldaisyworld_amd import _ffi
+    shape, K = (2000, 8, 8, 2), 70
+    B, H, W, N = shape
+    assert (32 << 20) // (136 * B) // 64 * 64 < K
+    outs = []
+    for switch, form in ((None, WAVE), ("DW_NO_EPISODE_WAVE", STEPWISE)):
+        eng = _engine(amd, B, H, W, N, "exact", monkeypatch, switch)
+        assert f"; ensemble episode: {form}" in eng.kernel_info(), eng.kernel_info()
+        tab = _table(eng, B)
+        L = _schedule(K, B)
+        codes, ut = _inputs(K, B, N, 11)
+        eng.init_random(31)
+        _quantise(eng)
+        alive, ok = eng.run_episode_ensemble(tab, L, _ffi.POLICY_ARGMIN, ut, codes, threshold_k=THRESHOLD_K)
+        outs.append((alive, ok, _everything(eng)))
+        eng.close()
+    (alive, ok, got), (ralive, rok, ref) = outs
+    assert ralive[64:].any() and rok[64:].any() and not rok[64:].all(), "nothing happens in the second launch's steps"
+    assert np.array_equal(alive, ralive) and np.array_equal(ok, rok)
+    for k in ("light", "dark", "prev_light", "prev_dark", "idx", "st", "action"):
+        assert np.array_equal(got[k], ref[k]), k
+    for f in FIELDS:
+        assert np.array_equal(got["reduce"][f], ref["reduce"][f]), f
+
+
 # ---------------------------------------------------------------------------------------------
 # 4. the degenerate table: the handle's own constants for every world, one luminosity per step
 # ---------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include <optional>
 #include <type_traits>
 #include <vector>
 
@@ -21,6 +22,7 @@
 #include "dw_host_util.hpp"
 #include "dw_plan.hpp"
 #include "dw_series.hpp"
+#include "dw_episode_staging.hpp"
 
 using namespace dw;
 
@@ -301,9 +303,6 @@ static bool episode_kernel_applies(const dw_handle* h);
 // run_episode_impl / dw_run_episode_mlp and the text of dw_kernel_info both read these two predicates.
 enum EpisodeForm { EPISODE_STEPWISE, EPISODE_WORKGROUP, EPISODE_WAVE };   // launches per step | episode_small / episode_mlp | one wave per world
 static EpisodeForm episode_form(const dw_handle* h);
-static int run_episode_trace_stepwise(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
-                                      const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
-                                      uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace);
 static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes = nullptr);
 // worlds a workgroup of the LDS-resident episode kernels holds (dw_episode.hpp: 256 / wpb threads per world)
 static int worlds_per_block(int cells) { return cells <= 256 ? 4 : (cells <= 1024 ? 2 : 1); }
@@ -315,6 +314,96 @@ static int ensure_scratch(dw_handle* h, size_t bytes) { return reserve(h->scratc
 // longer chunk after a short one does not pay a synchronous free + allocation inside a timed run
 static int ensure_ep_buf(dw_handle* h, size_t bytes) {
     return reserve(h->ep_buf, "the episode staging buffer", bytes, (size_t)4 << 20);
+}
+
+// The host side of an episode call's staging (EpisodeStaging): the handle's device buffer and, staged, its page-locked
+// image - the inputs go up in ONE copy, flags and records come back in ONE (round 3: four pageable uploads, a memset and
+// two pageable downloads - 88 us of host time per 64-step chunk of 1000 8x8 worlds against 116 us of kernel).  A direct
+// call (beyond 64 MiB; the launches per step, whose only input is the table) copies each region straight from / to the
+// caller's arrays.  Declare it in front of the call's SyncOnExit: uploads read its vectors.
+struct EpisodeBuffers {
+    using R = EpisodeStaging;
+    dw_handle* h;
+    const EpisodeStaging S;
+    unsigned char* img = nullptr;
+    std::vector<PhysF32> p32_own;                               // (direct calls)
+    std::vector<unsigned char> ut_own;
+
+    EpisodeBuffers(dw_handle* h_, const EpisodeStaging& S_) : h(h_), S(S_) {}
+    int alloc(bool staged) {
+        if (int rc = ensure_ep_buf(h, S.total)) return rc;
+        if (!staged) return DW_OK;
+        if (int rc = reserve(h->ep_pinned, "the page-locked episode staging", S.total, (size_t)1 << 20)) return rc;
+        img = h->ep_pinned.get();
+        return DW_OK;
+    }
+    template <class T = unsigned char>
+    T* dev(R::Region r) const { return S.at<T>(h->ep_buf.get(), r); }
+    // where the caller derives the float32 rows of the next upload
+    PhysF32* p32() {
+        if (img) return S.at<PhysF32>(img, R::P32);
+        p32_own.resize(S.bytes[R::P32] / sizeof(PhysF32));
+        return p32_own.data();
+    }
+    // the rows in p32(), `n_ls` luminosities; `first`: also P64 as the caller wrote it, use_table (null: zeros) and the table
+    int upload(const double* Ls, size_t n_ls, bool first, const uint8_t* use_table, const int8_t* table) {
+        const bool have_table = table && S.bn;
+        const size_t ut_bytes = S.bytes[R::USE_TABLE];
+        auto to_dev = [&](R::Region r, const void* src, size_t bytes) {
+            return bytes ? hipMemcpyAsync(dev(r), src, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
+        };
+        if (img) {
+            std::memcpy(img + S.off[R::LS], Ls, sizeof(double) * n_ls);
+            if (first) {
+                if (use_table) std::memcpy(img + S.off[R::USE_TABLE], use_table, ut_bytes);
+                else std::memset(img + S.off[R::USE_TABLE], 0, ut_bytes);
+                if (have_table) std::memcpy(img + S.off[R::TABLE], table, S.bytes[R::TABLE]);
+            }
+            const size_t upto = first ? S.input_end(have_table) : S.off[R::LS] + sizeof(double) * n_ls;
+            HIPCHK(hipMemcpyAsync(h->ep_buf.get(), img, upto, hipMemcpyHostToDevice, h->stream));
+            return DW_OK;
+        }
+        HIPCHK(to_dev(R::P32, p32_own.data(), S.bytes[R::P32]));
+        HIPCHK(to_dev(R::LS, Ls, sizeof(double) * n_ls));
+        if (ut_bytes) {
+            ut_own.assign(ut_bytes, 0);
+            if (use_table) std::memcpy(ut_own.data(), use_table, ut_bytes);
+            HIPCHK(to_dev(R::USE_TABLE, ut_own.data(), ut_bytes));
+        }
+        if (have_table) HIPCHK(to_dev(R::TABLE, table, S.bytes[R::TABLE]));
+        return DW_OK;
+    }
+    // flags and records come back (staged: the one span that covers what the caller wants), the stream is synchronised
+    int finish(uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace) {
+        if (!S.bn) agent_ok = nullptr;
+        struct { void* dst; R::Region r; } out[3] = {{world_alive, R::WORLD_ALIVE}, {agent_ok, R::AGENT_OK}, {trace, R::TRACE}};
+        size_t lo = S.total, hi = 0;
+        for (const auto& o : out) {
+            if (!o.dst) continue;
+            if (!img) HIPCHK(hipMemcpyAsync(o.dst, dev(o.r), S.bytes[o.r], hipMemcpyDeviceToHost, h->stream));
+            lo = S.off[o.r] < lo ? S.off[o.r] : lo;
+            hi = S.end(o.r) > hi ? S.end(o.r) : hi;
+        }
+        if (img && hi > lo) HIPCHK(hipMemcpyAsync(img + lo, h->ep_buf.get() + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (img)
+            for (const auto& o : out)
+                if (o.dst) std::memcpy(o.dst, img + S.off[o.r], S.bytes[o.r]);
+        return DW_OK;
+    }
+};
+
+// What the LDS-resident episode launches pass alike (EpisodeIO and EpisodeMlpIO): the planes in place, the agents, the
+// reductions of the current state, and the float32 sets and luminosities of the steps in the staging buffer
+template <class IO>
+static void fill_episode_io(IO& io, const dw_handle* h, const EpisodeStaging& S) {
+    const int cur = h->cur, prev = 1 - h->cur;
+    io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
+    io.idx = h->idx.get(); io.st = h->st.get();
+    io.P32 = S.at<const PhysF32>(h->ep_buf.get(), EpisodeStaging::P32);
+    io.Ls = S.at<const double>(h->ep_buf.get(), EpisodeStaging::LS);
+    io.stats = h->stats2[h->sp].get();
+    io.fixups = &io.stats[h->prm.batch].sum_l;
 }
 
 // Dynamic LDS above the default limit: the attribute belongs to the device's copy of the kernel (a handle is bound to
@@ -1785,12 +1874,13 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
         NEED(!member_b || (member_b[b] >= 0 && member_b[b] < n_members), DW_EINVAL, "world %d: member out of range", b);
     }
     NEED(n_members == 1 || (member_a && member_b), DW_EINVAL, "several parameter sets need both member maps");
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t wbytes = sizeof(double) * 1808 * (size_t)n_members;
-    const size_t o_ma = 0, o_mb = up(o_ma + sizeof(int) * B), o_r = up(o_mb + sizeof(int) * B);
-    const size_t o_d = up(o_r + sizeof(double) * K * bn), o_p32 = up(o_d + K * bn), o_ls = up(o_p32 + sizeof(PhysF32) * K);
-    const size_t total = up(o_ls + sizeof(double) * K);
-    if (int erc = ensure_ep_buf(h, total)) return erc;
+    EpisodeRegions regions;
+    regions.rows = K; regions.mlp = true;
+    const EpisodeStaging S(K, (size_t)B, (size_t)N, regions);
+    using R = EpisodeStaging;
+    const size_t o_ma = S.off[R::MEMBER_A], o_mb = S.off[R::MEMBER_B], o_p32 = S.off[R::P32], o_ls = S.off[R::LS];
+    if (int erc = ensure_ep_buf(h, S.total)) return erc;
     if (params) {                                               // the sets stay on the device for later calls (params == NULL)
         if (h->mlp_members != n_members) {
             h->mlp_w.reset();
@@ -1802,8 +1892,8 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     const double* d_w = h->mlp_w.get();
     const int* d_ma = member_a ? reinterpret_cast<const int*>(h->ep_buf.get() + o_ma) : nullptr;
     const int* d_mb = member_b ? reinterpret_cast<const int*>(h->ep_buf.get() + o_mb) : nullptr;
-    double* d_r = reinterpret_cast<double*>(h->ep_buf.get() + o_r);
-    unsigned char* d_d = h->ep_buf.get() + o_d;
+    double* d_r = S.at<double>(h->ep_buf.get(), R::REWARD);
+    unsigned char* d_d = S.at<unsigned char>(h->ep_buf.get(), R::DONE);
     SyncOnExit guard(h->stream);                              // params / member maps are the caller's
     if (params) HIPCHK(hipMemcpyAsync(h->mlp_w.get(), params, wbytes, hipMemcpyHostToDevice, h->stream));
     if (member_a) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ma, member_a, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
@@ -1830,14 +1920,9 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
             StatsDev* stats = h->stats2[h->sp].get();
             if (!wave_kernel) HIPCHK(hipMemsetAsync(stats, 0, sizeof(StatsDev) * (B + 1), h->stream));   // (the wave kernel assigns every record)
             EpisodeMlpIO io;
-            const int cur = h->cur, prev = 1 - h->cur;
-            io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
-            io.idx = h->idx.get(); io.st = h->st.get();
-            io.P32 = reinterpret_cast<const PhysF32*>(h->ep_buf.get() + o_p32);
-            io.Ls = reinterpret_cast<const double*>(h->ep_buf.get() + o_ls);
+            fill_episode_io(io, h, S);
             io.weights = d_w; io.member_a = d_ma; io.member_b = d_mb;
             io.reward = d_r + t * bn; io.done = d_d + t * bn;
-            io.stats = stats; io.fixups = &stats[B].sum_l;
             io.action = h->action.get();
             const bool ex = p.precision == DW_PRECISION_EXACT;
             if (wave_kernel) {
@@ -1954,7 +2039,7 @@ static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes) {
 
 static bool episode_kernel_applies(const dw_handle* h) { return episode_form(h) != EPISODE_STEPWISE && cur_quantised(h); }
 
-// The agents' part of a step of the stepwise episode loops: the actions of policy_mode - or, `from_table`, the caller's
+// The agents' part of a step of the stepwise episode loop: the actions of policy_mode - or, `from_table`, the caller's
 // slice `codes` [B*N] (-1 / -2: greedy / anti-greedy) - into h->action, then grazing (d_ok: the ok flags straight from it)
 static int launch_policy(dw_handle* h, int policy_mode, bool from_table, const unsigned char* codes, unsigned char* d_ok = nullptr) {
     const size_t bn = (size_t)h->prm.batch * h->prm.n_agents;
@@ -1971,89 +2056,111 @@ static int launch_policy(dw_handle* h, int policy_mode, bool from_table, const u
     return launch_agents(h, h->action.get(), h->prm.batch, h->prm.n_agents, false, nullptr, nullptr, d_ok);
 }
 
-// What both LDS-resident episode launches pass alike: the planes in place, the agents, the reductions of the current
-// state, and the float32 sets and luminosities of the steps at offsets of the staging buffer
-static EpisodeIO episode_io(const dw_handle* h, int policy_mode, size_t o_p32, size_t o_ls) {
+// What fill_episode_io fills, and the table and the flags of the steps from `t0` on.  The one-wave-per-world kernels (`wave`) take a null
+// use_table / table where the caller gave none.
+static EpisodeIO episode_io(const dw_handle* h, int policy_mode, const EpisodeStaging& S, size_t t0, bool wave, bool have_use_table,
+                            bool have_table) {
+    using R = EpisodeStaging;
+    unsigned char* dev = h->ep_buf.get();
     EpisodeIO io{};
-    const int cur = h->cur, prev = 1 - h->cur;
-    io.L = h->L16[cur].get(); io.D = h->D16[cur].get(); io.prevL = h->L16[prev].get(); io.prevD = h->D16[prev].get();
-    io.idx = h->idx.get(); io.st = h->st.get();
-    io.P32 = reinterpret_cast<const PhysF32*>(h->ep_buf.get() + o_p32);
-    io.Ls = reinterpret_cast<const double*>(h->ep_buf.get() + o_ls);
-    io.stats = h->stats2[h->sp].get();
-    io.fixups = &io.stats[h->prm.batch].sum_l;
+    fill_episode_io(io, h, S);
+    io.use_table = wave && !have_use_table ? nullptr : dev + S.off[R::USE_TABLE] + t0;
+    io.table = wave && !have_table ? nullptr : reinterpret_cast<const signed char*>(dev + S.off[R::TABLE] + t0 * S.bn);
+    io.world_alive = dev + S.off[R::WORLD_ALIVE] + t0 * S.B;
+    io.agent_ok = dev + S.off[R::AGENT_OK] + t0 * S.bn;
     io.action = (h->prm.n_agents > 0 && policy_mode != kPolicySkipAgents) ? h->action.get() : nullptr;
     return io;
 }
 
-// dw_run_episode for worlds that do not fit LDS: the same K steps as K x (policy, dw_step) issued
-// back-to-back on the handle's stream - policy kernel or table slice -> update_agents -> step kernel ->
-// flags from the step's reductions - with no host round trip in between; one synchronisation at the end.
+// An episode for shapes without an LDS-resident kernel: the same K steps as K x (policy, dw_step) issued back-to-back on
+// the handle's stream - policy kernel or table slice -> update_agents -> step kernel -> flags from the step's reductions
+// (`trace`, dw_run_episode_trace: and episode_stats_row_pw, which copies them into row t of the records) - with no host
+// round trip in between; one synchronisation at the end.  With `worlds` (dw_run_episode_ensemble; `sym`: for
+// launch_forward_pw) the step is that per-world single step of dw_step_n_trace_ensemble, from rows that go up as in the
+// trace calls (PwTable, the table chunks of plan_series without the test hook).  Fused step pairs only without either: the
+// step-1 sums of a pair would have to include the patch kernel's corrections, and the pair kernels take one constant set.
 static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
-                                const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
-                                uint8_t* world_alive, uint8_t* agent_ok) {
+                                const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
+                                uint8_t* agent_ok, dw_world_stats* trace, WorldRows* worlds = nullptr, bool sym = false) {
+    using R = EpisodeStaging;
     const dw_params& p = h->prm;
     const int N = p.n_agents, B = p.batch;
-    const size_t K = (size_t)nsteps, bn = (size_t)B * N;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_tab = 0, o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * B), o_code = up(o_ok + K * bn);
-    const size_t o_ps = up(o_code + bn), total = up(o_ps + sizeof(unsigned int) * 2 * B) + 256;
-    if (int erc = ensure_ep_buf(h, total)) return erc;
-    SyncOnExit guard(h->stream);                              // `table` is the caller's
-    if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
+    const size_t K = (size_t)nsteps, Bz = (size_t)B, bn = Bz * N;
+    const bool plain = !trace && !worlds;
+    EpisodeRegions regions;
+    regions.trace = trace != nullptr; regions.pairs = plain; regions.slack = 256;
+    EpisodeBuffers E(h, EpisodeStaging(K, Bz, (size_t)N, regions));
+    SeriesSchedule q;
+    std::optional<PwTable> tab;
+    if (worlds) {
+        q = plan_series(SeriesSpec{nsteps, Bz, sizeof(StatsDev), 0, 0, false, false, true, false, L_schedule});   // (single steps, no hook)
+        tab.emplace(h, PwLayout(Bz, q.trows));
+    }
+    if (int rc = E.alloc(false)) return rc;
+    if (tab)
+        if (int rc = tab->alloc("the per-world constants", {tab->item()})) return rc;
+    SyncOnExit guard(h->stream);                              // `table`, the flag arrays and `trace` are the caller's
+    if (int rc = E.upload(nullptr, 0, true, nullptr, table)) return rc;
+    unsigned char* const d_tab = E.dev(R::TABLE);
+    unsigned char* const d_wa = E.dev(R::WORLD_ALIVE);
+    unsigned char* const d_ok = E.dev(R::AGENT_OK);
+    unsigned char* const d_code = E.dev(R::CODE);
+    StatsDev* const rows = E.dev<StatsDev>(R::TRACE);
     const int nflag = B > (int)bn ? B : (int)bn;
+    // (with per-world constants DW_POLICY_ZEROS wins over use_table, without them use_table wins: DESIGN.md 3.2j)
+    const bool table_steps = use_table && !(worlds && policy_mode == DW_POLICY_ZEROS);
+    auto from_table = [&](size_t t) { return policy_mode == DW_POLICY_TABLE || (table_steps && use_table[t]); };
     // Step pairs on wide grids (dw_agents_fused.hpp): policy_t, graze_t, ONE fused launch for forward_t and
     // forward_{t+1}, then the agents' step t+1 recomputed around the agents and patched into the result.
     // Needs no per-step world reductions (the caller passed world_alive == NULL); the last step of the
     // call stays an ordinary step, so the handle ends exactly as after K calls of dw_step.
-    const bool may_pair = h->plan.allow_fuse && bn && N <= kLookaheadMaxAgents && policy_mode != kPolicySkipAgents &&
+    const bool may_pair = plain && h->plan.allow_fuse && bn && N <= kLookaheadMaxAgents && policy_mode != kPolicySkipAgents &&
                           !h->sw.no_agent_fuse;
     // With per-step world flags the fused launch also reduces what the flags of both steps need (STATS
     // variants: exact step-1 maximum, count of certain step-2 values above the threshold).
-    unsigned int* pstats = world_alive ? reinterpret_cast<unsigned int*>(h->ep_buf.get() + o_ps) : nullptr;
+    unsigned int* pstats = (plain && world_alive) ? E.dev<unsigned int>(R::PAIR_STATS) : nullptr;
     // zeroed once: every agents_lookahead_patch launch leaves its world's words cleared for the next pair
     if (pstats && may_pair) HIPCHK(hipMemsetAsync(pstats, 0, sizeof(unsigned int) * 2 * B, h->stream));
     // action codes of a pair's second step when they come from no table: one byte value for the whole episode
     const int uniform_code = policy_mode == DW_POLICY_ZEROS ? 0 : (policy_mode == DW_POLICY_ARGMIN ? 0xFE : 0xFF);
-    if (may_pair && policy_mode != DW_POLICY_TABLE)
-        HIPCHK(hipMemsetAsync(h->ep_buf.get() + o_code, uniform_code, bn, h->stream));
+    if (may_pair && policy_mode != DW_POLICY_TABLE) HIPCHK(hipMemsetAsync(d_code, uniform_code, bn, h->stream));
     // policy + update_agents of the step after a pair run inside that pair's patch kernel (phase E) while the chunk
     // continues: two launches per pair instead of four (DW_NO_AGENT_PREAPPLY: experiments)
     const bool no_preapply = h->sw.no_agent_preapply;
     bool pre_applied = false;
+    size_t c = 0;                                               // (worlds) the table chunk that starts next
     for (size_t t = 0; t < K; ++t) {
+        if (tab && (int)t == (c ? q.chunks[c - 1].end : 0)) {
+            if (int rc = tab->next_chunk(q, c, L_schedule, *worlds)) return rc;
+            ++c;
+        }
         const bool pair = may_pair && cur_quantised(h) && K - t >= 3;
         if (pre_applied) {
             pre_applied = false;                             // step t's policy and grazing were done by the last patch
         } else if (bn && policy_mode != kPolicySkipAgents) {
             // a pair's first step: the agents' ok flags straight from the grazing kernel
-            if (int rc = launch_policy(h, policy_mode, use_table && use_table[t], h->ep_buf.get() + o_tab + t * bn,
-                                       pair ? h->ep_buf.get() + o_ok + t * bn : nullptr)) return rc;
+            if (int rc = launch_policy(h, policy_mode, from_table(t), d_tab + t * bn, pair ? d_ok + t * bn : nullptr)) return rc;
         }
         if (pair) {
             const double L1 = L_schedule[t], L2 = L_schedule[t + 1];
             int rc = launch_forward_fused2(h, L1, L2, pstats, (float)threshold_k);   // pstats: zero (see above)
             if (rc) return rc;
-            // codes of step t+1: the caller's table slice, or one byte value for the whole ensemble
-            const bool tab2 = policy_mode == DW_POLICY_TABLE || (use_table && use_table[t + 1]);
-            unsigned char* codes = tab2 ? h->ep_buf.get() + o_tab + (t + 1) * bn : h->ep_buf.get() + o_code;
-            LookaheadArgs A;
+            LookaheadArgs A;                                 // (codes: the caller's table slice, or the uniform byte)
             A.inL = h->L16[1 - h->cur].get(); A.inD = h->D16[1 - h->cur].get();
             A.outL = h->L16[h->cur].get(); A.outD = h->D16[h->cur].get();
             A.idx = h->idx.get(); A.st = h->st.get();
-            A.code = reinterpret_cast<const signed char*>(codes);
-            A.agent_ok = h->ep_buf.get() + o_ok + (t + 1) * bn;
+            A.code = reinterpret_cast<const signed char*>(from_table(t + 1) ? d_tab + (t + 1) * bn : d_code);
+            A.agent_ok = d_ok + (t + 1) * bn;
             A.code_next = nullptr;
             A.agent_ok_next = nullptr;
             A.action_out = h->action.get();
             if (t + 2 < K && !no_preapply) {                   // the chunk continues with step t+2
-                const bool tab3 = policy_mode == DW_POLICY_TABLE || (use_table && use_table[t + 2]);
-                A.code_next = reinterpret_cast<const signed char*>(tab3 ? h->ep_buf.get() + o_tab + (t + 2) * bn : h->ep_buf.get() + o_code);
-                A.agent_ok_next = h->ep_buf.get() + o_ok + (t + 2) * bn;
+                A.code_next = reinterpret_cast<const signed char*>(from_table(t + 2) ? d_tab + (t + 2) * bn : d_code);
+                A.agent_ok_next = d_ok + (t + 2) * bn;
                 pre_applied = true;
             }
-            A.alive_t = pstats ? h->ep_buf.get() + o_wa + t * B : nullptr;
-            A.alive_t1 = pstats ? h->ep_buf.get() + o_wa + (t + 1) * B : nullptr;
+            A.alive_t = pstats ? d_wa + t * Bz : nullptr;
+            A.alive_t1 = pstats ? d_wa + (t + 1) * Bz : nullptr;
             A.pstats = pstats; A.thr = threshold_k;
             A.B = B; A.N = N; A.H = p.height; A.W = p.width; A.mask = p.obs_mask;
             A.agent_gamma = p.agent_gamma;
@@ -2067,15 +2174,20 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
             ++t;                                             // two steps done
             continue;
         }
-        int rc = launch_forward(h, L_schedule[t]);
-        if (rc) return rc;
+        if (tab) {
+            const size_t tr = q.row_of[t];
+            if (int rc = launch_forward_pw(h, tab->lay.p32(tab->dev(), tr), tab->lay.p64(tab->dev(), tr), tab->lay.fb(tab->dev()), sym, true)) return rc;
+        } else if (int rc = launch_forward(h, L_schedule[t])) {
+            return rc;
+        }
         hipLaunchKernelGGL(episode_flags, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, h->stream,
-                           h->stats2[h->sp].get(), h->st.get(), B, N, threshold_k, h->ep_buf.get() + o_wa + t * B, h->ep_buf.get() + o_ok + t * bn);
+                           h->stats2[h->sp].get(), h->st.get(), B, N, threshold_k, d_wa + t * Bz, d_ok + t * bn);
+        if (trace)
+            hipLaunchKernelGGL(episode_stats_row_pw, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream,
+                               h->stats2[h->sp].get(), B, rows + t * Bz);
         HIPCHK(hipGetLastError());
     }
-    if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * B, hipMemcpyDeviceToHost, h->stream));
-    if (agent_ok && bn) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (int rc = E.finish(world_alive, agent_ok, trace)) return rc;
     guard.disarm();
     return DW_OK;
 }
@@ -2096,7 +2208,7 @@ static int check_episode_call(const dw_handle* h, int32_t nsteps, int policy_mod
 }
 
 // `trace` (dw_run_episode_trace): also the records of every step, [K][B]; the one-wave-per-world form takes
-// episode_wave_stats_pw, every other form launches per step (run_episode_trace_stepwise).
+// episode_wave_stats_pw, every other form launches per step: no LDS workgroup kernel, the stated price of the records.
 static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                             const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
                             uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace) {
@@ -2105,77 +2217,37 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     if (int rc = check_episode_call(h, nsteps, policy_mode, use_table, table)) return rc;
     const int C = p.height * p.width, N = p.n_agents, B = p.batch;
     const EpisodeForm form = episode_form(h);                  // (F64 / collision_mode 1 were rejected above)
-    if (trace && form != EPISODE_WAVE)
-        return run_episode_trace_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
-                                          agent_ok, trace);
-    if (form == EPISODE_STEPWISE)
-        return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
-                                    agent_ok);
+    if (form == EPISODE_STEPWISE || (trace && form != EPISODE_WAVE))
+        return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace);
     const bool wave_kernel = form == EPISODE_WAVE;
     const int wpb = worlds_per_block(C);
     const size_t world_bytes = wave_kernel ? episode_wave_world_bytes(C, N) : episode_world_bytes(C, N);
     const size_t lds = trace ? episode_wave_stats_lds_bytes(C, N)     // (<= 64 KB for every shape of the form: static_assert there)
                              : world_bytes * wpb + (wave_kernel ? episode_wave_shared_bytes() : 0);
     NEED(lds <= 160 * 1024, DW_EINVAL, "too many agents for the LDS-resident episode kernel");
-    // device staging: [P32 K][Ls K][use_table K][table K*B*N] | [world_alive K*B][agent_ok K*B*N][trace K*B records]
-    const size_t K = (size_t)nsteps, bn = (size_t)B * N;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_p32 = 0, o_ls = up(o_p32 + sizeof(PhysF32) * K), o_ut = up(o_ls + sizeof(double) * K);
-    const size_t o_tab = up(o_ut + K), o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * B), o_tr = up(o_ok + K * bn);
-    const size_t tr_bytes = trace ? sizeof(StatsDev) * K * B : 0, total = up(o_tr + tr_bytes);
-    if (int erc = ensure_ep_buf(h, total)) return erc;
-    // The inputs are assembled in a page-locked image of the staging buffer and go up in ONE copy; the flags come back
-    // in ONE copy (round 3: four pageable uploads, a memset and two pageable downloads per chunk - 88 us of host time
-    // per 64-step chunk of 1000 8x8 worlds against 116 us of kernel).  Beyond 64 MiB: straight from / to the caller's arrays.
-    const bool staged = total <= ((size_t)64 << 20);
-    if (staged)
-        if (int rc = reserve(h->ep_pinned, "the page-locked episode staging", total, (size_t)1 << 20)) return rc;
-    std::vector<PhysF32> p32_own;
-    std::vector<unsigned char> ut_own;
-    PhysF32* p32 = nullptr;
-    unsigned char* ut = nullptr;
-    if (staged) {
-        p32 = reinterpret_cast<PhysF32*>(h->ep_pinned.get() + o_p32);
-        ut = h->ep_pinned.get() + o_ut;
-    } else {
-        p32_own.resize(K); ut_own.resize(K);
-        p32 = p32_own.data(); ut = ut_own.data();
-    }
+    const size_t K = (size_t)nsteps;
+    EpisodeRegions regions;
+    regions.rows = K; regions.use_table = true; regions.trace = trace != nullptr;
+    EpisodeBuffers E(h, EpisodeStaging(K, (size_t)B, (size_t)N, regions));
+    if (int rc = E.alloc(E.S.fits_image())) return rc;
+    PhysF32* p32 = E.p32();
     for (size_t t = 0; t < K; ++t) p32[t] = derive_f32(p, L_schedule[t]);
-    if (use_table) std::memcpy(ut, use_table, K); else std::memset(ut, 0, K);
-    SyncOnExit guard(h->stream);                              // the images above and the caller's arrays
-    if (staged) {
-        std::memcpy(h->ep_pinned.get() + o_ls, L_schedule, sizeof(double) * K);
-        if (table && bn) std::memcpy(h->ep_pinned.get() + o_tab, table, K * bn);
-        HIPCHK(hipMemcpyAsync(h->ep_buf.get(), h->ep_pinned.get(), (table && bn) ? o_tab + K * bn : o_ut + K, hipMemcpyHostToDevice, h->stream));
-    } else {
-        HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_p32, p32, sizeof(PhysF32) * K, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ls, L_schedule, sizeof(double) * K, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ut, ut, K, hipMemcpyHostToDevice, h->stream));
-        if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
-    }
+    SyncOnExit guard(h->stream);                              // E's images and the caller's arrays
+    if (int rc = E.upload(L_schedule, K, true, use_table, table)) return rc;
     StatsDev* stats = h->stats2[h->sp].get();
     // episode_wave ASSIGNS every world's whole record (its float64 count in `reserved`) and the counter record behind them:
     // nothing to clear; episode_small accumulates: cleared as before
     if (!wave_kernel) HIPCHK(hipMemsetAsync(stats, 0, sizeof(StatsDev) * (B + 1), h->stream));
-    EpisodeIO io = episode_io(h, policy_mode, o_p32, o_ls);
-    io.use_table = h->ep_buf.get() + o_ut;
-    io.table = reinterpret_cast<const signed char*>(h->ep_buf.get() + o_tab);
-    io.world_alive = h->ep_buf.get() + o_wa;
-    io.agent_ok = h->ep_buf.get() + o_ok;
+    const EpisodeIO io = episode_io(h, policy_mode, E.S, 0, wave_kernel, use_table != nullptr, table && E.S.bn);
     const PhysF64 P64 = make_f64(p, L_schedule[0]);
     const dim3 grid((unsigned)((B + wpb - 1) / wpb));
     const bool ex = p.precision == DW_PRECISION_EXACT;
     if (trace) {
-        io.use_table = use_table ? h->ep_buf.get() + o_ut : nullptr;
-        io.table = (table && bn) ? io.table : nullptr;
         auto kern = ex ? episode_wave_stats_pw<true> : episode_wave_stats_pw<false>;
-        const EpisodeWaveStatsArgs A{io, reinterpret_cast<StatsDev*>(h->ep_buf.get() + o_tr), B, N, p.height, p.width, nsteps,
+        const EpisodeWaveStatsArgs A{io, E.dev<StatsDev>(EpisodeStaging::TRACE), B, N, p.height, p.width, nsteps,
                                      policy_mode, p.obs_mask, threshold_k, p.agent_gamma, P64};
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, h->stream, A);
     } else if (wave_kernel) {
-        io.use_table = use_table ? h->ep_buf.get() + o_ut : nullptr;
-        io.table = (table && bn) ? io.table : nullptr;
         auto kern = ex ? episode_wave<true> : episode_wave<false>;
         if (int rc = set_lds_limit(h, kern, lds)) return rc;
         const EpisodeWaveArgs A{io, B, N, p.height, p.width, nsteps, policy_mode, p.obs_mask, threshold_k, p.agent_gamma, P64};
@@ -2187,71 +2259,16 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
                            p.obs_mask, p.agent_gamma, threshold_k, P64);
     }
     HIPCHK(hipGetLastError());
-    const bool want_ok = agent_ok && bn;
-    if (staged) {
-        if (world_alive || want_ok || trace) {                  // flags and records: ONE download
-            const size_t lo = world_alive ? o_wa : (want_ok ? o_ok : o_tr);
-            const size_t hi = trace ? o_tr + tr_bytes : (want_ok ? o_ok + K * bn : o_wa + K * B);
-            HIPCHK(hipMemcpyAsync(h->ep_pinned.get() + lo, h->ep_buf.get() + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
-        }
-    } else {
-        if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * B, hipMemcpyDeviceToHost, h->stream));
-        if (want_ok) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
-        if (trace) HIPCHK(hipMemcpyAsync(trace, h->ep_buf.get() + o_tr, tr_bytes, hipMemcpyDeviceToHost, h->stream));
-    }
     episode_done(h, L_schedule[K - 1], false);
     release_unquantised(h);
-    HIPCHK(hipStreamSynchronize(h->stream));      // flags are returned
+    if (int rc = E.finish(world_alive, agent_ok, trace)) return rc;      // flags are returned
     guard.disarm();
-    if (staged) {
-        if (world_alive) std::memcpy(world_alive, h->ep_pinned.get() + o_wa, K * B);
-        if (want_ok) std::memcpy(agent_ok, h->ep_pinned.get() + o_ok, K * bn);
-        if (trace) std::memcpy(trace, h->ep_pinned.get() + o_tr, tr_bytes);
-    }
     return DW_OK;
 }
 
 // ---- dw_run_episode_trace: dw_run_episode with the records of every step ------------------------------------------
 // The form the call takes: one wave per world (episode_wave_stats_pw) wherever dw_run_episode takes episode_wave; every
 // other shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step
-static bool episode_trace_wave(const dw_handle* h) { return episode_form(h) == EPISODE_WAVE; }
-
-// Launches per step from existing kernels, exactly as run_episode_stepwise issues them with pairing off - policy kernel
-// or table slice, update_agents, launch_forward, episode_flags - plus episode_stats_row_pw, which copies the step's
-// reductions into row t of the trace; one synchronisation at the end.  No fused step pairs (the step-1 sums of a pair
-// would have to include the patch kernel's corrections) and no LDS workgroup kernel: the stated price of the records.
-static int run_episode_trace_stepwise(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
-                                      const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
-                                      uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace) {
-    const dw_params& p = h->prm;
-    const int N = p.n_agents, B = p.batch;
-    const size_t K = (size_t)nsteps, bn = (size_t)B * N, Bz = (size_t)B;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_tab = 0, o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * Bz), o_tr = up(o_ok + K * bn);
-    const size_t total = up(o_tr + sizeof(StatsDev) * K * Bz) + 256;
-    if (int erc = ensure_ep_buf(h, total)) return erc;
-    SyncOnExit guard(h->stream);                                // `table`, the flag arrays and `trace` are the caller's
-    if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
-    const int nflag = B > (int)bn ? B : (int)bn;
-    StatsDev* const rows = reinterpret_cast<StatsDev*>(h->ep_buf.get() + o_tr);
-    for (size_t t = 0; t < K; ++t) {
-        if (bn && policy_mode != kPolicySkipAgents)
-            if (int rc = launch_policy(h, policy_mode, use_table && use_table[t], h->ep_buf.get() + o_tab + t * bn)) return rc;
-        if (int rc = launch_forward(h, L_schedule[t])) return rc;
-        hipLaunchKernelGGL(episode_flags, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, h->stream, h->stats2[h->sp].get(),
-                           h->st.get(), B, N, threshold_k, h->ep_buf.get() + o_wa + t * Bz, h->ep_buf.get() + o_ok + t * bn);
-        hipLaunchKernelGGL(episode_stats_row_pw, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream,
-                           h->stats2[h->sp].get(), B, rows + t * Bz);
-        HIPCHK(hipGetLastError());
-    }
-    if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * Bz, hipMemcpyDeviceToHost, h->stream));
-    if (agent_ok && bn) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(trace, rows, sizeof(StatsDev) * K * Bz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    guard.disarm();
-    return DW_OK;
-}
-
 int dw_run_episode_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                          const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
                          uint8_t* agent_ok, dw_world_stats* trace) {
@@ -2263,49 +2280,7 @@ int dw_run_episode_trace(dw_handle* h, int32_t nsteps, const double* L_schedule,
 
 // ---- dw_run_episode_ensemble: dw_run_episode with a set of physics constants and a luminosity column per world --------
 // The form the call takes: one wave per world (episode_wave_pw) wherever dw_run_episode takes episode_wave; every other
-// shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step
-static bool ensemble_episode_wave(const dw_handle* h) { return episode_form(h) == EPISODE_WAVE; }
-
-// Launches per step from existing kernels - launch_policy, launch_forward_pw (the per-world single step of
-// dw_step_n_trace_ensemble), episode_flags - with one synchronisation at the end; no fused pairs and no LDS workgroup
-// kernel.  The rows go up as in the trace calls (PwTable, the table chunks of plan_series without the test hook).
-static int run_episode_ensemble_stepwise(dw_handle* h, int32_t nsteps, WorldRows& worlds, bool sym, const double* L_schedule,
-                                         int policy_mode, const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
-                                         uint8_t* world_alive, uint8_t* agent_ok) {
-    const dw_params& p = h->prm;
-    const int N = p.n_agents, B = p.batch;
-    const size_t K = (size_t)nsteps, bn = (size_t)B * N, Bz = (size_t)B;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_tab = 0, o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * Bz), total = up(o_ok + K * bn) + 256;
-    const SeriesSchedule q = plan_series(SeriesSpec{nsteps, Bz, sizeof(StatsDev), 0, 0, false, false, true, false, L_schedule});   // (single steps, no hook)
-    PwTable tab(h, PwLayout(Bz, q.trows));
-    if (int rc = ensure_ep_buf(h, total)) return rc;
-    if (int rc = tab.alloc("the per-world constants", {tab.item()})) return rc;
-    SyncOnExit guard(h->stream);                                // `table` and the flag arrays are the caller's
-    if (table && bn) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_tab, table, K * bn, hipMemcpyHostToDevice, h->stream));
-    const int nflag = B > (int)bn ? B : (int)bn;
-    size_t c = 0;                                               // the table chunk that starts next
-    for (size_t t = 0; t < K; ++t) {
-        if ((int)t == (c ? q.chunks[c - 1].end : 0)) {
-            if (int rc = tab.next_chunk(q, c, L_schedule, worlds)) return rc;
-            ++c;
-        }
-        if (bn)
-            if (int rc = launch_policy(h, policy_mode, policy_mode != DW_POLICY_ZEROS && use_table && use_table[t],
-                                       h->ep_buf.get() + o_tab + t * bn)) return rc;
-        const size_t tr = q.row_of[t];
-        if (int rc = launch_forward_pw(h, tab.lay.p32(tab.dev(), tr), tab.lay.p64(tab.dev(), tr), tab.lay.fb(tab.dev()), sym, true)) return rc;
-        hipLaunchKernelGGL(episode_flags, dim3((unsigned)((nflag + 255) / 256)), dim3(256), 0, h->stream, h->stats2[h->sp].get(),
-                           h->st.get(), B, N, threshold_k, h->ep_buf.get() + o_wa + t * Bz, h->ep_buf.get() + o_ok + t * bn);
-        HIPCHK(hipGetLastError());
-    }
-    if (world_alive) HIPCHK(hipMemcpyAsync(world_alive, h->ep_buf.get() + o_wa, K * Bz, hipMemcpyDeviceToHost, h->stream));
-    if (agent_ok && bn) HIPCHK(hipMemcpyAsync(agent_ok, h->ep_buf.get() + o_ok, K * bn, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    guard.disarm();
-    return DW_OK;
-}
-
+// shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step, no LDS workgroup kernel
 int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params* worlds, const double* L_schedule, int policy_mode,
                             const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
                             uint8_t* agent_ok) {
@@ -2317,12 +2292,13 @@ int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params*
     // of dw_set_params for each world's set
     if (int rc = check_episode_call(h, nsteps, policy_mode, use_table, table)) return rc;
     const int C = p.height * p.width, N = p.n_agents, B = p.batch;
-    const size_t K = (size_t)nsteps, Bz = (size_t)B, bn = Bz * N;
-    WorldRows rows_of(p, worlds, Bz, !ensemble_episode_wave(h));
+    const size_t K = (size_t)nsteps, Bz = (size_t)B;
+    const bool wave = episode_form(h) == EPISODE_WAVE;
+    WorldRows rows_of(p, worlds, Bz, !wave);
     if (int rc = check_per_world(rows_of, worlds, L_schedule, K, Bz)) return rc;
-    if (!ensemble_episode_wave(h))
-        return run_episode_ensemble_stepwise(h, nsteps, rows_of, worlds_symmetric(worlds, Bz) && !h->sw.no_sym, L_schedule, policy_mode,
-                                             use_table, table, threshold_k, world_alive, agent_ok);
+    if (!wave)
+        return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, nullptr,
+                                    &rows_of, worlds_symmetric(worlds, Bz) && !h->sw.no_sym);
     const size_t lds = episode_wave_pw_shared_bytes() + episode_wave_pw_world_bytes(C, N) * 4;
     NEED(lds <= 160 * 1024, DW_EINVAL, "too many agents for the LDS-resident episode kernel");
     // The kernel keeps a world in LDS for a whole launch; a call is one launch unless its table of rows (136 B per step and
@@ -2332,56 +2308,34 @@ int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params*
     size_t rows = ((size_t)32 << 20) / row_bytes / kEwSeg * kEwSeg;
     rows = rows < (size_t)kEwSeg ? (size_t)kEwSeg : rows;
     rows = rows > K ? K : rows;
-    // staging, device and page-locked image alike: [P32 rows*B][Ls rows*B] | [P64 B][use_table K][table K*B*N] |
-    // [world_alive K*B][agent_ok K*B*N]: the inputs of the first launch go up in ONE copy, a later launch's rows in one
-    // more, the flags of the whole call come back in one
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_p32 = 0, o_ls = up(o_p32 + sizeof(PhysF32) * rows * Bz), o_p64 = up(o_ls + sizeof(double) * rows * Bz);
-    const size_t o_ut = up(o_p64 + sizeof(PhysF64) * Bz), o_tab = up(o_ut + K), o_wa = up(o_tab + K * bn), o_ok = up(o_wa + K * Bz);
-    const size_t total = up(o_ok + K * bn);
-    if (int rc = ensure_ep_buf(h, total)) return rc;
-    if (int rc = reserve(h->ep_pinned, "the page-locked episode staging", total, (size_t)1 << 20)) return rc;
-    unsigned char* img = h->ep_pinned.get();
-    unsigned char* dev = h->ep_buf.get();
+    // always staged: the first launch's inputs in ONE copy, a later launch's rows in one more, the call's flags in one
+    EpisodeRegions regions;
+    regions.rows = rows; regions.per_world = true; regions.use_table = true;
+    EpisodeBuffers E(h, EpisodeStaging(K, Bz, (size_t)N, regions));
+    if (int rc = E.alloc(true)) return rc;
     SyncOnExit guard(h->stream);                                // the image
-    PhysF64* p64 = reinterpret_cast<PhysF64*>(img + o_p64);
+    PhysF64* p64 = E.S.at<PhysF64>(E.img, EpisodeStaging::P64);
     for (size_t b = 0; b < Bz; ++b) p64[b] = make_f64(rows_of.params(b), 0.0);   // (L: replaced by the step's, from the Ls rows)
-    if (use_table) std::memcpy(img + o_ut, use_table, K); else std::memset(img + o_ut, 0, K);
-    const bool have_table = table && bn;
-    if (have_table) std::memcpy(img + o_tab, table, K * bn);
-    EpisodeIO io = episode_io(h, policy_mode, o_p32, o_ls);     // (every world's whole record is assigned by the kernel)
     const bool ex = p.precision == DW_PRECISION_EXACT;
     auto kern = ex ? episode_wave_pw<true> : episode_wave_pw<false>;
     if (int rc = set_lds_limit(h, kern, lds)) return rc;
-    PhysF32* r32 = reinterpret_cast<PhysF32*>(img + o_p32);
-    double* rls = reinterpret_cast<double*>(img + o_ls);
+    PhysF32* r32 = E.p32();
     for (size_t t0 = 0; t0 < K; t0 += rows) {
         const size_t kk = K - t0 < rows ? K - t0 : rows;
         if (t0) HIPCHK(hipStreamSynchronize(h->stream));        // the image's rows are free again
         for (size_t t = 0; t < kk; ++t) rows_of.single(L_schedule + (t0 + t) * Bz, r32 + t * Bz, nullptr);
-        std::memcpy(rls, L_schedule + t0 * Bz, sizeof(double) * kk * Bz);
-        const size_t upto = t0 ? o_ls + sizeof(double) * kk * Bz : (have_table ? o_tab + K * bn : o_ut + K);
-        HIPCHK(hipMemcpyAsync(dev, img, upto, hipMemcpyHostToDevice, h->stream));
-        io.use_table = use_table ? dev + o_ut + t0 : nullptr;
-        io.table = have_table ? reinterpret_cast<const signed char*>(dev + o_tab + t0 * bn) : nullptr;
-        io.world_alive = dev + o_wa + t0 * Bz;
-        io.agent_ok = dev + o_ok + t0 * bn;
-        const EpisodeWavePwArgs A{io, reinterpret_cast<const PhysF64*>(dev + o_p64), B, N, p.height, p.width, (int)kk, policy_mode,
+        if (int rc = E.upload(L_schedule + t0 * Bz, kk * Bz, t0 == 0, use_table, table)) return rc;
+        // (every world's whole record is assigned by the kernel)
+        const EpisodeWavePwArgs A{episode_io(h, policy_mode, E.S, t0, true, use_table != nullptr, table && E.S.bn),
+                                  E.dev<const PhysF64>(EpisodeStaging::P64), B, N, p.height, p.width, (int)kk, policy_mode,
                                   p.obs_mask, threshold_k, p.agent_gamma};
         hipLaunchKernelGGL(kern, dim3((unsigned)((B + 3) / 4)), dim3(256), lds, h->stream, A);
         HIPCHK(hipGetLastError());
         episode_done(h, 0.0, true);
     }
     release_unquantised(h);
-    const bool want_ok = agent_ok && bn;
-    if (world_alive || want_ok) {
-        const size_t lo = world_alive ? o_wa : o_ok, hi = want_ok ? o_ok + K * bn : o_wa + K * Bz;
-        HIPCHK(hipMemcpyAsync(img + lo, dev + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));                    // flags are returned
+    if (int rc = E.finish(world_alive, agent_ok, nullptr)) return rc;   // flags are returned
     guard.disarm();
-    if (world_alive) std::memcpy(world_alive, img + o_wa, K * Bz);
-    if (want_ok) std::memcpy(agent_ok, img + o_ok, K * bn);
     return DW_OK;
 }
 
@@ -2605,11 +2559,11 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     }
     {                                                           // the form dw_run_episode_ensemble takes
         const size_t n = std::strlen(buf);
-        snprintf(buf + n, buflen - n, "; ensemble episode: %s", ensemble_episode_wave(h) ? "one wave per world" : "launches per step");
+        snprintf(buf + n, buflen - n, "; ensemble episode: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
     }
     {                                                           // the form dw_run_episode_trace takes
         const size_t n = std::strlen(buf);
-        snprintf(buf + n, buflen - n, "; episode trace: %s", episode_trace_wave(h) ? "one wave per world" : "launches per step");
+        snprintf(buf + n, buflen - n, "; episode trace: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

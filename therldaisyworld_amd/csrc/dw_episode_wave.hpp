@@ -182,6 +182,30 @@ __device__ __forceinline__ void ew_update_agents(int a, const EwReach& R, bool i
     __builtin_amdgcn_wave_barrier();
 }
 
+// The action of this lane's agent for one step (ref agents/greedy.py:14-36 or the host-drawn table) - shared by
+// episode_wave, episode_wave_pw and episode_wave_stats_pw.  `tab`: 0..8, or -1 / -2: (anti-)greedy choice (unused unless
+// from_table).  Straight-line, select-based code for every lane (lanes that hold no agent work on agent 0's position and
+// are masked at the end): a lone wave per SIMD pays ~20 cycles for every taken branch, and the branchy form of this block
+// was half of the step's instructions.
+__device__ __forceinline__ int ew_policy_action(int policy_mode, bool from_table, int tab, const EwReach& R, int obs_mask) {
+    const bool greedy = from_table ? tab < 0 : policy_mode != kPolicyZeros;
+    const bool argmin = (from_table && tab < 0) ? tab == -2 : policy_mode == kPolicyArgmin;
+    // first maximum / minimum over the (masked) candidates, as np.argmax / np.argmin
+    const double v0 = ((obs_mask >> 3) & 1) ? R.nat0 : 0.0, v1 = ((obs_mask >> 1) & 1) ? R.nat1 : 0.0;
+    const double v2 = ((obs_mask >> 7) & 1) ? R.nat2 : 0.0, v3 = ((obs_mask >> 5) & 1) ? R.nat3 : 0.0;
+    // (np.argmin = the first maximum of the negated values: one sign flip per candidate - covers are never
+    // NaN, and -0.0 compares equal to 0.0 - instead of both comparisons and a select at every level)
+    const unsigned long long flip = argmin ? 0x8000000000000000ull : 0ull;
+    const double w0 = __longlong_as_double(__double_as_longlong(v0) ^ flip), w1 = __longlong_as_double(__double_as_longlong(v1) ^ flip);
+    const double w2 = __longlong_as_double(__double_as_longlong(v2) ^ flip), w3 = __longlong_as_double(__double_as_longlong(v3) ^ flip);
+    int best = 0;
+    double bestv = w0;
+    { const bool bt = w1 > bestv; best = bt ? 1 : best; bestv = bt ? w1 : bestv; }
+    { const bool bt = w2 > bestv; best = bt ? 2 : best; bestv = bt ? w2 : bestv; }
+    { const bool bt = w3 > bestv; best = bt ? 3 : best; }
+    return greedy ? 4 + best : (from_table ? tab : 0);
+}
+
 // ONE argument struct: the float64 constants are needed only by the rare near-tie path and are read from the kernarg
 // segment there (as by-value arguments they would sit in 34 SGPRs for the whole launch; `kernarg_struct`, dw_step_stream.hpp)
 struct EpisodeWaveArgs {
@@ -265,28 +289,10 @@ __global__ __launch_bounds__(256) void episode_wave(EpisodeWaveArgs A) {
             const PhysF32 P = sP32[ts];
             // ---- policy (ref agents/greedy.py:14-36 or the host-drawn table) + update_agents (ref :181-244) ----
             if (with_agents) {
-                // Straight-line, select-based code for every lane (lanes that hold no agent work on agent 0's position and
-                // are masked at the end): a lone wave per SIMD pays ~20 cycles for every taken branch, and the branchy
-                // form of this block was half of the step's instructions.
                 const bool from_table = policy_mode == kPolicyTable || ((ut_mask >> ts) & 1ull);           // wave-uniform
                 const int tab = (int)sTab[ts * N + alane];       // 0..8, or -1 / -2: (anti-)greedy choice (unused unless from_table)
                 const EwReach R = ew_reach(pc, ar, ac, H, W);
-                const bool greedy = from_table ? tab < 0 : policy_mode != kPolicyZeros;
-                const bool argmin = (from_table && tab < 0) ? tab == -2 : policy_mode == kPolicyArgmin;
-                // first maximum / minimum over the (masked) candidates, as np.argmax / np.argmin
-                const double v0 = ((obs_mask >> 3) & 1) ? R.nat0 : 0.0, v1 = ((obs_mask >> 1) & 1) ? R.nat1 : 0.0;
-                const double v2 = ((obs_mask >> 7) & 1) ? R.nat2 : 0.0, v3 = ((obs_mask >> 5) & 1) ? R.nat3 : 0.0;
-                // (np.argmin = the first maximum of the negated values: one sign flip per candidate - covers are never
-                // NaN, and -0.0 compares equal to 0.0 - instead of both comparisons and a select at every level)
-                const unsigned long long flip = argmin ? 0x8000000000000000ull : 0ull;
-                const double w0 = __longlong_as_double(__double_as_longlong(v0) ^ flip), w1 = __longlong_as_double(__double_as_longlong(v1) ^ flip);
-                const double w2 = __longlong_as_double(__double_as_longlong(v2) ^ flip), w3 = __longlong_as_double(__double_as_longlong(v3) ^ flip);
-                int best = 0;
-                double bestv = w0;
-                { const bool bt = w1 > bestv; best = bt ? 1 : best; bestv = bt ? w1 : bestv; }
-                { const bool bt = w2 > bestv; best = bt ? 2 : best; bestv = bt ? w2 : bestv; }
-                { const bool bt = w3 > bestv; best = bt ? 3 : best; }
-                const int a = greedy ? 4 + best : (from_table ? tab : 0);
+                const int a = ew_policy_action(policy_mode, from_table, tab, R, obs_mask);
                 if (t0 + ts == K - 1 && is_agent && io.action) io.action[(size_t)b * N + lane] = a;
                 ew_update_agents(a, R, is_agent, lane, N, W, agent_gamma, ast, ar, ac, pc);
             }

@@ -23,11 +23,11 @@ namespace dw {
 //  * lane 0 keeps the step's record (three uint32) in the world's own LDS area of 64 x 12 B; after the segment lane i
 //    writes step t0 + i's dw_world_stats row (reserved = 0) next to the segment's flags.  The launch's final io.stats are
 //    the last step's record.
-// Everything else - the cells' neighbour offsets, the policy, update_agents, the flags, the write-back of planes and
-// agents - is episode_wave's code: the shared pieces are called, the straight-line policy block is repeated verbatim.
-// The price of the records on every other shape is stated at dw_run_episode_trace (dw_api.hip): launches per step, no
-// fused step pairs (the step-1 sums of a pair would have to include the patch kernel's corrections), no LDS workgroup
-// kernel.
+// The rest of the step is episode_wave's pieces, called: ew_cells_init, ew_reach, ew_policy_action, ew_update_agents.
+// The prologue's loads, the table slice of a segment, the agents' flags and the write-back are written out as there, and
+// ew_forward_stats stays next to ew_forward: shared, they changed episode_wave's instructions.
+// The price of the records on every other shape is stated at run_episode_stepwise (dw_api.hip): launches per step, no
+// fused step pairs, no LDS workgroup kernel.
 // ---------------------------------------------------------------------------------------------
 constexpr size_t kEwRecBytes = (size_t)kEwSeg * 12;             // a world's records of one segment: {max, sumL, sumD} uint32
 
@@ -206,24 +206,12 @@ __global__ __launch_bounds__(256) void episode_wave_stats_pw(EpisodeWaveStatsArg
             float2* const pc = planes + cur * C;
             float2* const pn = planes + (1 - cur) * C;
             const PhysF32 P = sP32[ts];
-            // ---- policy + update_agents: episode_wave's block, verbatim ----
+            // ---- policy + update_agents ----
             if (with_agents) {
                 const bool from_table = policy_mode == kPolicyTable || ((ut_mask >> ts) & 1ull);           // wave-uniform
                 const int tab = (int)sTab[ts * N + alane];       // 0..8, or -1 / -2: (anti-)greedy choice (unused unless from_table)
                 const EwReach R = ew_reach(pc, ar, ac, H, W);
-                const bool greedy = from_table ? tab < 0 : policy_mode != kPolicyZeros;
-                const bool argmin = (from_table && tab < 0) ? tab == -2 : policy_mode == kPolicyArgmin;
-                const double v0 = ((obs_mask >> 3) & 1) ? R.nat0 : 0.0, v1 = ((obs_mask >> 1) & 1) ? R.nat1 : 0.0;
-                const double v2 = ((obs_mask >> 7) & 1) ? R.nat2 : 0.0, v3 = ((obs_mask >> 5) & 1) ? R.nat3 : 0.0;
-                const unsigned long long flip = argmin ? 0x8000000000000000ull : 0ull;
-                const double w0 = __longlong_as_double(__double_as_longlong(v0) ^ flip), w1 = __longlong_as_double(__double_as_longlong(v1) ^ flip);
-                const double w2 = __longlong_as_double(__double_as_longlong(v2) ^ flip), w3 = __longlong_as_double(__double_as_longlong(v3) ^ flip);
-                int best = 0;
-                double bestv = w0;
-                { const bool bt = w1 > bestv; best = bt ? 1 : best; bestv = bt ? w1 : bestv; }
-                { const bool bt = w2 > bestv; best = bt ? 2 : best; bestv = bt ? w2 : bestv; }
-                { const bool bt = w3 > bestv; best = bt ? 3 : best; }
-                const int a = greedy ? 4 + best : (from_table ? tab : 0);
+                const int a = ew_policy_action(policy_mode, from_table, tab, R, obs_mask);
                 if (t0 + ts == K - 1 && is_agent && io.action) io.action[(size_t)b * N + lane] = a;
                 ew_update_agents(a, R, is_agent, lane, N, W, agent_gamma, ast, ar, ac, pc);
             }

@@ -5,8 +5,8 @@
 
 On a wide-grid plan that takes step pairs (3 worlds of 70 x 320, float32-only) and on an 8 x 8 plan that takes the
 one-wave-per-world episode kernels (6 worlds, 2 agents each): dw_step_n_trace, dw_step_n_trace_temperature (shared L and
-per-world), dw_step_n_trace_per_world, dw_step_n_trace_ensemble (with and without temperature records), dw_run_episode and
-dw_run_episode_ensemble, 11 steps each, from an un-quantised and from a quantised state.  Two builds of the library that
+per-world), dw_step_n_trace_per_world, dw_step_n_trace_ensemble (with and without temperature records), dw_run_episode,
+dw_run_episode_ensemble and dw_run_episode_trace, 11 steps each, from an un-quantised and from a quantised state.  Two builds of the library that
 launch the same kernels the same number of times give the same per-kernel call counts (profiles/series_launches_*).
 DW_LIB selects the library.  Prints what was called; the numbers are the profiler's.
 """
@@ -44,6 +44,7 @@ def main():
             use = (np.arange(n) % 2).astype(np.uint8)
             eng.run_episode(L[:, 0], 0, use_table=use, table=table)
             eng.run_episode_ensemble(tab, L, 0, use_table=use, table=table)
+            eng.run_episode_trace(L[:, 0], 0, use_table=use, table=table)
             eng.step(0.9)
         print(f"{(B, H, W, N)} {precision}: {eng.kernel_info()}")
         eng.close()
