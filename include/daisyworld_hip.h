@@ -550,6 +550,35 @@ int dw_run_episode_trace(dw_handle* h, int32_t nsteps, const double* L_schedule,
                          uint8_t* world_alive /* [K][B], may be NULL */, uint8_t* agent_ok /* [K][B][N], may be NULL */,
                          dw_world_stats* trace /* [K][B], required */);
 
+/* dw_run_episode_trace that also records, for every step and world, the statistics of the local temperature field that
+ * step computes: the curves temp.mean() and temp.std() which the reference's animation with an agent appends after every
+ * env.step(action) (daisy/notebook_helpers.py:210-223 `update_fig_agent`) - whether grazers break the biosphere's
+ * temperature regulation - as ONE device-resident run, instead of one dw_step + dw_reduce_temperature round trip per step.
+ * Contract: everything dw_run_episode_trace leaves on the handle and in world_alive / agent_ok / trace for the same
+ * arguments - the planes, the retained previous state, the agents, dw_reduce, the device action buffer,
+ * dw_last_fixup_count, the flags, the records - this call leaves too, bit for bit, in DW_PRECISION_EXACT and
+ * DW_PRECISION_FAST (n_agents == 0 allowed).  `trace` may be NULL here.
+ *   temps[t*B + b]  the dw_temp_stats of the field `self.temp` (ref daisy_world_rl.py:410,415) of world b in step t: taken
+ *                   from the state AFTER step t's update_agents (grazed cells zeroed) and BEFORE its growth, at
+ *                   L_schedule[t] - what env.temp holds after the t-th env.step(action).  Required.
+ * Always float64, whatever the handle's precision: every cell's temperature is the float64 evaluation of the reference's
+ * staging, and the reduction is the deterministic one of dw_reduce_temperature (moments about the temperature of the
+ * world's cell (0, 0), the same association order).  Hence temps[K-1] equals dw_reduce_temperature(h, L_schedule[K-1], .)
+ * after the call bit for bit, both forms below return identical bytes, and a world without cover has std == 0.0 and
+ * min == max == mean.
+ * The forms are dw_run_episode_trace's.  H*W <= 256 with at most 64 agents: one launch, one wave per world
+ * (episode_wave_temp_pw, csrc/dw_episode_wave_temp_pw.hpp: each lane evaluates the temperature of its cells from the 3x3
+ * neighbourhoods the forward pass loads; the wave reduces them in the order of the on-demand reduction; lane 0 stores the
+ * step's 32-byte row).  Every other shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step, with the
+ * on-demand reduction's kernels between a step's update_agents and its step kernel (dw_kernel_info: "; episode
+ * temperature: one wave per world" / "launches per step").  Flags, records and temperature rows come down in one copy.
+ * Checked before anything is launched or allocated (the state is untouched): the rules of dw_run_episode_trace, and
+ * DW_EINVAL for a null temps.  Synchronises. */
+int dw_run_episode_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
+                                     const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
+                                     uint8_t* world_alive /* [K][B], may be NULL */, uint8_t* agent_ok /* [K][B][N], may be NULL */,
+                                     dw_world_stats* trace /* [K][B], may be NULL */, dw_temp_stats* temps /* [K][B], required */);
+
 /* ---- plumbing ------------------------------------------------------------------------------- */
 
 /* Use an existing HIP stream (e.g. torch's current stream) instead of the handle's own. */
@@ -567,7 +596,7 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark);
 /* Name and geometry of the step kernel the handle dispatches for its shape, for bench/profiles:
  * writes a NUL-terminated description into buf.  Appended fragments name the forms of the other entry points:
  * "; trace: ...", "; per-world L: ...", "; ensemble episode: ..." (dw_run_episode_ensemble), "; episode trace: ..."
- * (dw_run_episode_trace) and
+ * (dw_run_episode_trace), "; episode temperature: ..." (dw_run_episode_trace_temperature) and
  * "; episode: F; mlp episode: F" - the form dw_run_episode and
  * dw_run_episode_mlp take for the handle's shape, agent count, precision, collision mode and switches, F one of
  * "one wave per world" (H*W <= 256 and at most 64 agents, MLP: at most 4), "workgroup (LDS)" (H*W <= 4096) and

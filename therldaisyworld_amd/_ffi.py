@@ -126,6 +126,8 @@ SIGNATURES = {
                                           _pu8, _pu8]),
     "dw_run_episode_trace": (C.c_int, [_vp, _i32, _pd, C.c_int, _pu8, C.POINTER(C.c_int8), _u32, _pu8, _pu8,
                                        C.POINTER(DwWorldStats)]),
+    "dw_run_episode_trace_temperature": (C.c_int, [_vp, _i32, _pd, C.c_int, _pu8, C.POINTER(C.c_int8), _u32, _pu8, _pu8,
+                                                   C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
     "dw_set_stream": (C.c_int, [_vp, _vp]),
     "dw_sync": (C.c_int, [_vp]),
     "dw_timer_start": (C.c_int, [_vp]),

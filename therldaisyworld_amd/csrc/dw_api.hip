@@ -297,7 +297,8 @@ static int ensure_f64(dw_handle* h) {
 
 static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                             const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
-                            uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace = nullptr);
+                            uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace = nullptr,
+                            dw_temp_stats* temps = nullptr);
 static bool episode_kernel_applies(const dw_handle* h);
 // The form a handle's episode calls take: a pure function of its parameters and switches.  The dispatch of
 // run_episode_impl / dw_run_episode_mlp and the text of dw_kernel_info both read these two predicates.
@@ -374,21 +375,25 @@ struct EpisodeBuffers {
         return DW_OK;
     }
     // flags and records come back (staged: the one span that covers what the caller wants), the stream is synchronised
-    int finish(uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace) {
+    // (`temps`: the second block of TRACE, behind the records)
+    int finish(uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace, dw_temp_stats* temps = nullptr) {
         if (!S.bn) agent_ok = nullptr;
-        struct { void* dst; R::Region r; } out[3] = {{world_alive, R::WORLD_ALIVE}, {agent_ok, R::AGENT_OK}, {trace, R::TRACE}};
+        struct { void* dst; size_t off, bytes; } out[4] = {{world_alive, S.off[R::WORLD_ALIVE], S.bytes[R::WORLD_ALIVE]},
+                                                           {agent_ok, S.off[R::AGENT_OK], S.bytes[R::AGENT_OK]},
+                                                           {trace, S.off[R::TRACE], S.stats_bytes},
+                                                           {temps, S.temps_off(), S.temps_bytes}};
         size_t lo = S.total, hi = 0;
         for (const auto& o : out) {
             if (!o.dst) continue;
-            if (!img) HIPCHK(hipMemcpyAsync(o.dst, dev(o.r), S.bytes[o.r], hipMemcpyDeviceToHost, h->stream));
-            lo = S.off[o.r] < lo ? S.off[o.r] : lo;
-            hi = S.end(o.r) > hi ? S.end(o.r) : hi;
+            if (!img) HIPCHK(hipMemcpyAsync(o.dst, h->ep_buf.get() + o.off, o.bytes, hipMemcpyDeviceToHost, h->stream));
+            lo = o.off < lo ? o.off : lo;
+            hi = o.off + o.bytes > hi ? o.off + o.bytes : hi;
         }
         if (img && hi > lo) HIPCHK(hipMemcpyAsync(img + lo, h->ep_buf.get() + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         if (img)
             for (const auto& o : out)
-                if (o.dst) std::memcpy(o.dst, img + S.off[o.r], S.bytes[o.r]);
+                if (o.dst) std::memcpy(o.dst, img + o.off, o.bytes);
         return DW_OK;
     }
 };
@@ -2079,16 +2084,20 @@ static EpisodeIO episode_io(const dw_handle* h, int policy_mode, const EpisodeSt
 // launch_forward_pw) the step is that per-world single step of dw_step_n_trace_ensemble, from rows that go up as in the
 // trace calls (PwTable, the table chunks of plan_series without the test hook).  Fused step pairs only without either: the
 // step-1 sums of a pair would have to include the patch kernel's corrections, and the pair kernels take one constant set.
+// With `temps` (dw_run_episode_trace_temperature; the caller has allocated the reduction's partials): between a step's
+// update_agents and its step kernel, the statistics of the temperature field that step computes - temp_moments_pw on the
+// current planes at L_schedule[t] - into row t of the temperature block; single steps as with `trace`.
 static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                                 const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
-                                uint8_t* agent_ok, dw_world_stats* trace, WorldRows* worlds = nullptr, bool sym = false) {
+                                uint8_t* agent_ok, dw_world_stats* trace, WorldRows* worlds = nullptr, bool sym = false,
+                                dw_temp_stats* temps = nullptr) {
     using R = EpisodeStaging;
     const dw_params& p = h->prm;
     const int N = p.n_agents, B = p.batch;
     const size_t K = (size_t)nsteps, Bz = (size_t)B, bn = Bz * N;
-    const bool plain = !trace && !worlds;
+    const bool plain = !trace && !worlds && !temps;
     EpisodeRegions regions;
-    regions.trace = trace != nullptr; regions.pairs = plain; regions.slack = 256;
+    regions.trace = trace != nullptr || temps != nullptr; regions.temps = temps != nullptr; regions.pairs = plain; regions.slack = 256;
     EpisodeBuffers E(h, EpisodeStaging(K, Bz, (size_t)N, regions));
     SeriesSchedule q;
     std::optional<PwTable> tab;
@@ -2106,6 +2115,7 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
     unsigned char* const d_ok = E.dev(R::AGENT_OK);
     unsigned char* const d_code = E.dev(R::CODE);
     StatsDev* const rows = E.dev<StatsDev>(R::TRACE);
+    TempStatsDev* const trows = reinterpret_cast<TempStatsDev*>(h->ep_buf.get() + E.S.temps_off());
     const int nflag = B > (int)bn ? B : (int)bn;
     // (with per-world constants DW_POLICY_ZEROS wins over use_table, without them use_table wins: DESIGN.md 3.2j)
     const bool table_steps = use_table && !(worlds && policy_mode == DW_POLICY_ZEROS);
@@ -2174,6 +2184,8 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
             ++t;                                             // two steps done
             continue;
         }
+        if (temps)
+            if (int rc = launch_temp_moments(h, /*current=*/true, L_schedule[t], nullptr, trows + t * Bz)) return rc;
         if (tab) {
             const size_t tr = q.row_of[t];
             if (int rc = launch_forward_pw(h, tab->lay.p32(tab->dev(), tr), tab->lay.p64(tab->dev(), tr), tab->lay.fb(tab->dev()), sym, true)) return rc;
@@ -2187,7 +2199,7 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
                                h->stats2[h->sp].get(), B, rows + t * Bz);
         HIPCHK(hipGetLastError());
     }
-    if (int rc = E.finish(world_alive, agent_ok, trace)) return rc;
+    if (int rc = E.finish(world_alive, agent_ok, trace, temps)) return rc;
     guard.disarm();
     return DW_OK;
 }
@@ -2209,25 +2221,33 @@ static int check_episode_call(const dw_handle* h, int32_t nsteps, int policy_mod
 
 // `trace` (dw_run_episode_trace): also the records of every step, [K][B]; the one-wave-per-world form takes
 // episode_wave_stats_pw, every other form launches per step: no LDS workgroup kernel, the stated price of the records.
+// `temps` (dw_run_episode_trace_temperature): also the temperature records of every step, [K][B], behind the records in
+// the staging buffer; the same dispatch with episode_wave_temp_pw, which writes both.
 static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                             const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
-                            uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace) {
+                            uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace, dw_temp_stats* temps) {
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
     if (int rc = check_episode_call(h, nsteps, policy_mode, use_table, table)) return rc;
     const int C = p.height * p.width, N = p.n_agents, B = p.batch;
     const EpisodeForm form = episode_form(h);                  // (F64 / collision_mode 1 were rejected above)
-    if (form == EPISODE_STEPWISE || (trace && form != EPISODE_WAVE))
-        return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace);
+    const bool records = trace || temps;
+    if (form == EPISODE_STEPWISE || (records && form != EPISODE_WAVE)) {
+        if (temps)                                              // the partials of temp_moments_pw (the rows live in the staging buffer)
+            if (int rc = alloc_group(h, "the temperature reduction", {{h->temp_part, temp_part_bytes(h)}})) return rc;
+        return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace,
+                                    nullptr, false, temps);
+    }
     const bool wave_kernel = form == EPISODE_WAVE;
     const int wpb = worlds_per_block(C);
     const size_t world_bytes = wave_kernel ? episode_wave_world_bytes(C, N) : episode_world_bytes(C, N);
-    const size_t lds = trace ? episode_wave_stats_lds_bytes(C, N)     // (<= 64 KB for every shape of the form: static_assert there)
+    const size_t lds = temps ? episode_wave_temp_lds_bytes(C, N)      // (<= 64 KB for every shape of the form: static_assert there)
+                     : trace ? episode_wave_stats_lds_bytes(C, N)
                              : world_bytes * wpb + (wave_kernel ? episode_wave_shared_bytes() : 0);
     NEED(lds <= 160 * 1024, DW_EINVAL, "too many agents for the LDS-resident episode kernel");
     const size_t K = (size_t)nsteps;
     EpisodeRegions regions;
-    regions.rows = K; regions.use_table = true; regions.trace = trace != nullptr;
+    regions.rows = K; regions.use_table = true; regions.trace = records; regions.temps = temps != nullptr;
     EpisodeBuffers E(h, EpisodeStaging(K, (size_t)B, (size_t)N, regions));
     if (int rc = E.alloc(E.S.fits_image())) return rc;
     PhysF32* p32 = E.p32();
@@ -2242,7 +2262,13 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     const PhysF64 P64 = make_f64(p, L_schedule[0]);
     const dim3 grid((unsigned)((B + wpb - 1) / wpb));
     const bool ex = p.precision == DW_PRECISION_EXACT;
-    if (trace) {
+    if (temps) {
+        auto kern = ex ? episode_wave_temp_pw<true> : episode_wave_temp_pw<false>;
+        const EpisodeWaveTempArgs A{io, E.dev<StatsDev>(EpisodeStaging::TRACE),
+                                    reinterpret_cast<TempStatsDev*>(h->ep_buf.get() + E.S.temps_off()), B, N, p.height, p.width, nsteps,
+                                    policy_mode, p.obs_mask, threshold_k, p.agent_gamma, P64};
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, h->stream, A);
+    } else if (trace) {
         auto kern = ex ? episode_wave_stats_pw<true> : episode_wave_stats_pw<false>;
         const EpisodeWaveStatsArgs A{io, E.dev<StatsDev>(EpisodeStaging::TRACE), B, N, p.height, p.width, nsteps,
                                      policy_mode, p.obs_mask, threshold_k, p.agent_gamma, P64};
@@ -2261,7 +2287,7 @@ static int run_episode_impl(dw_handle* h, int32_t nsteps, const double* L_schedu
     HIPCHK(hipGetLastError());
     episode_done(h, L_schedule[K - 1], false);
     release_unquantised(h);
-    if (int rc = E.finish(world_alive, agent_ok, trace)) return rc;      // flags are returned
+    if (int rc = E.finish(world_alive, agent_ok, trace, temps)) return rc;      // flags are returned
     guard.disarm();
     return DW_OK;
 }
@@ -2276,6 +2302,19 @@ int dw_run_episode_trace(dw_handle* h, int32_t nsteps, const double* L_schedule,
     NEED(trace, DW_EINVAL, "dw_run_episode_trace needs a trace array");
     NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
     return run_episode_impl(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace);
+}
+
+// ---- dw_run_episode_trace_temperature: dw_run_episode_trace with the temperature records of every step -----------------
+// The form the call takes is dw_run_episode_trace's: one wave per world (episode_wave_temp_pw), or launches per step with
+// temp_moments_pw in front of every step kernel.  Both reduce in temp_moments_pw's order: the same bytes.
+int dw_run_episode_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
+                                     const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
+                                     uint8_t* agent_ok, dw_world_stats* trace, dw_temp_stats* temps) {
+    NEED(h && L_schedule, DW_EINVAL, "null argument");
+    NEED(temps, DW_EINVAL, "dw_run_episode_trace_temperature needs a temps array");
+    NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
+    static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev) && sizeof(TempStatsDev) == EpisodeStaging::kTempRow, "temperature record layout");
+    return run_episode_impl(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace, temps);
 }
 
 // ---- dw_run_episode_ensemble: dw_run_episode with a set of physics constants and a luminosity column per world --------
@@ -2564,6 +2603,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_run_episode_trace takes
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, "; episode trace: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
+    }
+    {                                                           // the form dw_run_episode_trace_temperature takes
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; episode temperature: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

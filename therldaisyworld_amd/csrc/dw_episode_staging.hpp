@@ -15,6 +15,7 @@ struct EpisodeRegions {
     bool per_world = false;     // the rows are [rows][B], and the worlds' float64 sets P64 [B] follow them
     bool use_table = false;     // use_table [K] on the device (the LDS-resident kernels; the launches per step read the caller's)
     bool trace = false;         // the records of every step, [K][B]
+    bool temps = false;         // ... followed by the temperature records of every step, [K][B] rows of 32 bytes (with `trace`)
     bool pairs = false;         // fused step pairs: the uniform action-code bytes [B*N] and the pair statistics [2*B] uint32
     bool mlp = false;           // dw_run_episode_mlp: member maps [B] x 2, reward and done [K][B*N]; no table, no flags
     size_t slack = 0;           // bytes behind the last region
@@ -24,8 +25,10 @@ struct EpisodeRegions {
 // of the page-locked image), what the device writes (ONE download of WORLD_ALIVE .. TRACE), what only the device uses.
 struct EpisodeStaging {
     enum Region { MEMBER_A, MEMBER_B, REWARD, DONE, P32, LS, P64, USE_TABLE, TABLE, WORLD_ALIVE, AGENT_OK, TRACE, CODE, PAIR_STATS, kRegions };
+    static constexpr size_t kTempRow = 32;                      // a temperature record: four doubles (dw_temp_stats)
     size_t K, B, bn;
     size_t off[kRegions], bytes[kRegions], total;
+    size_t stats_bytes, temps_bytes;                            // the two blocks of TRACE: [K][B] StatsDev | [K][B] temperature rows
 
     static size_t up(size_t v) { return (v + 255) / 256 * 256; }
 
@@ -41,7 +44,9 @@ struct EpisodeStaging {
         bytes[TABLE] = flags * K * bn;
         bytes[WORLD_ALIVE] = flags * K * B;
         bytes[AGENT_OK] = flags * K * bn;
-        bytes[TRACE] = r.trace ? sizeof(StatsDev) * K * B : 0;
+        stats_bytes = r.trace ? sizeof(StatsDev) * K * B : 0;
+        temps_bytes = r.trace && r.temps ? kTempRow * K * B : 0;
+        bytes[TRACE] = stats_bytes + temps_bytes;
         bytes[CODE] = r.pairs ? bn : 0;
         bytes[PAIR_STATS] = r.pairs ? sizeof(unsigned int) * 2 * B : 0;
         size_t o = 0;
@@ -52,6 +57,8 @@ struct EpisodeStaging {
         total = o + r.slack;
     }
     size_t end(Region r) const { return off[r] + bytes[r]; }
+    // where the temperature rows start: 8-byte aligned, sizeof(StatsDev) * K * B being a multiple of 8
+    size_t temps_off() const { return off[TRACE] + stats_bytes; }
     // the prefix a call's first upload covers: through the action table when the caller gave one, else through use_table
     size_t input_end(bool have_table) const { return have_table ? end(TABLE) : end(USE_TABLE); }
     // a page-locked image of the whole buffer is kept up to 64 MiB; beyond: straight from / to the caller's arrays

@@ -15,6 +15,7 @@
 //   dw_episode_wave.hpp   episode_wave      the same for H*W <= 256: one wave per world, no workgroup barrier in the step
 //   dw_episode_wave_pw.hpp episode_wave_pw  ... with the constants of each wave's own world (dw_run_episode_ensemble)
 //   dw_episode_wave_stats_pw.hpp episode_wave_stats_pw  ... with the records of every step (dw_run_episode_trace)
+//   dw_episode_wave_temp_pw.hpp episode_wave_temp_pw  ... and the temperature statistics of every step (dw_run_episode_trace_temperature)
 //   dw_agents.hpp         agents_update (ref :181-244), observe (ref get_obs :246-263), policy_greedy
 //                         (agents/greedy.py:14-36), policy_mlp (agents/mlp.py:97-116), reward/done, lifespans
 //   dw_agents_fused.hpp   agents_lookahead_patch: the agents' step between the two steps of a fused launch
@@ -42,3 +43,4 @@
 #include "dw_temp_moments.hpp"
 #include "dw_episode_wave_pw.hpp"
 #include "dw_episode_wave_stats_pw.hpp"
+#include "dw_episode_wave_temp_pw.hpp"

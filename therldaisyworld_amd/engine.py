@@ -421,12 +421,18 @@ class Engine:
             _ffi.ptr_u8(ok) if self.N else None))
         return (None if alive is None else alive.view(np.bool_)), ok.view(np.bool_)
 
-    def run_episode_trace(self, L_schedule, policy_mode, use_table=None, table=None, threshold_k=5):
+    def run_episode_trace(self, L_schedule, policy_mode, use_table=None, table=None, threshold_k=5, temperature=False):
         """`run_episode` that also records what `reduce()` would return after every step (`dw_run_episode_trace`): the
         daisy populations of an ensemble with grazing agents, in one device-resident run.  Returns (stats (K,B) of dtype
         `_ffi.STATS_DTYPE` with `reserved` 0, world_alive (K,B) bool, agent_ok (K,B,N) bool); flags, state and agents are
         `run_episode`'s for the same arguments, `world_alive == (stats["max_k"] > threshold_k)`, and the last row is
-        `reduce()` after the call."""
+        `reduce()` after the call.
+
+        `temperature=True` (`dw_run_episode_trace_temperature`): returns (stats, world_alive, agent_ok, temps), `temps`
+        (K, B) records of dtype `_ffi.TEMP_STATS_DTYPE` - mean, population std, min and max of the local temperature
+        field step t computes, from the state after its grazing and before its growth (the reference's `env.temp` after
+        the t-th `env.step(action)`), float64 in every precision.  Everything else is unchanged, and the last row is
+        `reduce_temperature(L_schedule[-1])` after the call, bit for bit."""
         Ls = np.ascontiguousarray(L_schedule, dtype=np.float64)
         K = Ls.shape[0]
         ut = None if use_table is None else np.ascontiguousarray(use_table, dtype=np.uint8)
@@ -438,6 +444,14 @@ class Engine:
         stats = np.zeros((K, self.B), dtype=_ffi.STATS_DTYPE)
         alive = np.empty((K, self.B), dtype=np.uint8)
         ok = np.empty((K, self.B, self.N), dtype=np.uint8)
+        if temperature:
+            temps = np.zeros((K, self.B), dtype=_ffi.TEMP_STATS_DTYPE)
+            self._check(self._lib.dw_run_episode_trace_temperature(
+                self._h, K, _ffi.ptr_d(Ls), int(policy_mode), _ffi.ptr_u8(ut),
+                None if tb is None else tb.ctypes.data_as(C.POINTER(C.c_int8)), int(threshold_k), _ffi.ptr_u8(alive),
+                _ffi.ptr_u8(ok) if self.N else None, stats.ctypes.data_as(C.POINTER(DwWorldStats)),
+                temps.ctypes.data_as(C.POINTER(DwTempStats))))
+            return stats, alive.view(np.bool_), ok.view(np.bool_), temps
         self._check(self._lib.dw_run_episode_trace(
             self._h, K, _ffi.ptr_d(Ls), int(policy_mode), _ffi.ptr_u8(ut),
             None if tb is None else tb.ctypes.data_as(C.POINTER(C.c_int8)), int(threshold_k), _ffi.ptr_u8(alive),

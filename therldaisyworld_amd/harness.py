@@ -294,7 +294,7 @@ def simulate_ramp(env, nsteps, obs=None, temperature=False):
     return _ramp_series(env, nsteps, eng.step_n_trace)
 
 
-def simulate_grazing(env, agent, nsteps, chunk=64, obs=None):
+def simulate_grazing(env, agent, nsteps, chunk=64, obs=None, temperature=False):
     """The `simulate_ramp` of an ensemble WITH agents: the time series of the daisy populations over the next `nsteps`
     steps while the agents graze - the curves of the reference's animations with an agent (daisy/notebook_helpers.py:
     218-223 `update_fig_agent`, rl_daisy_world.ipynb cells 12-16, greedy_longevity_abatement.ipynb cells 10-15 append
@@ -311,7 +311,14 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None):
     (n, B, N) bool - reward >= 0.1 after the step - and `agents_alive` (n, B) int, their number per world.  Afterwards
     `env.grid`, `env.step()`, `env.L`, `env.step_count` continue as if `nsteps` calls of `env.step(agent(obs))` had been
     made.  Precision "f64", `collision_mode == 1` and any other callable agent: the same dict from a host loop, one
-    `env.step` and one `reduce()` per step."""
+    `env.step` and one `reduce()` per step.
+
+    `temperature=True`: the run also records the per-world statistics of the local temperature field every step computes
+    from the grazed state - the reference's `env.temp.mean()` / `.std()` after each `env.step(action)`, the curves
+    `update_fig_agent` appends next to `env.dead_temp` (notebook_helpers.py:210-223) - through
+    `dw_run_episode_trace_temperature` (the first step and the host loop: `reduce_temperature` after the step).  The
+    dict gains `mean_temp`, `std_temp`, `min_temp`, `max_temp` (n, B) in kelvin and `dead_temp` (n,); everything else,
+    the state afterwards and the generator's final state are those of the cover-only run."""
     n = int(nsteps)
     if n < 1:
         raise ValueError("nsteps must be at least 1")
@@ -324,6 +331,7 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None):
     L = np.zeros(n, dtype=np.float64)
     stats = np.zeros((n, B), dtype=_ffi.STATS_DTYPE)
     ok = np.zeros((n, B, N), dtype=bool)
+    temps = np.zeros((n, B), dtype=_ffi.TEMP_STATS_DTYPE) if temperature else None
 
     def host_step(t, obs):
         """Step t as the notebook takes it; its row from `reduce()` and `done`."""
@@ -333,6 +341,8 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None):
         row = env._engine.reduce()
         for f in ("max_k", "sum_light_k", "sum_dark_k"):
             stats[f][t] = row[f]
+        if temperature:
+            temps[t] = env._engine.reduce_temperature(L[t])
         if N:
             ok[t] = ~np.asarray(done).reshape(B, N)
         return obs
@@ -357,10 +367,14 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None):
                         table[i] = agent.draw_random_actions(B, N)[..., 0]
             Ls = np.asarray(_luminosity_schedule(env, k), dtype=np.float64)
             L[t:t + k] = Ls
-            stats[t:t + k], _, ok[t:t + k] = eng.run_episode_trace(Ls, mode, use_table, table, LIFESPAN_THRESHOLD_K)
+            if temperature:
+                stats[t:t + k], _, ok[t:t + k], temps[t:t + k] = eng.run_episode_trace(Ls, mode, use_table, table,
+                                                                                       LIFESPAN_THRESHOLD_K, temperature=True)
+            else:
+                stats[t:t + k], _, ok[t:t + k] = eng.run_episode_trace(Ls, mode, use_table, table, LIFESPAN_THRESHOLD_K)
             _advance_host_scalars(env, k)
             t += k
-    out = _series_dict(env, L, stats)
+    out = _series_dict(env, L, stats, temps)
     out["agent_ok"] = ok
     out["agents_alive"] = ok.sum(axis=2)
     return out
