@@ -579,6 +579,47 @@ int dw_run_episode_trace_temperature(dw_handle* h, int32_t nsteps, const double*
                                      uint8_t* world_alive /* [K][B], may be NULL */, uint8_t* agent_ok /* [K][B][N], may be NULL */,
                                      dw_world_stats* trace /* [K][B], may be NULL */, dw_temp_stats* temps /* [K][B], required */);
 
+/* dw_run_episode_ensemble that also records, for every step and world, what dw_reduce would report after that step and
+ * the statistics of the temperature field that step computes: the population and temperature curves of every scenario
+ * of the reference's README - greedy, anti-greedy, random and no agents under light-and-dark and under neutral albedos,
+ * compared side by side (daisy/notebook_helpers.py:210-223 `update_fig_agent` after every env.step(action)) - as ONE
+ * device-resident run instead of one handle, one dw_set_params and one traced run per scenario.
+ * Contract: everything dw_run_episode_ensemble leaves on the handle and in world_alive / agent_ok for the same
+ * arguments - the planes, the retained previous state, the agents, dw_reduce, the device action buffer, the sum in
+ * dw_last_fixup_count, the flags, the "per-world" marks (saved and restored by the snapshots), DW_POLICY_ZEROS winning
+ * over use_table - this call leaves too, bit for bit, in DW_PRECISION_EXACT and DW_PRECISION_FAST (n_agents == 0 allowed).
+ *   trace[t*B + b]  the record dw_run_episode_trace writes for step t on a ONE-world handle that holds world b and its
+ *                   agents, carries worlds[b] (dw_set_params) and is given column b of the schedule and slice [:, b] of
+ *                   the table; reserved = 0.  Hence world_alive[t][b] == (trace[t*B+b].max_k > threshold_k), and the last
+ *                   row equals dw_reduce after the call.
+ *   temps[t*B + b]  the row dw_run_episode_trace_temperature writes on that one-world handle: the field `self.temp` of
+ *                   world b in step t, after the step's grazing and before its growth, at worlds[b] and
+ *                   L_schedule[t*B + b].  float64 in both precisions, reduced in the order of dw_reduce_temperature: both
+ *                   forms below return the same bytes, and a world without cover has std == 0.0 and min == max == mean.
+ * At least one of trace and temps is required (flags only: dw_run_episode_ensemble); a call without temps evaluates no
+ * float64 field.
+ * The forms are dw_run_episode_ensemble's.  H*W <= 256 with at most 64 agents: one wave per world
+ * (episode_wave_ens_trace_pw, csrc/dw_episode_wave_ens_trace_pw.hpp: episode_wave_pw's per-world rows in LDS with
+ * episode_wave_temp_pw's records; a world's float64 set is loaded once per launch, wave-uniformly, and only its L changes
+ * per step); a call whose rows pass 32 MiB takes several launches, each writing its flags and records from its first step's
+ * row on.  Every other shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step, with the on-demand
+ * reduction's kernels at each world's float64 row of the step between update_agents and the step kernel (dw_kernel_info:
+ * "; ensemble trace: one wave per world" / "launches per step").  Flags and records come down through the page-locked
+ * image in one copy while the staging buffer is at most 64 MiB; beyond (4096 steps of 1000 worlds: 229 MB) the image
+ * holds the inputs only and each output is copied straight into the caller's array.
+ * Checked before anything is launched or allocated (the state is untouched): the rules of dw_run_episode_ensemble, and
+ * DW_EINVAL when trace and temps are both null.  Synchronises.  Afterwards the handle is "per-world" as after
+ * dw_run_episode_ensemble. */
+int dw_run_episode_ensemble_trace(dw_handle* h, int32_t nsteps,
+                                  const dw_world_params* worlds /* [B] */,
+                                  const double* L_schedule      /* [nsteps][B] */,
+                                  int policy_mode, const uint8_t* use_table, const int8_t* table,
+                                  uint32_t threshold_k,
+                                  uint8_t* world_alive /* [K][B], may be NULL */,
+                                  uint8_t* agent_ok    /* [K][B][N], may be NULL */,
+                                  dw_world_stats* trace /* [K][B], may be NULL */,
+                                  dw_temp_stats* temps  /* [K][B], may be NULL */);
+
 /* ---- plumbing ------------------------------------------------------------------------------- */
 
 /* Use an existing HIP stream (e.g. torch's current stream) instead of the handle's own. */
@@ -596,7 +637,8 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark);
 /* Name and geometry of the step kernel the handle dispatches for its shape, for bench/profiles:
  * writes a NUL-terminated description into buf.  Appended fragments name the forms of the other entry points:
  * "; trace: ...", "; per-world L: ...", "; ensemble episode: ..." (dw_run_episode_ensemble), "; episode trace: ..."
- * (dw_run_episode_trace), "; episode temperature: ..." (dw_run_episode_trace_temperature) and
+ * (dw_run_episode_trace), "; episode temperature: ..." (dw_run_episode_trace_temperature), "; ensemble trace: ..."
+ * (dw_run_episode_ensemble_trace) and
  * "; episode: F; mlp episode: F" - the form dw_run_episode and
  * dw_run_episode_mlp take for the handle's shape, agent count, precision, collision mode and switches, F one of
  * "one wave per world" (H*W <= 256 and at most 64 agents, MLP: at most 4), "workgroup (LDS)" (H*W <= 4096) and

@@ -128,6 +128,8 @@ SIGNATURES = {
                                        C.POINTER(DwWorldStats)]),
     "dw_run_episode_trace_temperature": (C.c_int, [_vp, _i32, _pd, C.c_int, _pu8, C.POINTER(C.c_int8), _u32, _pu8, _pu8,
                                                    C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
+    "dw_run_episode_ensemble_trace": (C.c_int, [_vp, _i32, C.POINTER(DwWorldParams), _pd, C.c_int, _pu8, C.POINTER(C.c_int8),
+                                                _u32, _pu8, _pu8, C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
     "dw_set_stream": (C.c_int, [_vp, _vp]),
     "dw_sync": (C.c_int, [_vp]),
     "dw_timer_start": (C.c_int, [_vp]),

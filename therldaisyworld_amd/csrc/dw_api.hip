@@ -331,11 +331,16 @@ struct EpisodeBuffers {
     std::vector<unsigned char> ut_own;
 
     EpisodeBuffers(dw_handle* h_, const EpisodeStaging& S_) : h(h_), S(S_) {}
-    int alloc(bool staged) {
+    bool out_direct = false;                                    // the image holds the inputs only: finish() copies as a direct call
+    // `inputs_only` (staged): the image ends where the device's outputs begin - uploads as staged, finish() straight to
+    // the caller's arrays (dw_run_episode_ensemble_trace beyond fits_image(): its records alone may be hundreds of MB)
+    int alloc(bool staged, bool inputs_only = false) {
         if (int rc = ensure_ep_buf(h, S.total)) return rc;
         if (!staged) return DW_OK;
-        if (int rc = reserve(h->ep_pinned, "the page-locked episode staging", S.total, (size_t)1 << 20)) return rc;
+        const size_t image = inputs_only ? S.off[R::WORLD_ALIVE] : S.total;
+        if (int rc = reserve(h->ep_pinned, "the page-locked episode staging", image, (size_t)1 << 20)) return rc;
         img = h->ep_pinned.get();
+        out_direct = inputs_only;
         return DW_OK;
     }
     template <class T = unsigned char>
@@ -382,16 +387,17 @@ struct EpisodeBuffers {
                                                            {agent_ok, S.off[R::AGENT_OK], S.bytes[R::AGENT_OK]},
                                                            {trace, S.off[R::TRACE], S.stats_bytes},
                                                            {temps, S.temps_off(), S.temps_bytes}};
+        const bool staged = img && !out_direct;
         size_t lo = S.total, hi = 0;
         for (const auto& o : out) {
             if (!o.dst) continue;
-            if (!img) HIPCHK(hipMemcpyAsync(o.dst, h->ep_buf.get() + o.off, o.bytes, hipMemcpyDeviceToHost, h->stream));
+            if (!staged) HIPCHK(hipMemcpyAsync(o.dst, h->ep_buf.get() + o.off, o.bytes, hipMemcpyDeviceToHost, h->stream));
             lo = o.off < lo ? o.off : lo;
             hi = o.off + o.bytes > hi ? o.off + o.bytes : hi;
         }
-        if (img && hi > lo) HIPCHK(hipMemcpyAsync(img + lo, h->ep_buf.get() + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
+        if (staged && hi > lo) HIPCHK(hipMemcpyAsync(img + lo, h->ep_buf.get() + lo, hi - lo, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (img)
+        if (staged)
             for (const auto& o : out)
                 if (o.dst) std::memcpy(o.dst, img + o.off, o.bytes);
         return DW_OK;
@@ -2086,7 +2092,8 @@ static EpisodeIO episode_io(const dw_handle* h, int policy_mode, const EpisodeSt
 // step-1 sums of a pair would have to include the patch kernel's corrections, and the pair kernels take one constant set.
 // With `temps` (dw_run_episode_trace_temperature; the caller has allocated the reduction's partials): between a step's
 // update_agents and its step kernel, the statistics of the temperature field that step computes - temp_moments_pw on the
-// current planes at L_schedule[t] - into row t of the temperature block; single steps as with `trace`.
+// current planes at L_schedule[t], or with `worlds` (dw_run_episode_ensemble_trace) at each world's float64 row of the
+// step - into row t of the temperature block; single steps as with `trace`.
 static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                                 const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
                                 uint8_t* agent_ok, dw_world_stats* trace, WorldRows* worlds = nullptr, bool sym = false,
@@ -2184,8 +2191,9 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
             ++t;                                             // two steps done
             continue;
         }
-        if (temps)
-            if (int rc = launch_temp_moments(h, /*current=*/true, L_schedule[t], nullptr, trows + t * Bz)) return rc;
+        if (temps)                                              // (worlds: each world at its own float64 row of the step)
+            if (int rc = tab ? launch_temp_moments(h, /*current=*/true, 0.0, tab->lay.p64(tab->dev(), q.row_of[t]), trows + t * Bz)
+                             : launch_temp_moments(h, /*current=*/true, L_schedule[t], nullptr, trows + t * Bz)) return rc;
         if (tab) {
             const size_t tr = q.row_of[t];
             if (int rc = launch_forward_pw(h, tab->lay.p32(tab->dev(), tr), tab->lay.p64(tab->dev(), tr), tab->lay.fb(tab->dev()), sym, true)) return rc;
@@ -2319,12 +2327,14 @@ int dw_run_episode_trace_temperature(dw_handle* h, int32_t nsteps, const double*
 
 // ---- dw_run_episode_ensemble: dw_run_episode with a set of physics constants and a luminosity column per world --------
 // The form the call takes: one wave per world (episode_wave_pw) wherever dw_run_episode takes episode_wave; every other
-// shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step, no LDS workgroup kernel
-int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params* worlds, const double* L_schedule, int policy_mode,
-                            const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
-                            uint8_t* agent_ok) {
-    NEED(h && worlds && L_schedule, DW_EINVAL, "null argument");
-    NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
+// shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step, no LDS workgroup kernel.
+// `records` (dw_run_episode_ensemble_trace): also the records of every step (`trace`) and the temperature records
+// (`temps`), [K][B] each, either may be null; the same dispatch with episode_wave_ens_trace_pw<EXACT, temps given>, which
+// always writes the cover records on the device, or the launches per step with the rows of the per-world table.
+static int run_episode_ensemble_impl(dw_handle* h, int32_t nsteps, const dw_world_params* worlds, const double* L_schedule,
+                                     int policy_mode, const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
+                                     uint8_t* world_alive, uint8_t* agent_ok, bool records, dw_world_stats* trace,
+                                     dw_temp_stats* temps) {
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
     // every check before anything is launched or allocated: the rules of dw_run_episode, of the per-world schedules, and
@@ -2335,29 +2345,42 @@ int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params*
     const bool wave = episode_form(h) == EPISODE_WAVE;
     WorldRows rows_of(p, worlds, Bz, !wave);
     if (int rc = check_per_world(rows_of, worlds, L_schedule, K, Bz)) return rc;
-    if (!wave)
-        return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, nullptr,
-                                    &rows_of, worlds_symmetric(worlds, Bz) && !h->sw.no_sym);
-    const size_t lds = episode_wave_pw_shared_bytes() + episode_wave_pw_world_bytes(C, N) * 4;
+    if (!wave) {
+        if (temps)                                              // the partials of temp_moments_pw (the rows live in the staging buffer)
+            if (int rc = alloc_group(h, "the temperature reduction", {{h->temp_part, temp_part_bytes(h)}})) return rc;
+        return run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace,
+                                    &rows_of, worlds_symmetric(worlds, Bz) && !h->sw.no_sym, temps);
+    }
+    const size_t lds = records ? episode_wave_ens_trace_lds_bytes(C, N)
+                               : episode_wave_pw_shared_bytes() + episode_wave_pw_world_bytes(C, N) * 4;
     NEED(lds <= 160 * 1024, DW_EINVAL, "too many agents for the LDS-resident episode kernel");
     // The kernel keeps a world in LDS for a whole launch; a call is one launch unless its table of rows (136 B per step and
     // world) would pass 32 MiB: then launches of `rows` steps (a multiple of the 64-step segment), each continuing from the
-    // planes and agents the one before it wrote back - the same states, step for step.
+    // planes and agents the one before it wrote back - the same states, step for step - and writing its flags and records
+    // from row t0 of their blocks on.
     const size_t row_bytes = (sizeof(PhysF32) + sizeof(double)) * Bz;
     size_t rows = ((size_t)32 << 20) / row_bytes / kEwSeg * kEwSeg;
     rows = rows < (size_t)kEwSeg ? (size_t)kEwSeg : rows;
     rows = rows > K ? K : rows;
-    // always staged: the first launch's inputs in ONE copy, a later launch's rows in one more, the call's flags in one
+    // staged: the first launch's inputs in ONE copy, a later launch's rows in one more, the call's flags (and records) in
+    // one.  Flags only: always.  With records while the whole buffer fits the page-locked image (EpisodeStaging::fits_image);
+    // beyond, the image holds the inputs alone and the outputs come down straight into the caller's arrays.
     EpisodeRegions regions;
     regions.rows = rows; regions.per_world = true; regions.use_table = true;
+    regions.trace = records; regions.temps = records && temps != nullptr;
     EpisodeBuffers E(h, EpisodeStaging(K, Bz, (size_t)N, regions));
-    if (int rc = E.alloc(true)) return rc;
+    if (int rc = E.alloc(true, records && !E.S.fits_image())) return rc;
     SyncOnExit guard(h->stream);                                // the image
     PhysF64* p64 = E.S.at<PhysF64>(E.img, EpisodeStaging::P64);
     for (size_t b = 0; b < Bz; ++b) p64[b] = make_f64(rows_of.params(b), 0.0);   // (L: replaced by the step's, from the Ls rows)
     const bool ex = p.precision == DW_PRECISION_EXACT;
-    auto kern = ex ? episode_wave_pw<true> : episode_wave_pw<false>;
-    if (int rc = set_lds_limit(h, kern, lds)) return rc;
+    const dim3 grid((unsigned)((B + 3) / 4));
+    auto plain_kern = ex ? episode_wave_pw<true> : episode_wave_pw<false>;
+    auto rec_kern = temps ? (ex ? episode_wave_ens_trace_pw<true, true> : episode_wave_ens_trace_pw<false, true>)
+                          : (ex ? episode_wave_ens_trace_pw<true, false> : episode_wave_ens_trace_pw<false, false>);
+    if (int rc = records ? set_lds_limit(h, rec_kern, lds) : set_lds_limit(h, plain_kern, lds)) return rc;
+    StatsDev* const d_trace = E.dev<StatsDev>(EpisodeStaging::TRACE);
+    TempStatsDev* const d_temps = reinterpret_cast<TempStatsDev*>(h->ep_buf.get() + E.S.temps_off());
     PhysF32* r32 = E.p32();
     for (size_t t0 = 0; t0 < K; t0 += rows) {
         const size_t kk = K - t0 < rows ? K - t0 : rows;
@@ -2365,17 +2388,47 @@ int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params*
         for (size_t t = 0; t < kk; ++t) rows_of.single(L_schedule + (t0 + t) * Bz, r32 + t * Bz, nullptr);
         if (int rc = E.upload(L_schedule + t0 * Bz, kk * Bz, t0 == 0, use_table, table)) return rc;
         // (every world's whole record is assigned by the kernel)
-        const EpisodeWavePwArgs A{episode_io(h, policy_mode, E.S, t0, true, use_table != nullptr, table && E.S.bn),
-                                  E.dev<const PhysF64>(EpisodeStaging::P64), B, N, p.height, p.width, (int)kk, policy_mode,
-                                  p.obs_mask, threshold_k, p.agent_gamma};
-        hipLaunchKernelGGL(kern, dim3((unsigned)((B + 3) / 4)), dim3(256), lds, h->stream, A);
+        const EpisodeIO io = episode_io(h, policy_mode, E.S, t0, true, use_table != nullptr, table && E.S.bn);
+        if (records) {
+            const EpisodeWaveEnsTraceArgs A{io, d_trace + t0 * Bz, temps ? d_temps + t0 * Bz : nullptr,
+                                            E.dev<const PhysF64>(EpisodeStaging::P64), B, N, p.height, p.width, (int)kk, policy_mode,
+                                            p.obs_mask, threshold_k, p.agent_gamma};
+            hipLaunchKernelGGL(rec_kern, grid, dim3(256), lds, h->stream, A);
+        } else {
+            const EpisodeWavePwArgs A{io, E.dev<const PhysF64>(EpisodeStaging::P64), B, N, p.height, p.width, (int)kk, policy_mode,
+                                      p.obs_mask, threshold_k, p.agent_gamma};
+            hipLaunchKernelGGL(plain_kern, grid, dim3(256), lds, h->stream, A);
+        }
         HIPCHK(hipGetLastError());
         episode_done(h, 0.0, true);
     }
     release_unquantised(h);
-    if (int rc = E.finish(world_alive, agent_ok, nullptr)) return rc;   // flags are returned
+    if (int rc = E.finish(world_alive, agent_ok, trace, temps)) return rc;   // flags (and records) are returned
     guard.disarm();
     return DW_OK;
+}
+
+int dw_run_episode_ensemble(dw_handle* h, int32_t nsteps, const dw_world_params* worlds, const double* L_schedule, int policy_mode,
+                            const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
+                            uint8_t* agent_ok) {
+    NEED(h && worlds && L_schedule, DW_EINVAL, "null argument");
+    NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
+    return run_episode_ensemble_impl(h, nsteps, worlds, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
+                                     agent_ok, false, nullptr, nullptr);
+}
+
+// ---- dw_run_episode_ensemble_trace: dw_run_episode_ensemble with the records of every step ------------------------------
+// The form the call takes is dw_run_episode_ensemble's: one wave per world (episode_wave_ens_trace_pw), or launches per
+// step with temp_moments_pw at the world's own float64 row in front of every step kernel.  Both reduce in
+// temp_moments_pw's order: the same bytes.
+int dw_run_episode_ensemble_trace(dw_handle* h, int32_t nsteps, const dw_world_params* worlds, const double* L_schedule,
+                                  int policy_mode, const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
+                                  uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace, dw_temp_stats* temps) {
+    NEED(h && worlds && L_schedule, DW_EINVAL, "null argument");
+    NEED(trace || temps, DW_EINVAL, "dw_run_episode_ensemble_trace needs a trace or a temps array (flags only: dw_run_episode_ensemble)");
+    NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
+    return run_episode_ensemble_impl(h, nsteps, worlds, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
+                                     agent_ok, true, trace, temps);
 }
 
 // ---- device-side snapshots of the current state ----------------------------------------------------
@@ -2607,6 +2660,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_run_episode_trace_temperature takes
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, "; episode temperature: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
+    }
+    {                                                           // the form dw_run_episode_ensemble_trace takes
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; ensemble trace: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

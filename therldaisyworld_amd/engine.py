@@ -458,13 +458,19 @@ class Engine:
             _ffi.ptr_u8(ok) if self.N else None, stats.ctypes.data_as(C.POINTER(DwWorldStats))))
         return stats, alive.view(np.bool_), ok.view(np.bool_)
 
-    def run_episode_ensemble(self, worlds, Ls, mode, use_table=None, table=None, threshold_k=5):
+    def run_episode_ensemble(self, worlds, Ls, mode, use_table=None, table=None, threshold_k=5, trace=False,
+                             temperature=False):
         """`run_episode` with the physics constants `worlds[b]` (as `step_n_trace_ensemble` takes them) and the luminosity
         column `Ls[:, b]` of world b (`dw_run_episode_ensemble`): `Ls` is (K, B).  Each world ends, and reports the flags,
         exactly as a one-world engine with those constants, that column and slice `[:, b]` of the table would after
         `run_episode`.  Returns (world_alive (K,B) bool, agent_ok (K,B,N) bool).  The engine's own params are unchanged;
         afterwards it is "per-world" as after `step_n_trace_ensemble`: `download_grid`, `get_obs`, `download_caches` and
-        `reduce_temperature` raise until a shared-L step or an upload."""
+        `reduce_temperature` raise until a shared-L step or an upload.
+
+        `trace=True` and / or `temperature=True` (`dw_run_episode_ensemble_trace`): returns (world_alive, agent_ok, stats,
+        temps) - `stats` (K, B) of dtype `_ffi.STATS_DTYPE`, the records `run_episode_trace` writes on that one-world
+        engine, `temps` (K, B) of dtype `_ffi.TEMP_STATS_DTYPE`, its temperature rows (world b at `worlds[b]` and
+        `Ls[t, b]`); the one not asked for is None and costs nothing.  Flags, state and agents are unchanged by either."""
         tab = self._world_table(worlds)
         L = np.ascontiguousarray(Ls, dtype=np.float64)
         if L.ndim != 2 or L.shape[1] != self.B:
@@ -478,6 +484,16 @@ class Engine:
             raise ValueError(f"table must have shape {(K, self.B, self.N)}")
         alive = np.empty((K, self.B), dtype=np.uint8)
         ok = np.empty((K, self.B, self.N), dtype=np.uint8)
+        if trace or temperature:
+            stats = np.zeros((K, self.B), dtype=_ffi.STATS_DTYPE) if trace else None
+            temps = np.zeros((K, self.B), dtype=_ffi.TEMP_STATS_DTYPE) if temperature else None
+            self._check(self._lib.dw_run_episode_ensemble_trace(
+                self._h, K, tab.ctypes.data_as(C.POINTER(_ffi.DwWorldParams)), _ffi.ptr_d(L), int(mode), _ffi.ptr_u8(ut),
+                None if tb is None else tb.ctypes.data_as(C.POINTER(C.c_int8)), int(threshold_k), _ffi.ptr_u8(alive),
+                _ffi.ptr_u8(ok) if self.N else None,
+                None if stats is None else stats.ctypes.data_as(C.POINTER(DwWorldStats)),
+                None if temps is None else temps.ctypes.data_as(C.POINTER(DwTempStats))))
+            return alive.view(np.bool_), ok.view(np.bool_), stats, temps
         self._check(self._lib.dw_run_episode_ensemble(
             self._h, K, tab.ctypes.data_as(C.POINTER(_ffi.DwWorldParams)), _ffi.ptr_d(L), int(mode), _ffi.ptr_u8(ut),
             None if tb is None else tb.ctypes.data_as(C.POINTER(C.c_int8)), int(threshold_k), _ffi.ptr_u8(alive),

@@ -590,6 +590,96 @@ def simulate_lifespan_sweep(env, scenarios, worlds_per_scenario, chunk=32, obs=N
     return done_at, agents_done_at, table
 
 
+def simulate_grazing_sweep(env, scenarios, worlds_per_scenario, nsteps, chunk=64, obs=None, temperature=False):
+    """The population (and temperature) curves of several scenarios side by side from ONE device-resident run - the
+    reference README's comparison of greedy, anti-greedy, random and no agents under light-and-dark and under neutral
+    albedos, which shows when regulation breaks and why - instead of one environment, one configuration and one
+    `simulate_grazing` per scenario.
+
+    `scenarios`, `worlds_per_scenario` and `obs` are `simulate_lifespan_sweep`'s: scenario s owns the contiguous block of
+    worlds [s * Bs, (s + 1) * Bs), and `env.batch_size == len(scenarios) * Bs`.  Every scenario runs exactly `nsteps`
+    steps of the environment's own luminosity ramp: there is no stopping rule, as in `simulate_grazing`.
+
+    The first step starts from the un-quantised state as in `simulate_lifespan_sweep` (the policies' actions block by
+    block, `dw_update_agents`, one step of `dw_step_n_trace_ensemble`, which gives the first row of records and
+    temperature rows, `dw_get_reward_done`); then chunks of `chunk` steps of `dw_run_episode_ensemble_trace` with the
+    action table filled per block (`_sweep_action_table`, every scenario running).
+
+    Returns a dict with every per-world entry reshaped to (n, S, Bs, ...): `L` (n,); `mean_light`, `mean_dark`,
+    `max_cover`, `alive` and `stats` (n, S, Bs); `agent_ok` (n, S, Bs, N) bool and `agents_alive` (n, S, Bs) int; `params`,
+    the (S * Bs,) table of constants the run used.  `temperature=True`: also `mean_temp`, `std_temp`, `min_temp`,
+    `max_temp` (n, S, Bs) in kelvin and `dead_temp` (n, S, Bs), each world's lifeless temperature from its own `S`,
+    `albedo_bare` and `sigma`.  Block s of every entry is what `simulate_grazing` returns for that block of worlds with the
+    scenario's constants set on the environment when its epsilon is 0 (or it has no agent); a scenario with epsilon > 0
+    draws in `_sweep_action_table`'s order: statistically equivalent, not bit-equal.  Afterwards the worlds have no
+    common constants: `env.step()` and `env.grid` raise until `env.reset()`, as after `simulate_lifespan_sweep`."""
+    S, Bs = len(scenarios), int(worlds_per_scenario)
+    if S < 1 or Bs < 1 or int(env.batch_size) != S * Bs:
+        raise ValueError(f"env.batch_size ({int(env.batch_size)}) must be len(scenarios) * worlds_per_scenario ({S} * {Bs})")
+    for s, sc in enumerate(scenarios):
+        if sc.get("agent") is not None and type(sc["agent"]) is not Greedy:
+            raise ValueError(f"scenario {s}: the agent must be a Greedy or None")
+    if env.precision == "f64" or env.collision_mode != 0:
+        raise ValueError("simulate_grazing_sweep runs device-resident: precision 'exact' or 'fast', collision_mode 0")
+    n, K = int(nsteps), int(chunk)
+    if n < 1:
+        raise ValueError("nsteps must be at least 1")
+    if K < 1:
+        raise ValueError("chunk must be at least 1")
+    table = _sweep_param_table(env, scenarios, Bs)
+    if obs is None:
+        obs = env.reset()
+    B, N = S * Bs, int(env.n_agents)
+    L = np.zeros(n, dtype=np.float64)
+    stats = np.zeros((n, B), dtype=_ffi.STATS_DTYPE)
+    ok = np.zeros((n, B, N), dtype=bool)
+    temps = np.zeros((n, B), dtype=_ffi.TEMP_STATS_DTYPE) if temperature else None
+    running = np.ones(S, dtype=bool)
+    eng = env._ensure_engine()
+    env._sync_to_device()
+    # step 1: the initial state is not quantised (ref initialize_grid)
+    if N:
+        action = np.zeros((B, N, 1), dtype=np.int64)
+        for s, sc in enumerate(scenarios):
+            if sc.get("agent") is not None:
+                action[s * Bs:(s + 1) * Bs] = sc["agent"](obs[s * Bs:(s + 1) * Bs])
+        eng.update_agents(action)
+    L[0] = _luminosity_schedule(env, 1)[0]
+    first = eng.step_n_trace_ensemble(table, np.full((1, B), L[0], dtype=np.float64), temperature=temperature)
+    if temperature:
+        stats[:1], temps[:1] = first
+    else:
+        stats[:1] = first
+    _, done = eng.reward_done()
+    if N:
+        ok[0] = ~np.asarray(done).reshape(B, N)
+    _advance_host_scalars(env, 1)
+    env._per_world_L = True
+    t = 1
+    while t < n:
+        k = min(K, n - t)
+        Ls = np.asarray(_luminosity_schedule(env, k), dtype=np.float64)
+        L[t:t + k] = Ls
+        actions = _sweep_action_table(scenarios, running, k, Bs, N)
+        _, ok[t:t + k], stats[t:t + k], rows = eng.run_episode_ensemble(
+            table, np.repeat(Ls[:, None], B, axis=1), _ffi.POLICY_TABLE, None, actions, LIFESPAN_THRESHOLD_K, trace=True,
+            temperature=temperature)
+        if temperature:
+            temps[t:t + k] = rows
+        _advance_host_scalars(env, k)
+        t += k
+    out = _series_dict(env, L, stats, temps)
+    if temperature:
+        out["dead_temp"] = ((table["S"] * L[:, None] * (1 - table["albedo_bare"])) / table["sigma"]) ** (1 / 4)
+    out["agent_ok"] = ok
+    out["agents_alive"] = ok.sum(axis=2)
+    for key, value in out.items():
+        if key != "L":
+            out[key] = value.reshape((n, S, Bs) + value.shape[2:])
+    out["params"] = table
+    return out
+
+
 def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_chunk):
     """The step loop shared by the two fitness harnesses: chunks of steps device-resident
     (``dw_run_episode_mlp``), the reference's per-step float64 bookkeeping done by `after_chunk(rewards,
