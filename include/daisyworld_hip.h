@@ -96,7 +96,10 @@ typedef struct dw_handle dw_handle;
  * reset(), e.g. notebooks/greedy_longevity_abatement.ipynb cell 2:3-8). */
 typedef struct dw_params {
     int32_t abi_version;      /* must be DW_ABI_VERSION */
-    int32_t batch;            /* B: worlds in this handle (ref batch_size, :20) */
+    int32_t batch;            /* B: worlds in this handle (ref batch_size, :20).  No cap of its own: every call takes
+                                 ensembles of more than 65 535 worlds (the launches that spread worlds over a grid
+                                 dimension go in slices of that many); the limits are H*W <= 2^31-1 cells per world,
+                                 B*H*W < 9e18 cells and the device's memory */
     int32_t height;           /* H = grid_dimension (:29) */
     int32_t width;            /* W = grid_dimension; H != W is allowed (ft_convolve accepts it) */
     int32_t n_agents;         /* N agents per world (:79); 0 allowed */

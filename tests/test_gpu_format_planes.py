@@ -114,7 +114,11 @@ def test_exact_mode_against_the_oracle(amd, monkeypatch, shape):
 
 def test_world_base_beyond_32_bits(amd, monkeypatch):
     """34 worlds of 8192^2: a plane is 4.25 GiB, so the bases of worlds 32 and 33 do not fit 32 bits.  Per-world reductions
-    of all worlds and 8 sampled rows of worlds 0, 16 and 33, fast mode, 4 steps, one handle after the other."""
+    of all worlds and 8 sampled rows of worlds 0, 16 and 33, fast mode, 4 steps, one handle after the other.
+
+    This compares two builds of the step pairs with each other, at thresholds that fall on world boundaries.  The test of
+    the addressing itself - every kernel family past 2^32 cells with the thresholds inside a world, against small handles
+    holding the same global worlds and against the C oracle - is tests/test_gpu_large_offsets.py."""
     from therldaisyworld_amd import _ffi
     B, H, W = 34, 8192, 8192
     hip = ctypes.CDLL("libamdhip64.so")

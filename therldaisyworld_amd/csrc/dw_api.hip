@@ -491,10 +491,20 @@ static int launch_tiled(dw_handle* h, const plane_t* iL, const plane_t* iD, cons
     return DW_OK;
 }
 
-// one thread per cell (several for big jobs: *cpt): the grid of step_generic / step_generic_pw
-static dim3 generic_grid(const dw_params& p, int* cpt) {
+// The kernels that take their world from blockIdx.y - one thread per cell, or a chunk of cells per workgroup - are launched
+// on grids (x, worlds), and a grid holds 65 535 workgroups in y: an ensemble of more worlds goes in slices of that many,
+// f(b0, nb) for the worlds [b0, b0 + nb).  f advances every per-world address by b0 itself (planes by b0 * H * W cells,
+// tables and records by b0 entries), so the kernels see a batch of nb worlds and index inside the slice as ever.
+constexpr int kGridWorlds = 65535;
+template <class F>
+static void for_world_slices(int batch, F&& f) {
+    for (int b0 = 0; b0 < batch; b0 += kGridWorlds) f(b0, batch - b0 < kGridWorlds ? batch - b0 : kGridWorlds);
+}
+
+// one thread per cell (several for big jobs: *cpt): the x extent of the grid of step_generic / step_generic_pw
+static unsigned generic_grid_x(const dw_params& p, int* cpt) {
     *cpt = generic_cells_per_thread(p.batch, (long long)p.height * p.width);
-    return dim3((unsigned)(((long long)p.height * p.width + 256LL * *cpt - 1) / (256LL * *cpt)), (unsigned)p.batch);
+    return (unsigned)(((long long)p.height * p.width + 256LL * *cpt - 1) / (256LL * *cpt));
 }
 
 // ... any input format
@@ -502,9 +512,28 @@ template <class T, int PREC>
 static auto launch_generic(dw_handle* h, const T* iL, const T* iD, const StepOut& o, const FirstStepBound& fb = {}) {
     const dw_params& p = h->prm;
     int cpt;
-    const dim3 grid = generic_grid(p, &cpt);
-    hipLaunchKernelGGL((step_generic<T, PREC>), grid, dim3(256), 0, h->stream, iL, iD, o.L, o.D, p.height, p.width, o.P, o.P64,
-                       o.stats, o.fixups, o.zero_me, o.zero_n, cpt, fb);
+    const unsigned gx = generic_grid_x(p, &cpt);
+    const size_t n = (size_t)p.height * p.width;
+    for_world_slices(p.batch, [&](int b0, int nb) {               // (every slice clears zero_me: the same zeros again)
+        const size_t w = (size_t)b0 * n;
+        hipLaunchKernelGGL((step_generic<T, PREC>), dim3(gx, (unsigned)nb), dim3(256), 0, h->stream, iL + w, iD + w, o.L + w,
+                           o.D + w, p.height, p.width, o.P, o.P64, o.stats + b0, o.fixups, o.zero_me, o.zero_n, cpt, fb);
+    });
+}
+
+// the materialise launches of a batch: [B][7], [B][3], [B][3], [B][2] and [B] planes out (null: not wanted)
+template <class PrevT, bool POST>
+static void launch_materialise(dw_handle* h, const PrevT* pL, const PrevT* pD, const plane_t* cL, const plane_t* cD,
+                               const PhysF64& P, double* grid7, double* temps, double* betas, double* growth, double* teff) {
+    const dw_params& p = h->prm;
+    const size_t n = (size_t)p.height * p.width;
+    auto at = [](double* q, size_t off) { return q ? q + off : q; };
+    for_world_slices(p.batch, [&](int b0, int nb) {
+        const size_t w = (size_t)b0 * n;
+        hipLaunchKernelGGL((materialise<PrevT, POST>), dim3((unsigned)((n + 255) / 256), (unsigned)nb), dim3(256), 0, h->stream,
+                           pL + w, pD + w, cL + w, cD + w, p.height, p.width, P, at(grid7, 7 * w), at(temps, 3 * w),
+                           at(betas, 3 * w), at(growth, 2 * w), at(teff, w));
+    });
 }
 
 // the first step from the un-quantised state, read in its upload format (StepPlan::first_prec, first_stream)
@@ -633,9 +662,14 @@ static int launch_forward_pw(dw_handle* h, const PhysF32* row32, const PhysF64* 
     const bool ex = p.precision == DW_PRECISION_EXACT;
     auto generic = [&](auto* iL, auto* iD, auto PR) {
         int cpt;
-        const dim3 grid = generic_grid(p, &cpt);
-        hipLaunchKernelGGL((step_generic_pw<elem_t<decltype(iL)>, PR>), grid, dim3(256), 0, h->stream, iL, iD, o.L, o.D,
-                           p.height, p.width, row32, row64, rowfb, o.stats, o.fixups, o.zero_me, o.zero_n, cpt);
+        const unsigned gx = generic_grid_x(p, &cpt);
+        const size_t n = (size_t)p.height * p.width;
+        for_world_slices(p.batch, [&](int b0, int nb) {
+            const size_t w = (size_t)b0 * n;
+            hipLaunchKernelGGL((step_generic_pw<elem_t<decltype(iL)>, PR>), dim3(gx, (unsigned)nb), dim3(256), 0, h->stream,
+                               iL + w, iD + w, o.L + w, o.D + w, p.height, p.width, row32 + b0, row64 + b0,
+                               rowfb ? rowfb + b0 : rowfb, o.stats + b0, o.fixups, o.zero_me, o.zero_n, cpt);
+        });
     };
     const plane_t* iL = h->L16[h->cur].get();
     const plane_t* iD = h->D16[h->cur].get();
@@ -698,8 +732,12 @@ static int launch_temp_moments(dw_handle* h, bool current, double L, const PhysF
     TempPartial* part = h->temp_part.get();
     auto reduce = [&](auto* iL, auto* iD) {
         with_bool(row64 != nullptr, [&](auto TABLE) {
-            hipLaunchKernelGGL((temp_moments_pw<elem_t<decltype(iL)>, TABLE>), dim3((unsigned)chunks, (unsigned)p.batch), dim3(256),
-                               0, h->stream, iL, iD, p.height, p.width, P, row64, part);
+            for_world_slices(p.batch, [&](int b0, int nb) {
+                const size_t w = (size_t)b0 * p.height * p.width;
+                hipLaunchKernelGGL((temp_moments_pw<elem_t<decltype(iL)>, TABLE>), dim3((unsigned)chunks, (unsigned)nb), dim3(256),
+                                   0, h->stream, iL + w, iD + w, p.height, p.width, P, row64 ? row64 + b0 : row64,
+                                   part + (size_t)b0 * chunks);
+            });
         });
     };
     if (current) with_planes(h, h->unq == OWN_CUR, h->cur, reduce);
@@ -840,10 +878,13 @@ static auto init_random_into(dw_handle* h, uint64_t seed, T* L, T* D) {
     const dw_params& p = h->prm;
     if (int crc = clear_stats(h)) return crc;
     const int ncell = p.height * p.width;
-    const dim3 g((unsigned)((ncell + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
-    hipLaunchKernelGGL((init_random_cells<T>), g, dim3(256), 0, h->stream, L, D, ncell,
-                       (long long)p.world_offset, (unsigned long long)seed, (float)p.light_proportion,
-                       (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp].get());
+    for_world_slices(p.batch, [&](int b0, int nb) {              // (the draw is keyed by the GLOBAL world id: offset + b0 + b)
+        const dim3 g((unsigned)((ncell + kInitChunk - 1) / kInitChunk), (unsigned)nb);
+        const size_t w = (size_t)b0 * ncell;
+        hipLaunchKernelGGL((init_random_cells<T>), g, dim3(256), 0, h->stream, L + w, D + w, ncell,
+                           (long long)p.world_offset + b0, (unsigned long long)seed, (float)p.light_proportion,
+                           (float)p.dark_proportion, (float)p.initial_al, (float)p.initial_ad, h->stats2[h->sp].get() + b0);
+    });
     HIPCHK(hipGetLastError());
     if (p.n_agents) {
         const int bn = p.batch * p.n_agents;
@@ -904,7 +945,10 @@ static int check_params(const dw_params* p) {
     NEED(p->batch >= 1 && p->height >= 3 && p->width >= 3, DW_EINVAL,
          "need batch>=1 and grid >= 3x3 (got B=%d H=%d W=%d)", p->batch, p->height, p->width);
     NEED(p->height <= 65535 && p->width <= 65532, DW_EINVAL, "grid dimension too large");
-    // cell indices inside one world are int32 in the host code and in every kernel
+    // cell indices inside one world are int32 in the host code and in every kernel; everything above a world - its base,
+    // the per-world tables and records - is 64-bit.  The batch has no cap of its own: the kernels that take the world from
+    // blockIdx.y are launched in slices of 65 535 worlds (for_world_slices), every other kernel numbers strips, tiles or
+    // worlds in blockIdx.x (tests/test_gpu_large_offsets.py: 70 000 and 1 943 000 worlds, 2^32 cells)
     NEED((long long)p->height * p->width <= 0x7fffffffLL, DW_EINVAL,
          "a world of %dx%d cells exceeds the 2^31-1 cells per world the kernels index", p->height, p->width);
     NEED(p->n_agents >= 0, DW_EINVAL, "n_agents < 0");
@@ -1008,9 +1052,13 @@ static int refresh_stats(dw_handle* h) {
     const dw_params& p = h->prm;
     if (int rc = clear_stats(h)) return rc;
     const int n = p.height * p.width;
-    const dim3 g((unsigned)((n + kInitChunk - 1) / kInitChunk), (unsigned)p.batch);
     auto reduce = [&](auto* L, auto* D) {
-        hipLaunchKernelGGL((stats_only<elem_t<decltype(L)>>), g, dim3(256), 0, h->stream, L, D, n, h->stats2[h->sp].get());
+        for_world_slices(p.batch, [&](int b0, int nb) {
+            const dim3 g((unsigned)((n + kInitChunk - 1) / kInitChunk), (unsigned)nb);
+            const size_t w = (size_t)b0 * n;
+            hipLaunchKernelGGL((stats_only<elem_t<decltype(L)>>), g, dim3(256), 0, h->stream, L + w, D + w, n,
+                               h->stats2[h->sp].get() + b0);
+        });
     };
     if (cur_quantised(h)) reduce(h->L16[h->cur].get(), h->D16[h->cur].get());
     else with_unq_planes(h, reduce);
@@ -1153,13 +1201,11 @@ int dw_download_planes(dw_handle* h, int which, double* light, double* dark) {
 static int run_materialise(dw_handle* h, double L, double* d_grid7, double* d_temps, double* d_betas,
                            double* d_growth, double* d_teff) {
     const dw_params& p = h->prm;
-    const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
     const PhysF64 P = make_f64(p, h->stepped && !h->L_per_world ? h->L_last : L);   // (per-world: dw_download_caches' own L)
     const plane_t* cL = h->L16[h->cur].get();            // read by the POST variants only
     const plane_t* cD = h->D16[h->cur].get();
     with_derived_from(h, [&](auto* pL, auto* pD, auto POST) {
-        hipLaunchKernelGGL((materialise<elem_t<decltype(pL)>, POST>), g, dim3(256), 0, h->stream, pL, pD, cL, cD, p.height,
-                           p.width, P, d_grid7, d_temps, d_betas, d_growth, d_teff);
+        launch_materialise<elem_t<decltype(pL)>, POST>(h, pL, pD, cL, cD, P, d_grid7, d_temps, d_betas, d_growth, d_teff);
     });
     HIPCHK(hipGetLastError());
     if (h->stepped && d_grid7 && p.n_agents && h->have_agents) {
@@ -1575,13 +1621,16 @@ int dw_forward_f64(dw_handle* h, const double* light, const double* dark, double
     }
     const PhysF32 P = derive_f32(p, L);
     const PhysF64 P64 = make_f64(p, L);
-    const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
     unsigned long long* tmp_fix = &tmp_stats[p.batch].sum_l;
-    hipLaunchKernelGGL((step_generic<double, 2>), g, dim3(256), 0, h->stream, dL, dD, nL, nD, p.height, p.width, P,
-                       P64, tmp_stats, tmp_fix, (unsigned long long*)nullptr, 0);
-    hipLaunchKernelGGL((materialise<double, true>), g, dim3(256), 0, h->stream, dL, dD, nL, nD, p.height, p.width,
-                       P64, dG, temps ? d_t : (double*)nullptr, betas ? d_b : (double*)nullptr,
-                       growth ? d_g : (double*)nullptr, temp_effective ? d_e : (double*)nullptr);
+    for_world_slices(p.batch, [&](int b0, int nb) {
+        const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)nb);
+        const size_t w = (size_t)b0 * p.height * p.width;
+        hipLaunchKernelGGL((step_generic<double, 2>), g, dim3(256), 0, h->stream, dL + w, dD + w, nL + w, nD + w, p.height,
+                           p.width, P, P64, tmp_stats + b0, tmp_fix, (unsigned long long*)nullptr, 0);
+    });
+    launch_materialise<double, true>(h, dL, dD, nL, nD, P64, dG, temps ? d_t : (double*)nullptr,
+                                     betas ? d_b : (double*)nullptr, growth ? d_g : (double*)nullptr,
+                                     temp_effective ? d_e : (double*)nullptr);
     hipError_t le = hipGetLastError();
     if (le == hipSuccess && p.n_agents && h->have_agents) {
         hipLaunchKernelGGL(agents_stamp, dim3((p.batch + 63) / 64), dim3(64), 0, h->stream, dG, h->idx.get(), h->st.get(),
@@ -1614,8 +1663,11 @@ int dw_conv3x3_f64(dw_handle* h, const double* plane, const double kernel[9], do
     for (int i = 0; i < 9; ++i) K.k[i] = kernel[i];
     SyncOnExit guard(h->stream);                              // `plane` / `out` are the caller's
     HIPCHK(hipMemcpyAsync(d_in, plane, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
-    hipLaunchKernelGGL(conv3x3_f64, g, dim3(256), 0, h->stream, d_in, d_out, p.height, p.width, K);
+    for_world_slices(p.batch, [&](int b0, int nb) {
+        const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)nb);
+        const size_t w = (size_t)b0 * p.height * p.width;
+        hipLaunchKernelGGL(conv3x3_f64, g, dim3(256), 0, h->stream, d_in + w, d_out + w, p.height, p.width, K);
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -1639,9 +1691,12 @@ int dw_stage_f64(dw_handle* h, int stage, const double* in, double* out, double 
     const PhysF64 P = make_f64(p, L);
     SyncOnExit guard(h->stream);                              // `in` / `out` are the caller's
     HIPCHK(hipMemcpyAsync(d_in, in, sizeof(double) * nin * n, hipMemcpyHostToDevice, h->stream));
-    const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
     with_int<kStageAlbedo, kStageDensity, kStageTemperature, kStageGrowthRate, kStageGrowth>(stage, [&](auto S) {
-        hipLaunchKernelGGL((stage_f64<S>), g, dim3(256), 0, h->stream, d_in, d_out, p.batch, p.height, p.width, P, K);
+        for_world_slices(p.batch, [&](int b0, int nb) {          // (the kernel's B is the stride between planes: the batch's)
+            const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)nb);
+            const size_t w = (size_t)b0 * p.height * p.width;
+            hipLaunchKernelGGL((stage_f64<S>), g, dim3(256), 0, h->stream, d_in + w, d_out + w, p.batch, p.height, p.width, P, K);
+        });
     });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof(double) * nout * n, hipMemcpyDeviceToHost, h->stream));
@@ -2691,9 +2746,12 @@ int dw_audit_tie_bound(dw_handle* h, double L, double out[4]) {
     if (rc) return rc;
     unsigned long long* d = reinterpret_cast<unsigned long long*>(h->scratch.get());
     HIPCHK(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), h->stream));
-    const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)p.batch);
-    hipLaunchKernelGGL(tie_audit, g, dim3(256), 0, h->stream, h->L16[h->cur].get(), h->D16[h->cur].get(), p.height, p.width,
-                       derive_f32(p, L), make_f64(p, L), d, pl.sym_albedo && pl.kind == STEP_STREAM ? 1 : 0);
+    for_world_slices(p.batch, [&](int b0, int nb) {
+        const dim3 g((unsigned)((p.height * p.width + 255) / 256), (unsigned)nb);
+        const size_t w = (size_t)b0 * p.height * p.width;
+        hipLaunchKernelGGL(tie_audit, g, dim3(256), 0, h->stream, h->L16[h->cur].get() + w, h->D16[h->cur].get() + w, p.height,
+                           p.width, derive_f32(p, L), make_f64(p, L), d, pl.sym_albedo && pl.kind == STEP_STREAM ? 1 : 0);
+    });
     HIPCHK(hipGetLastError());
     unsigned long long r[4];
     HIPCHK(hipMemcpyAsync(r, d, sizeof(r), hipMemcpyDeviceToHost, h->stream));
