@@ -623,6 +623,40 @@ int dw_run_episode_ensemble_trace(dw_handle* h, int32_t nsteps,
                                   dw_world_stats* trace /* [K][B], may be NULL */,
                                   dw_temp_stats* temps  /* [K][B], may be NULL */);
 
+/* dw_run_episode_mlp that also records, for every step and world, what dw_reduce would report after that step and, on
+ * demand, the statistics of the temperature field that step computes: the curves of the reference's trained-agent demo
+ * (daisy/notebook_helpers.py:210-223 `update_fig_agent`, the existential-risk notebook's MLP cells: env.grid[:,1].mean(),
+ * env.grid[:,2].mean(), temp.mean() and temp.std() appended after every env.step(action) while a trained MLP,
+ * agents/mlp.py:97-116, grazes) without one host round trip per step.
+ * Contract: everything dw_run_episode_mlp leaves for the same arguments - reward, done, the planes, the retained previous
+ * state, the agents, dw_reduce, the device action buffer, dw_last_fixup_count, the parameter sets kept on the device for
+ * a later params == NULL, the handle's shared-L marks - this call leaves too, bit for bit, in DW_PRECISION_EXACT and
+ * DW_PRECISION_FAST.
+ *   trace[t*B + b]  {max_k, sum_light_k, sum_dark_k} of world b after step t: the record dw_reduce returns after t + 1
+ *                   single steps, reserved = 0.  The last row equals dw_reduce after the call.
+ *   temps[t*B + b]  the dw_temp_stats of the field `self.temp` (ref daisy_world_rl.py:410,415) of world b in step t: after
+ *                   that step's update_agents and before its growth, at L_schedule[t].  float64 in both precisions,
+ *                   reduced in dw_reduce_temperature's order: the last row equals dw_reduce_temperature(h,
+ *                   L_schedule[K-1], .) after the call, both forms below return the same bytes, and a world without cover
+ *                   has std == 0.0 and min == max == mean.
+ * At least one of trace and temps is required (rewards only: dw_run_episode_mlp); a call without temps evaluates no
+ * float64 temperature field.
+ * The forms (dw_kernel_info: "; mlp trace: one wave per world" / "launches per step").  H*W <= 256 with at most 4 agents,
+ * once the current and the retained previous state are quantised: one wave per world (episode_mlp_wave_trace_pw,
+ * csrc/dw_episode_mlp_wave_trace_pw.hpp: episode_mlp_wave's step with episode_wave_stats_pw's and episode_wave_temp_pw's
+ * records).  Every other case - the workgroup shapes, larger worlds, DW_NO_EPISODE_WAVE, DW_NO_EPISODE_KERNEL, the first
+ * steps of an episode - launches per step: observe, policy_mlp, grazing, with temps the on-demand temperature reduction
+ * (on an un-quantised state in its own format), the step kernel, the record row.  There is no LDS workgroup kernel with
+ * records: the price dw_run_episode_trace states.  A call that starts per step and continues in the wave kernel writes one
+ * continuous set of rows.
+ * Checked before anything is launched or allocated (the state is untouched): the rules of dw_run_episode_mlp, and
+ * DW_EINVAL when trace and temps are both null.  DW_ENOMEM keeps nothing.  Synchronises. */
+int dw_run_episode_mlp_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params /* [n_members][1808] */,
+                             int32_t n_members, const int32_t* member_a /* [B] */, const int32_t* member_b /* [B] */,
+                             int32_t split, double L_init, double* reward /* [K][B][N], may be NULL */,
+                             uint8_t* done /* [K][B][N], may be NULL */, dw_world_stats* trace /* [K][B], may be NULL */,
+                             dw_temp_stats* temps /* [K][B], may be NULL */);
+
 /* ---- plumbing ------------------------------------------------------------------------------- */
 
 /* Use an existing HIP stream (e.g. torch's current stream) instead of the handle's own. */
@@ -641,7 +675,7 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark);
  * writes a NUL-terminated description into buf.  Appended fragments name the forms of the other entry points:
  * "; trace: ...", "; per-world L: ...", "; ensemble episode: ..." (dw_run_episode_ensemble), "; episode trace: ..."
  * (dw_run_episode_trace), "; episode temperature: ..." (dw_run_episode_trace_temperature), "; ensemble trace: ..."
- * (dw_run_episode_ensemble_trace) and
+ * (dw_run_episode_ensemble_trace), "; mlp trace: ..." (dw_run_episode_mlp_trace) and
  * "; episode: F; mlp episode: F" - the form dw_run_episode and
  * dw_run_episode_mlp take for the handle's shape, agent count, precision, collision mode and switches, F one of
  * "one wave per world" (H*W <= 256 and at most 64 agents, MLP: at most 4), "workgroup (LDS)" (H*W <= 4096) and

@@ -1919,10 +1919,15 @@ int dw_policy_mlp_population(dw_handle* h, const double* params, int32_t n_membe
 // K steps with MLP policies without a host round trip: parameters and member maps go to the device once;
 // per step: observe (all agents) -> policy_mlp for [0, split) and [split, N) -> update_agents -> step ->
 // reward / done of the step into the [K][B][N] device buffers; one download and synchronisation at the end.
-int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params, int32_t n_members,
-                       const int32_t* member_a, const int32_t* member_b, int32_t split, double L_init, double* reward,
-                       uint8_t* done) {
-    NEED(h && L_schedule, DW_EINVAL, "null argument");
+// `trace` / `temps` (dw_run_episode_mlp_trace; either may be null): also the records of every step and the temperature
+// records, [K][B] each, in the TRACE region of the staging buffer.  The one-wave-per-world form takes
+// episode_mlp_wave_trace_pw<EXACT, temps given>; every other form - and the first steps of an episode - launches per step,
+// with temp_moments_pw on the grazed current state (in its own format while it is the un-quantised upload) in front of the
+// step kernel and episode_stats_row_pw behind it: no LDS workgroup kernel, the stated price of the records.
+static int run_episode_mlp_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params, int32_t n_members,
+                                const int32_t* member_a, const int32_t* member_b, int32_t split, double L_init, double* reward,
+                                uint8_t* done, dw_world_stats* trace, dw_temp_stats* temps) {
+    const bool records = trace || temps;
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
     NEED(nsteps >= 1 && nsteps <= 4096, DW_EINVAL, "nsteps must be in 1..4096");
@@ -1942,10 +1947,12 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     NEED(n_members == 1 || (member_a && member_b), DW_EINVAL, "several parameter sets need both member maps");
     const size_t wbytes = sizeof(double) * 1808 * (size_t)n_members;
     EpisodeRegions regions;
-    regions.rows = K; regions.mlp = true;
+    regions.rows = K; regions.mlp = true; regions.trace = records; regions.temps = temps != nullptr;
     const EpisodeStaging S(K, (size_t)B, (size_t)N, regions);
     using R = EpisodeStaging;
     const size_t o_ma = S.off[R::MEMBER_A], o_mb = S.off[R::MEMBER_B], o_p32 = S.off[R::P32], o_ls = S.off[R::LS];
+    if (temps)                                                  // the partials of temp_moments_pw (the rows live in the staging buffer)
+        if (int rc = alloc_group(h, "the temperature reduction", {{h->temp_part, temp_part_bytes(h)}})) return rc;
     if (int erc = ensure_ep_buf(h, S.total)) return erc;
     if (params) {                                               // the sets stay on the device for later calls (params == NULL)
         if (h->mlp_members != n_members) {
@@ -1960,6 +1967,8 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     const int* d_mb = member_b ? reinterpret_cast<const int*>(h->ep_buf.get() + o_mb) : nullptr;
     double* d_r = S.at<double>(h->ep_buf.get(), R::REWARD);
     unsigned char* d_d = S.at<unsigned char>(h->ep_buf.get(), R::DONE);
+    StatsDev* const d_rows = S.at<StatsDev>(h->ep_buf.get(), R::TRACE);
+    TempStatsDev* const d_trows = reinterpret_cast<TempStatsDev*>(h->ep_buf.get() + S.temps_off());
     SyncOnExit guard(h->stream);                              // params / member maps are the caller's
     if (params) HIPCHK(hipMemcpyAsync(h->mlp_w.get(), params, wbytes, hipMemcpyHostToDevice, h->stream));
     if (member_a) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ma, member_a, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
@@ -1971,7 +1980,8 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
     const int wpb = worlds_per_block(Cc);
     size_t lds = 0;
     const EpisodeForm form = episode_mlp_form(h, &lds);
-    const bool wave_kernel = form == EPISODE_WAVE, small = form != EPISODE_STEPWISE;
+    const bool wave_kernel = form == EPISODE_WAVE, small = records ? form == EPISODE_WAVE : form != EPISODE_STEPWISE;
+    if (records) lds = episode_mlp_wave_trace_lds_bytes(Cc, N);
     std::vector<PhysF32> p32;
     SyncOnExit guard2(h->stream);                             // p32 (filled below) must outlive its upload
     size_t t = 0;
@@ -1991,7 +2001,15 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
             io.reward = d_r + t * bn; io.done = d_d + t * bn;
             io.action = h->action.get();
             const bool ex = p.precision == DW_PRECISION_EXACT;
-            if (wave_kernel) {
+            if (records) {
+                auto kern = temps ? (ex ? episode_mlp_wave_trace_pw<true, true> : episode_mlp_wave_trace_pw<false, true>)
+                                  : (ex ? episode_mlp_wave_trace_pw<true, false> : episode_mlp_wave_trace_pw<false, false>);
+                if (int rc = set_lds_limit(h, kern, lds)) return rc;
+                const EpisodeMlpWaveTraceArgs A{io, d_rows + t * B, temps ? d_trows + t * B : nullptr, B, N, p.height, p.width,
+                                                (int)Kr, p.obs_mask, (int)split, p.agent_gamma, h->L_last,
+                                                make_f64(p, L_schedule[t])};
+                hipLaunchKernelGGL(kern, dim3((unsigned)((B + 3) / 4)), dim3(256), lds, h->stream, A);
+            } else if (wave_kernel) {
                 auto kern = ex ? episode_mlp_wave<true> : episode_mlp_wave<false>;
                 if (int rc = set_lds_limit(h, kern, lds)) return rc;
                 const EpisodeMlpWaveArgs A{io, B, N, p.height, p.width, (int)Kr, p.obs_mask, (int)split, p.agent_gamma,
@@ -2020,16 +2038,50 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
         HIPCHK(hipGetLastError());
         rc = launch_agents(h, h->action.get(), B, N, false, d_r + t * bn, d_d + t * bn);
         if (rc) return rc;
+        if (temps) {                                            // the field this step computes: after its grazing, at its luminosity
+            rc = launch_temp_moments(h, /*current=*/true, L_schedule[t], nullptr, d_trows + t * B);
+            if (rc) return rc;
+        }
         rc = launch_forward(h, L_schedule[t]);
         if (rc) return rc;
+        if (trace) {
+            hipLaunchKernelGGL(episode_stats_row_pw, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream,
+                               h->stats2[h->sp].get(), B, d_rows + t * B);
+            HIPCHK(hipGetLastError());
+        }
         ++t;
     }
     if (reward) HIPCHK(hipMemcpyAsync(reward, d_r, sizeof(double) * K * bn, hipMemcpyDeviceToHost, h->stream));
     if (done) HIPCHK(hipMemcpyAsync(done, d_d, K * bn, hipMemcpyDeviceToHost, h->stream));
+    if (trace) HIPCHK(hipMemcpyAsync(trace, d_rows, S.stats_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (temps) HIPCHK(hipMemcpyAsync(temps, d_trows, S.temps_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     guard2.disarm();
     guard.disarm();
     return DW_OK;
+}
+
+int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params, int32_t n_members,
+                       const int32_t* member_a, const int32_t* member_b, int32_t split, double L_init, double* reward,
+                       uint8_t* done) {
+    NEED(h && L_schedule, DW_EINVAL, "null argument");
+    return run_episode_mlp_impl(h, nsteps, L_schedule, params, n_members, member_a, member_b, split, L_init, reward, done, nullptr,
+                                nullptr);
+}
+
+// ---- dw_run_episode_mlp_trace: dw_run_episode_mlp with the records of every step -----------------------------------------
+// The form the call takes: one wave per world (episode_mlp_wave_trace_pw) wherever dw_run_episode_mlp takes episode_mlp_wave;
+// every other shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step.  Both reduce the temperature field in
+// temp_moments_pw's order: the same bytes.
+int dw_run_episode_mlp_trace(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params, int32_t n_members,
+                             const int32_t* member_a, const int32_t* member_b, int32_t split, double L_init, double* reward,
+                             uint8_t* done, dw_world_stats* trace, dw_temp_stats* temps) {
+    NEED(h && L_schedule, DW_EINVAL, "null argument");
+    NEED(trace || temps, DW_EINVAL, "dw_run_episode_mlp_trace needs a trace or a temps array (rewards only: dw_run_episode_mlp)");
+    static_assert(sizeof(dw_temp_stats) == sizeof(TempStatsDev) && sizeof(TempStatsDev) == EpisodeStaging::kTempRow, "temperature record layout");
+    static_assert(sizeof(dw_world_stats) == sizeof(StatsDev), "record layout");
+    return run_episode_mlp_impl(h, nsteps, L_schedule, params, n_members, member_a, member_b, split, L_init, reward, done, trace,
+                                temps);
 }
 
 int dw_lifespan_reset(dw_handle* h) {
@@ -2719,6 +2771,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_run_episode_ensemble_trace takes
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, "; ensemble trace: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
+    }
+    {                                                           // the form dw_run_episode_mlp_trace takes
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; mlp trace: %s", episode_mlp_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

@@ -501,7 +501,7 @@ class Engine:
         return alive.view(np.bool_), ok.view(np.bool_)
 
     def run_episode_mlp(self, L_schedule, params, member_a=None, member_b=None, split=None, L_init=0.75,
-                        reuse_buffers=False, n_members=None):
+                        reuse_buffers=False, n_members=None, trace=False, temperature=False):
         """K device-resident steps with MLP policies: agents [0, split) of world b use parameter set
         member_a[b], agents [split, N) member_b[b].  Returns (reward (K,B,N,1) float64, done (K,B,N,1) bool)
         exactly as K calls of env.step would (ref step :486-492).
@@ -510,7 +510,13 @@ class Engine:
         (pass `n_members`).  `reuse_buffers=True`: the returned arrays are views of page-locked buffers owned by this
         engine (no staging copy on the way back) and are OVERWRITTEN by the next call with reuse_buffers=True - for
         harnesses that consume a chunk's rewards before they run the next one.  `reuse_buffers=1` selects a SECOND such
-        buffer (True is buffer 0): a harness that runs chunk c + 1 while it still reads chunk c's rewards alternates."""
+        buffer (True is buffer 0): a harness that runs chunk c + 1 while it still reads chunk c's rewards alternates.
+
+        `trace=True` and / or `temperature=True` (`dw_run_episode_mlp_trace`): returns (reward, done, stats, temps) -
+        `stats` (K, B) of dtype `_ffi.STATS_DTYPE`, what `reduce()` would return after every step (`reserved` 0), `temps`
+        (K, B) of dtype `_ffi.TEMP_STATS_DTYPE`, the statistics of the temperature field step t computes (after its grazing,
+        before its growth, at `L_schedule[t]`; float64 in every precision); the one not asked for is None and costs nothing.
+        Rewards, done flags, state and agents are unchanged by either."""
         Ls = np.ascontiguousarray(L_schedule, dtype=np.float64)
         K = Ls.shape[0]
         if params is None:
@@ -534,6 +540,15 @@ class Engine:
         else:
             reward = np.empty((K, self.B, self.N, 1))              # (every element is written by the library; done: 0 / 1)
             done = np.empty((K, self.B, self.N, 1), dtype=np.uint8)
+        if trace or temperature:
+            stats = np.zeros((K, self.B), dtype=_ffi.STATS_DTYPE) if trace else None
+            temps = np.zeros((K, self.B), dtype=_ffi.TEMP_STATS_DTYPE) if temperature else None
+            self._check(self._lib.dw_run_episode_mlp_trace(
+                self._h, K, _ffi.ptr_d(Ls), _ffi.ptr_d(w), nm, _ffi.ptr_i(ma), _ffi.ptr_i(mb), split, float(L_init),
+                _ffi.ptr_d(reward), _ffi.ptr_u8(done),
+                None if stats is None else stats.ctypes.data_as(C.POINTER(DwWorldStats)),
+                None if temps is None else temps.ctypes.data_as(C.POINTER(DwTempStats))))
+            return reward, done.view(np.bool_), stats, temps
         self._check(self._lib.dw_run_episode_mlp(self._h, K, _ffi.ptr_d(Ls), _ffi.ptr_d(w), nm, _ffi.ptr_i(ma),
                                            _ffi.ptr_i(mb), split, float(L_init), _ffi.ptr_d(reward), _ffi.ptr_u8(done)))
         return reward, done.view(np.bool_)

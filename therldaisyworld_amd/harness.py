@@ -745,6 +745,72 @@ def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_c
         pool.shutdown(wait=True)
 
 
+def simulate_grazing_mlp(env, agent, nsteps, adversary=None, chunk=64, obs=None, temperature=False):
+    """The `simulate_grazing` of LEARNED policies: the time series of the daisy populations over the next `nsteps` steps
+    while MLP policies graze - the curves of the reference's trained-agent demo (daisy/notebook_helpers.py:210-223
+    `update_fig_agent`, the existential-risk notebook's MLP cells append `env.grid[:, 1].mean()`, `env.grid[:, 2].mean()`,
+    `temp.mean()` and `temp.std()` after every `env.step(action)`) - without a host round trip per step: observations, the
+    MLP forward pass, grazing, physics and the per-step, per-world reductions stay on the device for `chunk` steps at a
+    time (`dw_run_episode_mlp_trace`).  `agent` drives agents [0, N // 2) of every world and `adversary` the rest, as in
+    `get_fitness`; `adversary=None`: `agent` drives them all.  `obs=None`: reset the environment first.
+
+    The parameter sets go up with the first chunk and stay on the device.  There is no stopping rule: exactly `nsteps`
+    steps are taken.  Returns the dict of `simulate_grazing` - `L`, `mean_light`, `mean_dark`, `max_cover`, `alive`,
+    `stats`, `agent_ok` (n, B, N) bool (not done: reward >= 0.1 after the step) and `agents_alive` (n, B) - plus `reward`
+    (n, B, N) float64, the step's `reward * (reward > 0)`; `temperature=True` adds `mean_temp`, `std_temp`, `min_temp`,
+    `max_temp` (n, B) in kelvin and `dead_temp` (n,).  Afterwards `env.grid`, `env.step()`, `env.L`, `env.step_count`
+    continue as if `nsteps` calls of `env.step(action)` had been made.
+
+    Precision "f64" and `collision_mode == 1` have no device-resident form: ValueError - `simulate_grazing` with a
+    callable agent is the host-loop route."""
+    n = int(nsteps)
+    if n < 1:
+        raise ValueError("nsteps must be at least 1")
+    K = int(chunk)
+    if K < 1:
+        raise ValueError("chunk must be at least 1")
+    if env.precision == "f64" or env.collision_mode == 1:
+        raise ValueError('simulate_grazing_mlp runs device-resident in precision "exact" or "fast" with collision_mode 0; '
+                         "simulate_grazing with a callable agent is the host-loop route")
+    if obs is None:
+        env.reset()
+    B, N = int(env.batch_size), int(env.n_agents)
+    if adversary is None:
+        params, split = np.asarray(agent.get_parameters(), dtype=np.float64).reshape(1, 1808), N
+        member_a = member_b = None
+    else:
+        params, split = np.stack([agent.get_parameters(), adversary.get_parameters()]), N // 2
+        member_a, member_b = np.zeros(B, dtype=np.int32), np.ones(B, dtype=np.int32)
+    eng = env._ensure_engine()
+    env._sync_to_device()
+    L = np.zeros(n, dtype=np.float64)
+    stats = np.zeros((n, B), dtype=_ffi.STATS_DTYPE)
+    ok = np.zeros((n, B, N), dtype=bool)
+    reward = np.zeros((n, B, N), dtype=np.float64)
+    temps = np.zeros((n, B), dtype=_ffi.TEMP_STATS_DTYPE) if temperature else None
+    t = 0
+    while t < n:
+        k = min(K, n - t)
+        Ls = np.asarray(_luminosity_schedule(env, k), dtype=np.float64)
+        L[t:t + k] = Ls
+        # the parameter sets go up with the first chunk and stay on the device; the first steps of an episode (an
+        # un-quantised state) are taken inside the call, launches per step
+        r, d, st, tp = eng.run_episode_mlp(Ls, params if t == 0 else None, member_a, member_b, split, env._L_pass,
+                                           n_members=params.shape[0], trace=True, temperature=bool(temperature))
+        reward[t:t + k] = r[..., 0]
+        ok[t:t + k] = ~d[..., 0]
+        stats[t:t + k] = st
+        if temperature:
+            temps[t:t + k] = tp
+        _advance_host_scalars(env, k)
+        t += k
+    out = _series_dict(env, L, stats, temps)
+    out["agent_ok"] = ok
+    out["agents_alive"] = ok.sum(axis=2)
+    out["reward"] = reward
+    return out
+
+
 def _fitness_chunk(acc, rewards, dones, half):
     """Bookkeeping of `get_fitness` for one chunk of K steps (rewards (K,B,N,1) = reward * (reward > 0), dones
     (K,B,N,1) bool), equal to the reference's per-step statements (daisy/evo/sges.py:160-176: all_done,
