@@ -302,6 +302,57 @@ int dw_step_n_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_sc
                                 dw_world_stats* trace /* [nsteps][B], may be NULL */,
                                 dw_temp_stats* temps  /* [nsteps][B] */);
 
+/* Spatial frames: the image panels of the reference's figure (daisy/notebook_helpers.py plot_grid / update_fig:
+ * tensor_to_image(env.grid[:, :3]) and tensor_to_image(env.temp)) without moving the planes.  A frame holds, per tile of
+ * tile_h x tile_w cells of each selected world, the exact integer sums of the light and dark per-mille cover and the
+ * float64 mean of the local temperature (kelvin).  TH = H / tile_h, TW = W / tile_w tiles per world, row-major; at 1 x 1
+ * tiles a frame is env.grid[:, 1], env.grid[:, 2] (times 1000) and env.temp themselves. */
+typedef struct dw_tile_cover { uint32_t sum_light_k, sum_dark_k; } dw_tile_cover;   /* 8 bytes, per-mille integers */
+typedef struct dw_frame_spec {
+    int32_t tile_h, tile_w;        /* must divide H and W; tile_h * tile_w <= 1 048 576 (the sums fit 32 bits) */
+    int32_t n_worlds;              /* S: number of selected worlds; 0 with worlds == NULL: all B, in order */
+    const int32_t* worlds;         /* [S] distinct world indices in 0..B-1, any order */
+} dw_frame_spec;
+
+/* One frame of the handle's state, on demand (also the way to frames of a per-step loop WITH agents: one call after each
+ * dw_step / dw_env_step).
+ *   cover      the tile sums of the CURRENT state, which must be quantised: DW_ESTATE ("the current state is not quantised
+ *              yet; take the first step with dw_step") before the first step after an un-quantised upload.
+ *   temp_mean  the tile means of the field dw_reduce_temperature(h, L, .) reduces - the same source state (after a step the
+ *              retained previous state, in its own format while that is the un-quantised upload), the same rule for L,
+ *              DW_ESTATE in the same cases.  Every cell's temperature is the double dw_download_caches returns in
+ *              temps[:, 0]: float64 in all three precisions.  The sum of a tile is taken in a fixed order that depends on
+ *              (tile_h, tile_w) only - not on B, the selection or the entry point; no atomics: world b's bytes are the
+ *              same alone and in any ensemble, and a 1 x 1 tile is the cell's double itself.
+ * At least one of the two is required.  Only the selected worlds are evaluated.  Synchronises.
+ * DW_EINVAL (checked before anything is launched or allocated): a null handle or spec, both outputs null, a tile that does
+ * not divide the grid or has more than 2^20 cells, n_worlds < 0, n_worlds > 0 with null worlds, a world index out of range
+ * or listed twice, a luminosity that is not finite or is negative; DW_ESTATE: no state (and the cases above);
+ * DW_ENOMEM: the frame buffers could not be allocated (nothing is kept). */
+int dw_reduce_tiles(dw_handle* h, double L, const dw_frame_spec* spec,
+                    dw_tile_cover* cover /* [S][TH][TW], may be NULL */, double* temp_mean /* [S][TH][TW], may be NULL */);
+
+/* dw_step_n_trace with frames: nsteps agent-free steps at L_schedule[t] (no agent update is made, with or without agents on
+ * the handle), and a frame at every stride-th step: F = nsteps / stride frames, frame f belongs to step
+ * t_f = (f + 1) * stride - 1.  Steps after the last whole stride are taken and recorded in `trace`, but have no frame.
+ *   cover[f]      the tile sums of the state AFTER step t_f: the tiles of a world sum to trace[t_f]'s sums.
+ *   temp_mean[f]  the tile means of the field step t_f COMPUTES - the state before it at L_schedule[t_f], the row convention
+ *                 of dw_step_n_trace_temperature: what env.temp holds after t_f + 1 calls of env.step().  The bytes are
+ *                 those dw_reduce_tiles returns for that state.
+ * Planes, retained previous state, dw_reduce, dw_last_fixup_count and `trace` afterwards are those of dw_step_n_trace with
+ * the same schedule, bit for bit, in all three precisions, from a quantised or an un-quantised state.  A frame step is a
+ * single launch (its input and its output planes are in HBM around it); the steps between two frames pair where
+ * dw_step_n_trace would pair a run of their number.  Frames wait on the device and are downloaded once per 32 MiB of frame
+ * records (a larger frame on its own); there is no other host synchronisation between the steps.  A call without temp_mean
+ * evaluates no float64 field.  nsteps == 0 is a no-op.  Synchronises.
+ * DW_EINVAL (before anything is launched or allocated; the state is untouched): dw_reduce_tiles' cases, a null L_schedule,
+ * stride < 1, nsteps < 0; DW_ESTATE: no state; DW_ENOMEM: a buffer could not be allocated (nothing is kept).
+ * Out of scope: per-world luminosities or constants, and frames inside the episode loops (dw_run_episode*) - there, call
+ * dw_reduce_tiles between the calls. */
+int dw_step_n_frames(dw_handle* h, int32_t nsteps, const double* L_schedule /* [nsteps] */, const dw_frame_spec* spec,
+                     int32_t stride, dw_tile_cover* cover /* [F][S][TH][TW], may be NULL */,
+                     double* temp_mean /* [F][S][TH][TW], may be NULL */, dw_world_stats* trace /* [nsteps][B], may be NULL */);
+
 /* Per-world physics constants: the members of dw_params a world of an ensemble call may have of its own (ref
  * daisy_world_rl.py:32-52, :65-69) - a sweep over q2, gamma, the albedos, temp_optimal or dt as ONE traced run instead of
  * one handle and one run per value (the reference's run_q2_sims runs its ramp three times with env.q2 = 0, q/64, q/8). */

@@ -54,6 +54,17 @@ class DwTempStats(C.Structure):
 
 TEMP_STATS_DTYPE = np.dtype([("mean", "<f8"), ("std", "<f8"), ("min", "<f8"), ("max", "<f8")])
 
+class DwTileCover(C.Structure):
+    _fields_ = [("sum_light_k", C.c_uint32), ("sum_dark_k", C.c_uint32)]
+
+
+TILE_COVER_DTYPE = np.dtype([("sum_light_k", "<u4"), ("sum_dark_k", "<u4")])
+
+
+class DwFrameSpec(C.Structure):
+    _fields_ = [("tile_h", C.c_int32), ("tile_w", C.c_int32), ("n_worlds", C.c_int32), ("worlds", C.POINTER(C.c_int32))]
+
+
 WORLD_PARAM_NAMES = ("p", "g", "S", "sigma", "gamma", "q", "q2", "dt", "albedo_bare", "albedo_light", "albedo_dark",
                      "temp_optimal")
 
@@ -97,6 +108,9 @@ SIGNATURES = {
     "dw_step_n_trace_per_world": (C.c_int, [_vp, _i32, _pd, C.POINTER(DwWorldStats)]),
     "dw_reduce_temperature": (C.c_int, [_vp, _dbl, C.POINTER(DwTempStats)]),
     "dw_step_n_trace_temperature": (C.c_int, [_vp, _i32, _pd, C.c_int, C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
+    "dw_reduce_tiles": (C.c_int, [_vp, _dbl, C.POINTER(DwFrameSpec), C.POINTER(DwTileCover), _pd]),
+    "dw_step_n_frames": (C.c_int, [_vp, _i32, _pd, C.POINTER(DwFrameSpec), _i32, C.POINTER(DwTileCover), _pd,
+                                   C.POINTER(DwWorldStats)]),
     "dw_world_params_of": (C.c_int, [_vp, C.POINTER(DwWorldParams)]),
     "dw_step_n_trace_ensemble": (C.c_int, [_vp, _i32, C.POINTER(DwWorldParams), _pd, C.POINTER(DwWorldStats),
                                            C.POINTER(DwTempStats)]),

@@ -140,6 +140,12 @@ struct dw_handle {
     // the reduction in flight (one group: allocated all or nothing)
     DevBuf<TempStatsDev> temp_d;
     DevBuf<TempPartial> temp_part;
+    // dw_reduce_tiles / dw_step_n_frames: the selected worlds [S], the frames that wait for their download (cover records
+    // and temperature means, [frames][S][TH][TW] each) and the [S][TH*TW][chunks] partials of large tiles (one group)
+    DevBuf<int> frame_sel;
+    DevBuf<TileCoverDev> frame_cover;
+    DevBuf<double> frame_temp;
+    DevBuf<double> tile_part;
     // dw_step_n_trace_per_world: the constants of a chunk of steps, one entry per step and world (PwLayout), and their
     // page-locked host image
     DevBuf<unsigned char> pw_tab;
@@ -748,6 +754,142 @@ static int launch_temp_moments(dw_handle* h, bool current, double L, const PhysF
     HIPCHK(hipGetLastError());
     return DW_OK;
 }
+
+// ---- spatial frames (dw_reduce_tiles, dw_step_n_frames) --------------------------------------------------------------
+// A checked dw_frame_spec: the tile geometry, the selection (`listed`: frame_sel holds it; otherwise world s is s), which
+// mapping reduces a tile's temperatures (a function of the tile's cells alone, dw_tile_maps.hpp) and the sizes.
+struct FrameShape {
+    TileGeom G{};
+    int S = 0;
+    bool listed = false;
+    const int32_t* worlds = nullptr;  // the caller's list (uploaded by upload_selection)
+    size_t tiles = 0;                 // per world
+    int map = 0;
+    bool vec8 = false;                // tile_cover_pw<8> applies
+    size_t records() const { return (size_t)S * tiles; }                        // of one frame, each of 8 bytes
+    size_t part_bytes() const { return G.chunks > 1 ? sizeof(double) * records() * (size_t)G.chunks : 0; }
+    size_t sel_bytes() const { return listed ? sizeof(int) * (size_t)S : 0; }
+};
+
+static int check_frame_spec(const dw_handle* h, const dw_frame_spec* spec, FrameShape* out) {
+    const dw_params& p = h->prm;
+    NEED(spec->tile_h >= 1 && spec->tile_w >= 1 && p.height % spec->tile_h == 0 && p.width % spec->tile_w == 0, DW_EINVAL,
+         "a %d x %d tile does not divide the %d x %d grid", spec->tile_h, spec->tile_w, p.height, p.width);
+    const long long n = (long long)spec->tile_h * spec->tile_w;
+    NEED(n <= (1LL << 20), DW_EINVAL, "a %d x %d tile has more than 1 048 576 cells (its per-mille sums would not fit 32 bits)",
+         spec->tile_h, spec->tile_w);
+    NEED(spec->n_worlds >= 0, DW_EINVAL, "n_worlds < 0");
+    NEED(spec->n_worlds == 0 || spec->worlds, DW_EINVAL, "n_worlds > 0 with a null list of worlds");
+    std::vector<unsigned char> seen(spec->n_worlds ? (size_t)p.batch : 0, 0);
+    for (int32_t i = 0; i < spec->n_worlds; ++i) {
+        const int32_t b = spec->worlds[i];
+        NEED(b >= 0 && b < p.batch, DW_EINVAL, "worlds[%d] = %d is not a world of this handle (0..%d)", i, b, p.batch - 1);
+        NEED(!seen[(size_t)b], DW_EINVAL, "worlds[%d] = %d is listed twice", i, b);
+        seen[(size_t)b] = 1;
+    }
+    FrameShape s;
+    TileGeom& G = s.G;
+    G.H = p.height, G.W = p.width, G.th = spec->tile_h, G.tw = spec->tile_w, G.TH = G.H / G.th, G.TW = G.W / G.tw;
+    for (G.rpt = G.th < 16 ? G.th : 16; G.th % G.rpt; --G.rpt) {}
+    s.map = n <= kTileThreadCells ? 0 : (n <= kTileWaveCells ? 1 : 2);
+    G.chunks = s.map == 2 ? (int)((n + kTileChunk - 1) / kTileChunk) : 1;
+    s.listed = spec->n_worlds > 0;
+    s.worlds = spec->worlds;
+    s.S = s.listed ? spec->n_worlds : p.batch;
+    s.tiles = (size_t)G.TH * G.TW;
+    s.vec8 = G.W % 8 == 0 && (G.tw % 8 == 0 || 8 % G.tw == 0);
+    *out = s;
+    return DW_OK;
+}
+static int check_luminosity(double L, long long t) {
+    NEED(std::isfinite(L) && L >= 0.0, DW_EINVAL, "L[step %lld] = %g: a luminosity is finite and not negative", t, L);
+    return DW_OK;
+}
+
+static int upload_selection(dw_handle* h, const FrameShape& s) {
+    if (s.listed) HIPCHK(hipMemcpyAsync(h->frame_sel.get(), s.worlds, s.sel_bytes(), hipMemcpyHostToDevice, h->stream));
+    return DW_OK;
+}
+
+// the tile sums of the binary16 planes of buffer `buf` into rec[S][TH][TW]
+static int launch_tile_cover(dw_handle* h, const FrameShape& s, int buf, TileCoverDev* rec) {
+    const TileGeom& G = s.G;
+    const int* sel = s.listed ? h->frame_sel.get() : nullptr;
+    HIPCHK(hipMemsetAsync(rec, 0, sizeof(TileCoverDev) * s.records(), h->stream));   // (the kernel adds: integers, any order)
+    with_bool(s.vec8, [&](auto V8) {
+        constexpr int VEC = V8 ? 8 : 1;
+        const unsigned gx = (unsigned)(((long long)(G.H / G.rpt) * (G.W / VEC) + 255) / 256);
+        for_world_slices(s.S, [&](int s0, int ns) {
+            hipLaunchKernelGGL((tile_cover_pw<VEC>), dim3(gx, (unsigned)ns), dim3(256), 0, h->stream, h->L16[buf].get(),
+                               h->D16[buf].get(), G, sel, s0, rec);
+        });
+    });
+    HIPCHK(hipGetLastError());
+    return DW_OK;
+}
+
+// The tile means of the temperature field a step at luminosity L computes from the CURRENT state (`current`: the frame
+// steps, in front of the step) or of the field the caches hold (the state with_derived_from names), into mean[S][TH][TW]
+static int launch_tile_temp(dw_handle* h, bool current, double L, const FrameShape& s, double* mean) {
+    const TileGeom& G = s.G;
+    const PhysF64 P = make_f64(h->prm, L);
+    const int* sel = s.listed ? h->frame_sel.get() : nullptr;
+    double* part = h->tile_part.get();
+    const unsigned gx = s.map == 0 ? (unsigned)((s.tiles + 255) / 256) : (s.map == 1 ? (unsigned)((s.tiles + 3) / 4)
+                                                                                      : (unsigned)(s.tiles * (size_t)G.chunks));
+    auto reduce = [&](auto* iL, auto* iD) {
+        with_int<0, 1, 2>(s.map, [&](auto MAP) {
+            for_world_slices(s.S, [&](int s0, int ns) {
+                hipLaunchKernelGGL((tile_temp_pw<elem_t<decltype(iL)>, MAP>), dim3(gx, (unsigned)ns), dim3(256), 0, h->stream, iL,
+                                   iD, G, P, sel, s0, mean, part);
+            });
+        });
+    };
+    if (current) with_planes(h, h->unq == OWN_CUR, h->cur, reduce);
+    else with_derived_from(h, [&](auto* iL, auto* iD, auto) { reduce(iL, iD); });
+    HIPCHK(hipGetLastError());
+    if (G.chunks > 1) {
+        hipLaunchKernelGGL(tile_temp_finish_pw, dim3((unsigned)((s.records() + 255) / 256)), dim3(256), 0, h->stream, part,
+                           s.records(), G.chunks, (double)G.th * (double)G.tw, mean);
+        HIPCHK(hipGetLastError());
+    }
+    return DW_OK;
+}
+
+// The frames of one dw_step_n_frames call: they wait in a ring of `cap` frames on the device (32 MiB of records, at least
+// one frame) and come down when it is full and at the end of the run.
+struct FrameRun {
+    dw_handle* h;
+    FrameShape sh;
+    int stride;
+    dw_tile_cover* cover;             // the caller's arrays [F][S][TH][TW] (either may be null)
+    double* temp;
+    size_t total = 0, cap = 1, done = 0;
+    void plan(size_t nframes) {
+        const size_t bytes = sh.records() * ((cover ? sizeof(TileCoverDev) : 0) + (temp ? sizeof(double) : 0));
+        total = nframes;
+        cap = h->sw.frame_ring >= 1 ? (size_t)h->sw.frame_ring : ((size_t)32 << 20) / bytes;
+        cap = cap < 1 ? 1 : cap;
+        cap = cap > total ? total : cap;                        // (a run without a frame holds none)
+    }
+    size_t cover_bytes() const { return cover ? sizeof(TileCoverDev) * cap * sh.records() : 0; }
+    size_t temp_bytes() const { return temp ? sizeof(double) * cap * sh.records() : 0; }
+    // in front of a frame step: the field it computes, from its input planes
+    int before(double L) {
+        return temp ? launch_tile_temp(h, true, L, sh, h->frame_temp.get() + done % cap * sh.records()) : DW_OK;
+    }
+    // behind it: the cover of the state it left; the ring goes down when it is full or the last frame is in
+    int after() {
+        if (cover)
+            if (int rc = launch_tile_cover(h, sh, h->cur, h->frame_cover.get() + done % cap * sh.records())) return rc;
+        ++done;
+        if (done % cap != 0 && done != total) return DW_OK;
+        const size_t k = (done - 1) % cap + 1, at = (done - k) * sh.records(), n = k * sh.records();
+        if (cover) HIPCHK(hipMemcpyAsync(cover + at, h->frame_cover.get(), sizeof(TileCoverDev) * n, hipMemcpyDeviceToHost, h->stream));
+        if (temp) HIPCHK(hipMemcpyAsync(temp + at, h->frame_temp.get(), sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        return DW_OK;
+    }
+};
 
 // f(MODE, PACK) for the strip layout of the fused kernels: packed worlds in rotating 256-column strips, the others by
 // the plan's mode
@@ -1464,12 +1606,17 @@ struct SeriesRun {
     bool sym, constants;              // (table) what launch_forward_pw takes besides its rows
     size_t B, row_bytes, trow_bytes;
     bool first_pair = true;
+    FrameRun* frames = nullptr;       // dw_step_n_frames: the tile maps around the steps the schedule marks
     // the reductions of every step go to a row of trace_d: a series is wanted, or pair kernels add theirs there
     bool keep_rows() const { return trace || q.even; }
 
     int alloc() {
         const GroupItem<DeviceMem> tr{h->trace_d, keep_rows() ? q.rows * row_bytes : 0}, part{h->temp_part, temp_part_bytes(h)},
             td{h->temp_d, q.rows * trow_bytes};
+        if (frames)
+            return alloc_group(h, "the trace buffer and the frame buffers",
+                               {tr, {h->frame_sel, frames->sh.sel_bytes()}, {h->frame_cover, frames->cover_bytes()},
+                                {h->frame_temp, frames->temp_bytes()}, {h->tile_part, frames->sh.part_bytes()}});
         if (!table) return temps ? alloc_group(h, "the trace buffer and the temperature reduction", {tr, part, td})
                                  : alloc_group(h, "the trace buffer", {tr});
         if (temps) return table->alloc("the per-world constants, the trace buffer and the temperature reduction", {table->item(), tr, part, td});
@@ -1490,10 +1637,13 @@ struct SeriesRun {
         const PhysF64* r64 = table ? table->lay.p64(tab, tr) : nullptr;
         if (temps)
             if (int rc = launch_temp_moments(h, true, table ? 0.0 : Ls[t], r64, h->temp_d.get() + sr * B)) return rc;
+        const bool frame = frames && q.is_frame[(size_t)t];
+        if (frame)
+            if (int rc = frames->before(Ls[t])) return rc;
         if (int rc = table ? launch_forward_pw(h, table->lay.p32(tab, tr), r64, table->lay.fb(tab), sym, constants)
                            : launch_forward(h, Ls[t])) return rc;
         if (row) HIPCHK(hipMemcpyAsync(row, h->stats2[h->sp].get(), row_bytes, hipMemcpyDeviceToDevice, h->stream));
-        return DW_OK;
+        return frame ? frames->after() : DW_OK;
     }
     int run(WorldRows* worlds) {
         const int nsteps = (int)q.is_pair.size();
@@ -1522,7 +1672,8 @@ struct SeriesRun {
 // that the constants were per-world.  `always_even`, `may_pair`: plan_series.
 enum SeriesForm { SHARED_L, PER_WORLD_L, PER_WORLD_CONSTANTS };
 static int run_series(dw_handle* h, int32_t nsteps, const double* L_schedule, dw_world_stats* trace, dw_temp_stats* temps,
-                      bool always_even, bool may_pair, SeriesForm form = SHARED_L, const dw_world_params* worlds = nullptr) {
+                      bool always_even, bool may_pair, SeriesForm form = SHARED_L, const dw_world_params* worlds = nullptr,
+                      FrameRun* frames = nullptr) {
     const bool pw = form != SHARED_L;
     NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
     if (nsteps == 0) return DW_OK;
@@ -1536,12 +1687,16 @@ static int run_series(dw_handle* h, int32_t nsteps, const double* L_schedule, dw
     const bool sym = worlds ? worlds_symmetric(worlds, B) && !h->sw.no_sym : h->plan.sym_albedo;
     HIPCHK(hipSetDevice(p.device));
     const SeriesSchedule q = plan_series(SeriesSpec{nsteps, B, sizeof(StatsDev), sizeof(TempStatsDev), h->sw.trace_rows, always_even,
-                                                    may_pair, cur_quantised(h), temps != nullptr, pw ? L_schedule : nullptr});
+                                                    may_pair, cur_quantised(h), temps != nullptr, pw ? L_schedule : nullptr,
+                                                    frames ? frames->stride : 0, frames && frames->temp});
+    if (frames) frames->plan(q.nframes);
     std::unique_ptr<PwTable> table(pw ? new PwTable(h, PwLayout(B, q.trows, q.prows)) : nullptr);
     SeriesRun run{h, q, L_schedule, trace, temps, table.get(), sym, form == PER_WORLD_CONSTANTS, B, sizeof(StatsDev) * B, sizeof(TempStatsDev) * B};
+    run.frames = frames;
     if (int rc = run.alloc()) return rc;
     SyncOnExit sync(h->stream);                                 // the downloads fill the caller's arrays
     h->fused_launches = 0;
+    if (int rc = frames ? upload_selection(h, frames->sh) : DW_OK) return rc;
     if (int rc = run.run(rows.get())) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     sync.disarm();
@@ -1575,6 +1730,49 @@ int dw_step_n_trace_temperature(dw_handle* h, int32_t nsteps, const double* L_sc
                                 dw_temp_stats* temps) {
     NEED(h && L_schedule && temps, DW_EINVAL, "null argument");
     return run_series(h, nsteps, L_schedule, trace, temps, false, false, per_world ? PER_WORLD_L : SHARED_L);
+}
+
+int dw_reduce_tiles(dw_handle* h, double L, const dw_frame_spec* spec, dw_tile_cover* cover, double* temp_mean) {
+    static_assert(sizeof(dw_tile_cover) == 8 && sizeof(dw_tile_cover) == sizeof(TileCoverDev), "tile record layout");
+    NEED(h && spec, DW_EINVAL, "null argument");
+    NEED(cover || temp_mean, DW_EINVAL, "neither cover nor temp_mean is wanted");
+    FrameShape sh;
+    if (int rc = check_frame_spec(h, spec, &sh)) return rc;
+    if (int rc = check_luminosity(L, 0)) return rc;
+    NEED(h->have_state, DW_ESTATE, "no state");
+    NEED(!cover || cur_quantised(h), DW_ESTATE, "the current state is not quantised yet; take the first step with dw_step");
+    if (temp_mean) NEED_SHARED_CONSTANTS(h, "dw_reduce_tiles");
+    HIPCHK(hipSetDevice(h->prm.device));
+    const size_t n = sh.records();
+    if (int rc = alloc_group(h, "the frame buffers", {{h->frame_sel, sh.sel_bytes()}, {h->frame_cover, cover ? sizeof(TileCoverDev) * n : 0},
+                                                       {h->frame_temp, temp_mean ? sizeof(double) * n : 0},
+                                                       {h->tile_part, temp_mean ? sh.part_bytes() : 0}})) return rc;
+    SyncOnExit sync(h->stream);                                 // the selection comes from the caller's array
+    if (int rc = upload_selection(h, sh)) return rc;
+    if (cover) {
+        if (int rc = launch_tile_cover(h, sh, h->cur, h->frame_cover.get())) return rc;
+        HIPCHK(hipMemcpyAsync(cover, h->frame_cover.get(), sizeof(TileCoverDev) * n, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (temp_mean) {                                            // (the luminosity: run_materialise's rule - the caches' own)
+        if (int rc = launch_tile_temp(h, false, h->stepped && !h->L_per_world ? h->L_last : L, sh, h->frame_temp.get())) return rc;
+        HIPCHK(hipMemcpyAsync(temp_mean, h->frame_temp.get(), sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    sync.disarm();
+    return DW_OK;
+}
+
+int dw_step_n_frames(dw_handle* h, int32_t nsteps, const double* L_schedule, const dw_frame_spec* spec, int32_t stride,
+                     dw_tile_cover* cover, double* temp_mean, dw_world_stats* trace) {
+    NEED(h && L_schedule && spec, DW_EINVAL, "null argument");
+    NEED(cover || temp_mean, DW_EINVAL, "neither cover nor temp_mean is wanted");
+    NEED(stride >= 1, DW_EINVAL, "stride < 1");
+    NEED(nsteps >= 0, DW_EINVAL, "nsteps < 0");
+    FrameRun frames{h, FrameShape{}, stride, cover, temp_mean};
+    if (int rc = check_frame_spec(h, spec, &frames.sh)) return rc;
+    for (int32_t t = 0; t < nsteps; ++t)
+        if (int rc = check_luminosity(L_schedule[t], t)) return rc;
+    return run_series(h, nsteps, L_schedule, trace, nullptr, true, h->plan.trace_pairs, SHARED_L, nullptr, &frames);
 }
 
 int dw_last_step_n_timing(dw_handle* h, float* fused_ms, int32_t* fused_launches, int32_t* plane_elem_bytes) {

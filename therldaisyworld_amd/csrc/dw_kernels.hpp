@@ -23,6 +23,7 @@
 //   dw_agents_fused.hpp   agents_lookahead_patch: the agents' step between the two steps of a fused launch
 //   dw_state_io.hpp       materialise (ref self.grid :445-459 / :304-323), init_random (Philox), conversions
 //   dw_temp_moments.hpp   temp_moments_pw   per-world mean / std / min / max of the local temperature (ref :410,415)
+//   dw_tile_maps.hpp      tile_cover_pw, tile_temp_pw   per-tile cover sums and temperature means of selected worlds (frames)
 //
 // Wavefront = 64 lanes, 256-thread workgroups (4 waves), no MFMA.  Planes are binary16 per-mille integers: 8
 // algorithmic bytes per cell-update (2 planes read + 2 written).  Measured bounds (DESIGN.md sections 3 and 6): the
@@ -48,3 +49,4 @@
 #include "dw_episode_wave_temp_pw.hpp"
 #include "dw_episode_wave_ens_trace_pw.hpp"
 #include "dw_episode_mlp_wave_trace_pw.hpp"
+#include "dw_tile_maps.hpp"

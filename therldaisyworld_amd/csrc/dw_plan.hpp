@@ -29,12 +29,13 @@ namespace dw {
 //                          packed leftover columns (StepPlan::seam_strips): an A/B in one process
 //   DW_TEST_TRACE_ROWS=n   (test hook) dw_step_n_trace holds n rows of the series on the device at a time (rounded down to
 //                          even, at least 2) instead of 32 MiB of them: multi-chunk runs with a handful of worlds
+//   DW_TEST_FRAME_RING=n   (test hook) dw_step_n_frames holds n frames on the device at a time instead of 32 MiB of them
 struct Switches {
     bool no_sym = false, no_pack = false, no_fuse = false, no_ring = false, no_fmt_planes = false, no_seam_strips = false,
          no_episode_kernel = false,
          no_episode_wave = false, no_agent_fuse = false, no_agent_preapply = false, first_f64 = false,
          first_generic = false, force_rescan = false, test_hooks = false;
-    int pack_min_strips = -1, strip_rows = 0, tile_rpt = 0, queue_cap = -1, mismatch_cap = -1, trace_rows = 0;
+    int pack_min_strips = -1, strip_rows = 0, tile_rpt = 0, queue_cap = -1, mismatch_cap = -1, trace_rows = 0, frame_ring = 0;
     double first_slack = -1.0;
     char kernel[16] = {0};           // DW_KERNEL: "tiled" | "stream"
     char text[256] = {0};            // what was set, for dw_kernel_info
@@ -62,6 +63,7 @@ inline Switches read_switches() {
     num("DW_TILE_RPT", w.tile_rpt, false);
     num("DW_TEST_QUEUE_CAP", w.queue_cap, true); num("DW_TEST_MISMATCH_CAP", w.mismatch_cap, true);
     num("DW_TEST_TRACE_ROWS", w.trace_rows, true);
+    num("DW_TEST_FRAME_RING", w.frame_ring, true);
     if (test_hook("DW_TEST_FORCE_RESCAN")) { w.force_rescan = true; note("DW_TEST_FORCE_RESCAN", nullptr); }
     if (const char* e = test_hook("DW_TEST_FIRST_SLACK")) { w.first_slack = std::atof(e); note("DW_TEST_FIRST_SLACK", e); }
     if (const char* e = std::getenv("DW_KERNEL")) { snprintf(w.kernel, sizeof(w.kernel), "%s", e); note("DW_KERNEL", e); }

@@ -111,12 +111,20 @@ struct SeriesSpec {
     bool quantised = true;            // ... from a quantised state: the current one is
     bool temps = false;               // temperature records are wanted (reduced in front of every step: single steps only)
     const double* table_Ls = nullptr; // [nsteps][B]: the steps read their constants from the per-world table
+    // frames (dw_step_n_frames): step t with (t + 1) % frame_stride == 0 leaves a frame - the tile maps of the state after
+    // it and (frame_temps) of the temperature field it computes from the state before it.  < 1: no frames.
+    int frame_stride = 0;
+    bool frame_temps = false;
+    bool is_frame(size_t t) const { return frame_stride >= 1 && (t + 1) % (size_t)frame_stride == 0; }
 };
 
 struct SeriesSchedule {
     size_t rows = 0;                          // rows of the series on the device at a time: step t fills row t % rows
     std::vector<unsigned char> is_pair;       // [nsteps] a step pair starts at t
     size_t npairs = 0;
+    std::vector<unsigned char> is_frame;      // [nsteps] step t leaves a frame (none without SeriesSpec::frame_stride)
+    size_t nframes = 0;
+    bool frame_temps = false;                 // ... with the temperature map, reduced in front of the step
     bool even = false;                        // chunks laid out for pairs: an even number of rows, at least two, zeroed
     // the table (table_Ls): capacity in single-step and pair rows, the row step t (or the pair at t) reads, whether it is
     // the first to read it, and the chunks - the steps before `end` have their rows on the device after its upload
@@ -141,10 +149,16 @@ inline SeriesSchedule plan_series(const SeriesSpec& s) {
     q.rows = rows = clamp(rows, 1, n);
     // A pair where dw_step_n would issue one - from a quantised state (a first single step makes it so), never the closing
     // one or two steps (the retained previous state stays the true predecessor) - with both rows in one chunk of the series
+    // A frame step is a single launch (its input planes and its output planes are in HBM around it), and the steps
+    // between two frames pair as a run of their number would: `end` is the frame step ahead, or the end of the run.
     q.is_pair.assign(n, 0);
+    q.is_frame.assign(n, 0);
+    q.frame_temps = s.frame_stride >= 1 && s.frame_temps;
+    for (size_t t = 0; t < n; ++t) q.nframes += q.is_frame[t] = s.is_frame(t);
     bool quantised = s.quantised;
-    for (size_t t = 0; t < n;) {
-        if (pairs && quantised && n - t >= 3 && t % rows + 2 <= rows) { q.is_pair[t] = 1; ++q.npairs; t += 2; }
+    for (size_t t = 0, end = 0; t < n;) {
+        if (end <= t) for (end = t; end < n && !q.is_frame[end]; ++end) {}
+        if (pairs && quantised && end - t >= 3 && t % rows + 2 <= rows) { q.is_pair[t] = 1; ++q.npairs; t += 2; }
         else { quantised = true; t += 1; }
     }
     if (!s.table_Ls) return q;

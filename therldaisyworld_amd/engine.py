@@ -336,6 +336,54 @@ class Engine:
         self._check(self._lib.dw_reduce_temperature(self._h, float(L), out.ctypes.data_as(C.POINTER(DwTempStats))))
         return out
 
+    # -- spatial frames -----------------------------------------------------------------------
+    def _frame_spec(self, tile, worlds):
+        """(`DwFrameSpec`, the array its list points into, (S, TH, TW)) for `tile` (an int or (tile_h, tile_w)) and
+        `worlds` (None: all B in order).  What the library refuses (a tile that does not divide the grid, a world listed
+        twice ...) is left to the library: the shape is then only a placeholder."""
+        th, tw = (int(tile), int(tile)) if np.isscalar(tile) else (int(tile[0]), int(tile[1]))
+        sel = None if worlds is None else np.ascontiguousarray(worlds, dtype=np.int32).reshape(-1)
+        if sel is not None and sel.size == 0:
+            raise ValueError("an empty selection of worlds: pass worlds=None for all of them")
+        spec = _ffi.DwFrameSpec(th, tw, 0 if sel is None else int(sel.size),
+                                None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int32)))
+        S = self.B if sel is None else int(sel.size)
+        return spec, sel, (S, max(self.H // th, 1) if th > 0 else 1, max(self.W // tw, 1) if tw > 0 else 1)
+
+    def reduce_tiles(self, L, tile=(1, 1), worlds=None, cover=True, temperature=True):
+        """One frame of the engine's state (`dw_reduce_tiles`): per tile of `tile` = (tile_h, tile_w) cells of each world in
+        `worlds` (None: all), `cover` - records of dtype `_ffi.TILE_COVER_DTYPE`, the exact per-mille sums of light and dark
+        cover of the CURRENT state - and `temperature` - the float64 mean in kelvin of the field `download_caches(L)` returns
+        as `temps[:, 0]` (after a step: what the reference's `env.temp` holds).  Returns `(cover, temp)`, arrays of shape
+        (S, H // tile_h, W // tile_w), None for what was not asked for.  At 1 x 1 tiles these are the planes and the field
+        themselves, cell for cell and bit for bit."""
+        spec, sel, shape = self._frame_spec(tile, worlds)
+        cov = np.zeros(shape, dtype=_ffi.TILE_COVER_DTYPE) if cover else None
+        tmp = np.zeros(shape, dtype=np.float64) if temperature else None
+        self._check(self._lib.dw_reduce_tiles(
+            self._h, float(L), C.byref(spec), cov.ctypes.data_as(C.POINTER(_ffi.DwTileCover)) if cover else None,
+            _ffi.ptr_d(tmp) if temperature else None))
+        return cov, tmp
+
+    def step_n_frames(self, L_schedule, stride=1, tile=(1, 1), worlds=None, cover=True, temperature=True, trace=True):
+        """`step_n_trace` with frames (`dw_step_n_frames`): `len(L_schedule)` agent-free steps, and at every `stride`-th
+        step a frame as `reduce_tiles` describes it - `cover` of the state after that step, `temperature` of the field that
+        step computes (the reference's `env.temp` after it).  Returns `(cover, temp, stats)`: (F, S, TH, TW) arrays with
+        F = n // stride (None for what was not asked for) and the (n, B) records of `step_n_trace` (None with
+        `trace=False`).  The state afterwards is that of `step_n_trace`, bit for bit."""
+        Ls = np.ascontiguousarray(L_schedule, dtype=np.float64).reshape(-1)
+        spec, sel, shape = self._frame_spec(tile, worlds)
+        stride = int(stride)
+        F = Ls.size // stride if stride >= 1 else 0
+        cov = np.zeros((F, *shape), dtype=_ffi.TILE_COVER_DTYPE) if cover else None
+        tmp = np.zeros((F, *shape), dtype=np.float64) if temperature else None
+        out = np.zeros((Ls.size, self.B), dtype=_ffi.STATS_DTYPE) if trace else None
+        self._check(self._lib.dw_step_n_frames(
+            self._h, int(Ls.size), _ffi.ptr_d(Ls), C.byref(spec), stride,
+            cov.ctypes.data_as(C.POINTER(_ffi.DwTileCover)) if cover else None, _ffi.ptr_d(tmp) if temperature else None,
+            out.ctypes.data_as(C.POINTER(DwWorldStats)) if trace else None))
+        return cov, tmp, out
+
     def policy_greedy(self, argmin=False):
         self._check(self._lib.dw_policy_greedy(self._h, _ffi.POLICY_ARGMIN if argmin else _ffi.POLICY_ARGMAX))
 

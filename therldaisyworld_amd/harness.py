@@ -294,6 +294,45 @@ def simulate_ramp(env, nsteps, obs=None, temperature=False):
     return _ramp_series(env, nsteps, eng.step_n_trace)
 
 
+def simulate_frames(env, nsteps, stride=1, tile=1, worlds=None, temperature=True, obs=None):
+    """`simulate_ramp` with pictures: the next `nsteps` steps of an agent-free ensemble in ONE device-resident run
+    (`dw_step_n_frames`) that also leaves, at every `stride`-th step, a frame of the worlds in `worlds` (None: all) - the
+    image panels of the reference's figure (daisy/notebook_helpers.py `plot_grid` / `update_fig`:
+    `tensor_to_image(env.grid[:, :3])`, `tensor_to_image(env.temp)`) reduced on the device to tiles of `tile` cells (an int
+    or (tile_h, tile_w); 1: the planes and the field themselves).  `obs=None`: reset the environment first.
+
+    Returns `simulate_ramp`'s dict for all `nsteps` steps plus: `frame_steps` (F,), `env.step_count` after each frame's
+    step (F = nsteps // stride); `frame_L` (F,), that step's luminosity; `light`, `dark` (F, S, TH, TW), the mean cover of
+    each tile - at 1 x 1 tiles `env.grid[:, 1]` and `env.grid[:, 2]` after that step; `cover`, the raw records (exact
+    per-mille sums, dtype `_ffi.TILE_COVER_DTYPE`); `worlds` (S,); and with `temperature`: `temp` (F, S, TH, TW) in kelvin,
+    the tile means of `env.temp` after that step (at 1 x 1 tiles `env.temp[:, 0]` bit for bit), and `frame_dead_temp` (F,).
+    Afterwards `env.grid`, `env.step()`, `env.L`, `env.step_count` continue as if the steps had been taken one by one.
+    With agents, take the steps with `env.step` and call `env._engine.reduce_tiles` after each."""
+    if env.n_agents:
+        raise ValueError("simulate_frames is for agent-free ensembles (n_agents == 0): with agents the reference's step(None) "
+                         "still grazes with action 0 - step with env.step and call the engine's reduce_tiles after each step")
+    if obs is None:
+        env.reset()
+    eng = env._ensure_engine()
+    env._sync_to_device()
+    n, stride = int(nsteps), int(stride)
+    L = np.asarray(_luminosity_schedule(env, n), dtype=np.float64)
+    step0 = int(env.step_count)
+    cover, temp, stats = eng.step_n_frames(L, stride=stride, tile=tile, worlds=worlds, cover=True, temperature=bool(temperature),
+                                           trace=True)
+    _advance_host_scalars(env, n)
+    out = _series_dict(env, L, stats)
+    at = np.arange(stride - 1, n - n % stride, stride)          # the frames' steps within the run
+    th, tw = (int(tile), int(tile)) if np.isscalar(tile) else (int(tile[0]), int(tile[1]))
+    cells = float(th * tw)
+    out.update(frame_steps=step0 + at + 1, frame_L=L[at],
+               light=cover["sum_light_k"] / 1000.0 / cells, dark=cover["sum_dark_k"] / 1000.0 / cells, cover=cover,
+               worlds=np.arange(int(env.batch_size)) if worlds is None else np.asarray(worlds, dtype=np.int64).reshape(-1))
+    if temperature:
+        out.update(temp=temp, frame_dead_temp=dead_temperature(env, L[at]))
+    return out
+
+
 def simulate_grazing(env, agent, nsteps, chunk=64, obs=None, temperature=False):
     """The `simulate_ramp` of an ensemble WITH agents: the time series of the daisy populations over the next `nsteps`
     steps while the agents graze - the curves of the reference's animations with an agent (daisy/notebook_helpers.py:
