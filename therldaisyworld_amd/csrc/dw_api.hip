@@ -1481,8 +1481,10 @@ int dw_step_n(dw_handle* h, int32_t nsteps, double* L_io, double dL, double min_
     // unless the ensemble is big enough to fill the GPU with wave-strips, where the packed fused kernel is
     // 1.5-1.8x faster (measured crossover between 2 M and 16 M cells: tools/kbench.py 512 64 / 4096 64).
     const bool big_packed = h->plan.allow_fuse && h->plan.packed && h->cells >= ((size_t)1 << 23);
+    // (the episode kernels stage the agents of a world with it: a handle whose agents were never uploaded takes the step
+    // kernels below, which - like dw_step without actions - do not look at them)
     if (!use_device_actions && nsteps - s0 > 1 && h->have_state && h->prm.height * h->prm.width <= 4096 && !big_packed &&
-        episode_kernel_applies(h)) {
+        (h->prm.n_agents == 0 || h->have_agents) && episode_kernel_applies(h)) {
         std::vector<double> Ls;
         while (s0 < nsteps) {
             const int k = nsteps - s0 < 4096 ? nsteps - s0 : 4096;
@@ -2143,6 +2145,9 @@ static int run_episode_mlp_impl(dw_handle* h, int32_t nsteps, const double* L_sc
         NEED(!member_b || (member_b[b] >= 0 && member_b[b] < n_members), DW_EINVAL, "world %d: member out of range", b);
     }
     NEED(n_members == 1 || (member_a && member_b), DW_EINVAL, "several parameter sets need both member maps");
+    // every step observes first: refused here, before the caller's sets replace the resident ones (a refused call leaves
+    // the handle as it was, the parameter sets a later params == NULL relies on included)
+    NEED_SHARED_L(h, "the episode's first observation");
     const size_t wbytes = sizeof(double) * 1808 * (size_t)n_members;
     EpisodeRegions regions;
     regions.rows = K; regions.mlp = true; regions.trace = records; regions.temps = temps != nullptr;
