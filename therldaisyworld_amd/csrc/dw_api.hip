@@ -933,11 +933,13 @@ static int launch_forward_fused2(dw_handle* h, double L1, double L2, unsigned in
         });
     } else if (pl.seam_strips && !pstats && !exact) {
         const FusedGeom &gs = pl.seam_geom, &gl = pl.left_geom;
-        hipLaunchKernelGGL(step_stream_fused2_seam_pw, dim3((unsigned)gs.chunk * 8u), dim3(256), 0, h->stream, inL, inD, o.L, o.D,
-                           gs, P1, P2, o.zero_me, o.zero_n);
+        const auto seam = pl.row_landing ? step_stream_fused2_land_seam_pw : step_stream_fused2_seam_pw;
+        const auto left = pl.row_landing ? step_stream_fused2_land_left_pw : step_stream_fused2_left_pw;
+        hipLaunchKernelGGL(seam, dim3((unsigned)gs.chunk * 8u), dim3(256), 0, h->stream, inL, inD, o.L, o.D, gs, P1, P2, o.zero_me,
+                           o.zero_n);
         if (gl.nstrips)
-            hipLaunchKernelGGL(step_stream_fused2_left_pw, dim3((unsigned)gl.chunk * 8u), dim3(256), 0, h->stream, inL, inD, o.L,
-                               o.D, gl, P1, P2, o.zero_me, 0);
+            hipLaunchKernelGGL(left, dim3((unsigned)gl.chunk * 8u), dim3(256), 0, h->stream, inL, inD, o.L, o.D, gl, P1, P2,
+                               o.zero_me, 0);
     } else if (pl.fmt_planes && !pstats && !exact) {
         hipLaunchKernelGGL((step_stream_fused2_fmt_pw<kFusedOvl>), grid, dim3(256), 0, h->stream, inL, inD, o.L, o.D, g, P1, P2,
                            o.zero_me, o.zero_n);
@@ -2932,6 +2934,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
                 const size_t m = std::strlen(buf);
                 snprintf(buf + m, buflen - m, ", seam strips: %d x %d columns + %d columns of %d row bands per wave", pl.seam_geom.ncs,
                          kSeamCols, pl.left_geom.cols_per_strip, pl.left_geom.wpr);
+            }
+            if (pl.row_landing) {
+                const size_t m = std::strlen(buf);
+                snprintf(buf + m, buflen - m, ", rows land in place: step_stream_fused2_land_seam_pw + _land_left_pw");
             }
             const size_t m = std::strlen(buf);
             snprintf(buf + m, buflen - m, ")");

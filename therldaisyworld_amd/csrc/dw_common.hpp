@@ -114,6 +114,34 @@ __device__ __forceinline__ float4 widen4(const float4& v) {
                        __uint_as_float((unsigned int)hi), __uint_as_float((unsigned int)(hi >> 32)));
 }
 
+// Rows that land where they stay (fused2_body, LAND): the load names the window slot's own register pairs as its
+// destination, so no move follows it.  The compiler cannot see such a load: the caller issues it only behind the last
+// read of the slot's old row (a read the compiler placed later would make it copy the old row first) and orders the
+// first read of the new row behind a counted wait (fmt_landed), through which the landed values pass as operands.
+// Accesses the compiler does not count only make ITS waits stricter: vmcnt retires in issue order.
+__device__ __forceinline__ void fmt_land2(dw_f32x2& dst, const dw_i32x4& rsrc, int voff, int soff) {
+    asm volatile("buffer_load_format_xy %0, %1, %2, %3 offen" : "+v"(dst) : "v"(voff), "s"(rsrc), "s"(soff));
+}
+template <int IMM>                                              // (no scalar offset; IMM: the instruction's byte offset)
+__device__ __forceinline__ void fmt_land2(dw_f32x2& dst, const dw_i32x4& rsrc, int voff) {
+    asm volatile("buffer_load_format_xy %0, %1, %2, 0 offen offset:%3" : "+v"(dst) : "v"(voff), "s"(rsrc), "n"(IMM));
+}
+// YOUNGER: the vector memory accesses issued behind the landing loads that may still be in flight (the row stores).
+// The landed pairs pass as 64-bit integers, as in widen4: typed as float pairs, the two middle pair sums of the row would
+// be formed as one packed add and moved apart again.
+template <int YOUNGER>
+__device__ __forceinline__ void fmt_landed(unsigned long long& a, unsigned long long& b, unsigned long long& c,
+                                           unsigned long long& d) {
+    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(YOUNGER));
+}
+__device__ __forceinline__ unsigned long long pair_bits(float lo, float hi) {
+    return (unsigned long long)__float_as_uint(lo) | ((unsigned long long)__float_as_uint(hi) << 32);
+}
+__device__ __forceinline__ float4 pairs_float4(unsigned long long lo, unsigned long long hi) {
+    return make_float4(__uint_as_float((unsigned int)lo), __uint_as_float((unsigned int)(lo >> 32)),
+                       __uint_as_float((unsigned int)hi), __uint_as_float((unsigned int)(hi >> 32)));
+}
+
 // a coordinate at most one period outside [0, n) back onto the torus (agents move by one cell, stencils reach two)
 __device__ __forceinline__ int wrap_near(int v, int n) { return v < 0 ? v + n : (v >= n ? v - n : v); }
 // ... at most TWO periods outside (a repair reaches four rows beyond a strip of a world that may be only three rows tall)
@@ -188,6 +216,44 @@ __device__ __forceinline__ void cells4(const PhysF32& P, const Row4& upL, const 
         }
 #pragma unroll
         for (int e = 0; e < N; ++e) {
+            ol[i + e] = Lanes<T>::get(vl, e);
+            od[i + e] = Lanes<T>::get(vd, e);
+        }
+    }
+}
+
+// The float32-only map of cells4 in two parts: up_sums4 forms the four sums per plane that read the UP row (the same
+// additions, in cells4's order), cells4_up the rest from them.  Between the two the up row is dead, which is where a
+// kernel that lands its next input row in that row's registers issues the load (fused2_body, LAND).
+struct UpSums4 { dw_f32x2 xl[2], cl[2], xd[2], cd[2]; };     // up.x + dn.x and up.h2 + dn.h2, light and dark
+__device__ __forceinline__ UpSums4 up_sums4(const Row4& upL, const Row4& dnL, const Row4& upD, const Row4& dnD) {
+#pragma clang fp contract(off)
+    using T = dw_f32x2;
+    UpSums4 s;
+#pragma unroll
+    for (int i = 0; i < 4; i += 2) {
+        auto pr = [&](const float* a) -> T { return Lanes<T>::load(a, i); };
+        s.xl[i / 2] = pr(upL.x) + pr(dnL.x);
+        s.cl[i / 2] = pr(upL.h2) + pr(dnL.h2);
+        s.xd[i / 2] = pr(upD.x) + pr(dnD.x);
+        s.cd[i / 2] = pr(upD.h2) + pr(dnD.h2);
+    }
+    return s;
+}
+__device__ __forceinline__ void cells4_up(const PhysF32& P, const UpSums4& s, const Row4& miL, const Row4& miD, float* ol,
+                                          float* od) {
+#pragma clang fp contract(off)
+    using T = dw_f32x2;
+#pragma unroll
+    for (int i = 0; i < 4; i += 2) {
+        auto pr = [&](const float* a) -> T { return Lanes<T>::load(a, i); };
+        const T li = pr(miL.x), di = pr(miD.x);
+        const T El = pr(miL.h2) + s.xl[i / 2];
+        const T Ed = pr(miD.h2) + s.xd[i / 2];
+        const GrowthT<T> g = growth_t<kFastSplit, T, false>(P, li, di, El, s.cl[i / 2], Ed, s.cd[i / 2]);
+        const T vl = finish_fast_t<T>(li, g.dKl, g.fl), vd = finish_fast_t<T>(di, g.dKd, g.fd);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
             ol[i + e] = Lanes<T>::get(vl, e);
             od[i + e] = Lanes<T>::get(vd, e);
         }

@@ -27,11 +27,14 @@ namespace dw {
 //                          instead of format buffer accesses (StepPlan::fmt_planes): an A/B in one process
 //   DW_NO_SEAM_STRIPS=1    the format-access step pairs keep their overlapped 248-column strips instead of seam strips with
 //                          packed leftover columns (StepPlan::seam_strips): an A/B in one process
+//   DW_NO_ROW_LANDING=1    the seam-strip step pairs keep the kernels whose prefetched rows change registers once instead of
+//                          those whose rows land in their window slots (StepPlan::row_landing): an A/B in one process
 //   DW_TEST_TRACE_ROWS=n   (test hook) dw_step_n_trace holds n rows of the series on the device at a time (rounded down to
 //                          even, at least 2) instead of 32 MiB of them: multi-chunk runs with a handful of worlds
 //   DW_TEST_FRAME_RING=n   (test hook) dw_step_n_frames holds n frames on the device at a time instead of 32 MiB of them
 struct Switches {
     bool no_sym = false, no_pack = false, no_fuse = false, no_ring = false, no_fmt_planes = false, no_seam_strips = false,
+         no_row_landing = false,
          no_episode_kernel = false,
          no_episode_wave = false, no_agent_fuse = false, no_agent_preapply = false, first_f64 = false,
          first_generic = false, force_rescan = false, test_hooks = false;
@@ -56,6 +59,7 @@ inline Switches read_switches() {
     w.test_hooks = std::getenv("DW_TEST_HOOKS") != nullptr;
     flag("DW_NO_SYM", w.no_sym); flag("DW_NO_PACK", w.no_pack); flag("DW_NO_FUSE", w.no_fuse); flag("DW_NO_RING", w.no_ring);
     flag("DW_NO_FMT_PLANES", w.no_fmt_planes); flag("DW_NO_SEAM_STRIPS", w.no_seam_strips);
+    flag("DW_NO_ROW_LANDING", w.no_row_landing);
     flag("DW_NO_EPISODE_KERNEL", w.no_episode_kernel); flag("DW_NO_EPISODE_WAVE", w.no_episode_wave);
     flag("DW_NO_AGENT_FUSE", w.no_agent_fuse); flag("DW_NO_AGENT_PREAPPLY", w.no_agent_preapply);
     flag("DW_FIRST_STEP_F64", w.first_f64); flag("DW_FIRST_GENERIC", w.first_generic);
@@ -318,6 +322,8 @@ struct StepPlan {
     bool seam_strips = false;         // ... in the seam-strip layout where that takes fewer waves (seam_layout): the launches
     FusedGeom seam_geom{}, left_geom{};   // of step_stream_fused2_seam_pw and, if columns are left over (left_geom.nstrips
                                       // != 0), of step_stream_fused2_left_pw
+    bool row_landing = false;         // ... by the kernels whose input rows land in their window slots
+                                      // (step_stream_fused2_land_seam_pw, step_stream_fused2_land_left_pw): same geometry
     bool trace_pairs = false;         // dw_step_n_trace records step pairs (trace_pair_fast / trace_pair_exact: un-packed
                                       // overlapped or rotating strips); otherwise single steps, a copy of B records each
     bool sym_albedo = false;          // a_dark - a_bare == -(a_light - a_bare) exactly: the exact wave-strip kernels use
@@ -442,6 +448,7 @@ inline StepPlan plan_steps(const dw_params& p, const Switches& sw) {
         s.fmt_planes = p.precision == DW_PRECISION_FAST && s.allow_fuse && !s.packed && s.fused_mode == kFusedOvl && !sw.no_fmt_planes &&
                        (size_t)p.height * p.width * sizeof(plane_t) < ((size_t)1 << 31);
         s.seam_strips = s.fmt_planes && !sw.no_seam_strips && seam_layout(f, &s.seam_geom, &s.left_geom);
+        s.row_landing = s.seam_strips && !sw.no_row_landing;
     } else if (quads && p.width >= 64) {
         s.kind = STEP_TILED;
         const int Wq = p.width / 4;

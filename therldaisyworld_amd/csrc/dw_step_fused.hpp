@@ -118,6 +118,9 @@ __device__ inline void exact2_cell(const TI* __restrict__ pL, const TI* __restri
 // FMT (step_stream_fused2_fmt_pw below: the plain float32 kernel on overlapped strips): the rows of the row
 // loop travel through format buffer accesses (dw_common.hpp) - loaded as float32, stored from float32, their row offset
 // in a scalar register.  The repairs' scattered patches and gathers stay plain global accesses (cold).
+// LAND (with SEAM; step_stream_fused2_land_seam_pw / _land_left_pw below): the row loop without register moves - the
+// prefetched input row lands in the window slot it will occupy (fmt_land2, dw_common.hpp: issued behind the
+// step-1 sums that read the slot's old row last, read behind a counted wait), and the bare-fraction pair stays in VGPRs.
 // SEAM (with FMT; dw_types.hpp): the two strip forms that replace the overlapped 248-column strips where they take fewer
 // waves (seam_layout, dw_plan.hpp).  Neither adds an instruction to a row map, exchanges anything between waves or
 // changes a cell's arithmetic.
@@ -134,7 +137,7 @@ __device__ inline void exact2_cell(const TI* __restrict__ pL, const TI* __restri
 //               its band's first row, clamp and wrap of the row index and byte offsets; the row WITHIN the band is
 //               wave-uniform.  Lanes of a missing band shadow the world's last one and do not write.
 template <int MODE, bool EXACT, bool PACK = false, bool STATS = false, bool SYM = false, typename TI = plane_t,
-          typename TO = plane_t, bool TRACE = false, bool FMT = false, int SEAM = kSeamNone>
+          typename TO = plane_t, bool TRACE = false, bool FMT = false, int SEAM = kSeamNone, bool LAND = false>
 __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI* __restrict__ inD,
                                             TO* __restrict__ outL, TO* __restrict__ outD, const FusedGeom& G,
                                             const PhysF32& P1_, const PhysF32& P2_, const PhysF64& P64,
@@ -146,6 +149,7 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     static_assert(!RING || !PACK, "the ring exchange is written for un-packed worlds");
     static_assert(!TRACE || (!PACK && !STATS && !RING), "the trace form exists for un-packed overlapped / rotating strips");
     static_assert(SEAM == kSeamNone || FMT, "the seam strips exist for the format-access kernel");
+    static_assert(!LAND || SEAM != kSeamNone, "rows land in their window slots in the two seam-strip forms");
     static_assert(!FMT || (MODE == kFusedOvl && !EXACT && !PACK && !STATS && !TRACE), "the format-access form exists for the plain float32 kernel on overlapped strips");
     __shared__ float s_edge[RING ? 2 * 4 * 8 : 1];               // RING: [parity][wave][.w of lane 63 x4 | .x of lane 0 x4]
     __shared__ uint4 s_queue[EXACT ? 4 * kWaveQueueCap * 3 : 1];
@@ -226,8 +230,9 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
     int fmt_col = 0, fmt_row = 0, fmt_col_b = 0;
     if constexpr (FMT) {
         const unsigned int world_bytes = (unsigned int)(G.H * G.W) * 2u;
-        fmt_inL = fmt_plane_rsrc(inL, b, world_bytes, SEAM == kSeamStrip ? kFmtRsrcPairs : kFmtRsrcQuads);
-        fmt_inD = fmt_plane_rsrc(inD, b, world_bytes, SEAM == kSeamStrip ? kFmtRsrcPairs : kFmtRsrcQuads);
+        // (LAND: the leftover waves load pairs too - a row lands in the register pairs the window keeps it in)
+        fmt_inL = fmt_plane_rsrc(inL, b, world_bytes, (SEAM == kSeamStrip || LAND) ? kFmtRsrcPairs : kFmtRsrcQuads);
+        fmt_inD = fmt_plane_rsrc(inD, b, world_bytes, (SEAM == kSeamStrip || LAND) ? kFmtRsrcPairs : kFmtRsrcQuads);
         fmt_outL = fmt_plane_rsrc(outL, b, world_bytes);
         fmt_outD = fmt_plane_rsrc(outD, b, world_bytes);
         fmt_col = col * 2;
@@ -242,6 +247,11 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
             int lr = min(rr + band_dr, r0 + band_dr + band_nr + 1);
             lr = lr < 0 ? lr + G.H : lr;
             lr = lr >= G.H ? lr - G.H : lr;
+            if constexpr (LAND) {
+                w.l = fmt_load2x2(fmt_inL, fmt_col + lr * fmt_row, fmt_col_b + lr * fmt_row, 0);
+                w.d = fmt_load2x2(fmt_inD, fmt_col + lr * fmt_row, fmt_col_b + lr * fmt_row, 0);
+                return w;
+            }
             w.l = fmt_load4(fmt_inL, fmt_col + lr * fmt_row, 0);
             w.d = fmt_load4(fmt_inD, fmt_col + lr * fmt_row, 0);
             return w;
@@ -323,6 +333,9 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
         if constexpr ((PIN & 4) != 0) { asm volatile("" : "+v"(P1.eKb)); P2.eKb = P1.eKb; }
         if constexpr ((PIN & 8) != 0) { asm volatile("" : "+v"(P1.gt)); P2.gt = P1.gt; }
     }
+    // LAND: the same for the float32 map's bare-fraction pair, which does not depend on the luminosity (6 v_mov_b64 per
+    // iteration of the row loop otherwise; the two halves are picked by op_sel)
+    if constexpr (LAND) { asm volatile("" : "+v"(P1.pck)); P2.pck = P1.pck; }
     // STATS accumulators.  Un-packed worlds (CHEAP): st_m1 = this lane's maximum of the float32 step-1 values, ties
     // included (a near-tie cell's float32 value is within one quantum of the exact one, so a maximum >= thr + 2 proves
     // the biosphere alive whatever the ties were); st_x1 = exact values that decide otherwise (maximum <= thr + 1: a
@@ -541,12 +554,48 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
             Row4* const ob[2] = {&IL[2], &ID[2]};
             rows_ring(va, oa, std::integral_constant<int, 4>{});
             rows_ring(vb, ob, std::integral_constant<int, 2>{});
+        } else if constexpr (LAND) {                            // (no slot is taken yet: wherever the compiler puts them)
+            to_rows4(p0.l, p0.d, IL[0], ID[0]);
+            to_rows4(p1.l, p1.d, IL[1], ID[1]);
+            to_rows4(p2.l, p2.d, IL[2], ID[2]);
         } else {
             to_rows4(widen4(p0.l), widen4(p0.d), IL[0], ID[0]);
             to_rows4(widen4(p1.l), widen4(p1.d), IL[1], ID[1]);
             to_rows4(widen4(p2.l), widen4(p2.d), IL[2], ID[2]);
         }
     }
+    // LAND: input row rr (load_raw's row) straight into the x registers of window slot (L, D), whose old row nothing reads
+    // any more; landed<YOUNGER>: the wait in front of the first read, then the slot's pair sums
+    auto land_row = [&](int rr, Row4& L, Row4& D) {
+        dw_f32x2 la{L.x[0], L.x[1]}, lb{L.x[2], L.x[3]}, da{D.x[0], D.x[1]}, db{D.x[2], D.x[3]};
+        if constexpr (SEAM == kSeamLeft) {
+            // load_raw's row of the lane's own band; the second pair lies 4 bytes on: the instruction's offset
+            int lr = min(rr + band_dr, r0 + band_dr + band_nr + 1);
+            lr = lr < 0 ? lr + G.H : lr;
+            lr = lr >= G.H ? lr - G.H : lr;
+            const int voff = fmt_col + lr * fmt_row;
+            fmt_land2<0>(la, fmt_inL, voff);
+            fmt_land2<4>(lb, fmt_inL, voff);
+            fmt_land2<0>(da, fmt_inD, voff);
+            fmt_land2<4>(db, fmt_inD, voff);
+        } else {
+            rr = min(rr, r0 + nr + 1);
+            rr = rr < 0 ? rr + G.H : rr;
+            rr = rr >= G.H ? rr - G.H : rr;
+            fmt_land2(la, fmt_inL, fmt_col, rr * fmt_row);
+            fmt_land2(lb, fmt_inL, fmt_col_b, rr * fmt_row);
+            fmt_land2(da, fmt_inD, fmt_col, rr * fmt_row);
+            fmt_land2(db, fmt_inD, fmt_col_b, rr * fmt_row);
+        }
+        L.x[0] = la.x; L.x[1] = la.y; L.x[2] = lb.x; L.x[3] = lb.y;
+        D.x[0] = da.x; D.x[1] = da.y; D.x[2] = db.x; D.x[3] = db.y;
+    };
+    auto landed = [&](auto YOUNGER, Row4& L, Row4& D) {
+        unsigned long long la = pair_bits(L.x[0], L.x[1]), lb = pair_bits(L.x[2], L.x[3]);
+        unsigned long long da = pair_bits(D.x[0], D.x[1]), db = pair_bits(D.x[2], D.x[3]);
+        fmt_landed<decltype(YOUNGER)::value>(la, lb, da, db);
+        to_rows4(pairs_float4(la, lb), pairs_float4(da, db), L, D);
+    };
     using U0 = std::integral_constant<int, 0>;
     using U1 = std::integral_constant<int, 1>;
     using U2 = std::integral_constant<int, 2>;
@@ -562,7 +611,18 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
         constexpr bool do1 = decltype(D1)::value, do2 = decltype(D2)::value;
         constexpr bool st_on = STATS && decltype(ST)::value;   // (the quiet copy of the loop: statistics off)
         RawIn nx;
-        if (do1) nx = load_raw(r0 + j);                        // input row j+2, needed by the NEXT iteration
+        UpSums4 up1;
+        if constexpr (LAND) {
+            // input row j+2 lands in the slot of input row j-1, the "up" row of this iteration's step-1 map: its sums
+            // first, pinned in front of the load
+            if constexpr (do1) {
+                up1 = up_sums4(IL[(u + 2) % 3], IL[(u + 1) % 3], ID[(u + 2) % 3], ID[(u + 1) % 3]);
+                asm volatile("" : "+v"(up1.xl[0]), "+v"(up1.xl[1]), "+v"(up1.cl[0]), "+v"(up1.cl[1]),
+                                  "+v"(up1.xd[0]), "+v"(up1.xd[1]), "+v"(up1.cd[0]), "+v"(up1.cd[1]));
+                __builtin_amdgcn_sched_barrier(0);
+                land_row(r0 + j, IL[(u + 2) % 3], ID[(u + 2) % 3]);
+            }
+        } else if (do1) nx = load_raw(r0 + j);                 // input row j+2, needed by the NEXT iteration
         __builtin_amdgcn_sched_barrier(0);
         float l1[4], d1[4], l2[4], d2[4];
         TieT tie1[4], tie2[4];
@@ -570,7 +630,9 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
         if (do2)
             row_cells(P2, SL[u], SL[(u + 1) % 3], SL[(u + 2) % 3], SD[u], SD[(u + 1) % 3], SD[(u + 2) % 3], l2, d2, tie2,
                       use2, st_on ? &sm2 : nullptr);
-        if (do1)
+        if constexpr (LAND) {
+            if constexpr (do1) cells4_up(P1, up1, IL[u], ID[u], l1, d1);
+        } else if (do1)
             row_cells(P1, IL[(u + 2) % 3], IL[u], IL[(u + 1) % 3], ID[(u + 2) % 3], ID[u], ID[(u + 1) % 3], l1, d1, tie1,
                       need1m, st_on ? &sm1 : nullptr);
         if (do2) {
@@ -606,6 +668,13 @@ __device__ __forceinline__ void fused2_body(const TI* __restrict__ inL, const TI
                                      widen4(nx.l), widen4(nx.d)};
                 Row4* const o[4] = {&SL[u], &SD[u], &IL[(u + 2) % 3], &ID[(u + 2) % 3]};
                 rows_ring(v, o, std::integral_constant<int, 4>{});
+            } else if constexpr (LAND) {
+                to_rows4(make_float4(l1[0], l1[1], l1[2], l1[3]), make_float4(d1[0], d1[1], d1[2], d1[3]), SL[u], SD[u]);
+                __builtin_amdgcn_sched_barrier(0);
+                // behind the landing loads this iteration issued its two row stores (kSeamStrip, do2; the leftover
+                // waves' stores are per band: they wait for everything)
+                landed(std::integral_constant<int, (SEAM == kSeamStrip && do2) ? 2 : 0>{}, IL[(u + 2) % 3], ID[(u + 2) % 3]);
+                pin_edge_sums(IL[(u + 2) % 3], ID[(u + 2) % 3]);
             } else {
                 to_rows4(make_float4(l1[0], l1[1], l1[2], l1[3]), make_float4(d1[0], d1[1], d1[2], d1[3]), SL[u], SD[u]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -943,6 +1012,25 @@ void step_stream_fused2_left_pw(const plane_t* __restrict__ inL, const plane_t* 
     const double zero = 0.0;
     fused2_body<kFusedOvl, false, false, false, false, plane_t, plane_t, false, true, kSeamLeft>(inL, inD, outL, outD, G, P1, P2, dummy,
                                                                                                 zero, zero, zero_me, zero_n);
+}
+// The same two with rows that land in their window slots (fused2_body, LAND): same geometry, same launches, same values.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DW_FUSED_FAST_WAVES, DW_FUSED_FAST_WAVES)))
+void step_stream_fused2_land_seam_pw(const plane_t* __restrict__ inL, const plane_t* __restrict__ inD,
+                                     plane_t* __restrict__ outL, plane_t* __restrict__ outD, FusedGeom G, PhysF32 P1, PhysF32 P2,
+                                     unsigned long long* __restrict__ zero_me, int zero_n) {
+    const PhysF64 dummy{};
+    const double zero = 0.0;
+    fused2_body<kFusedOvl, false, false, false, false, plane_t, plane_t, false, true, kSeamStrip, true>(inL, inD, outL, outD, G, P1, P2,
+                                                                                                       dummy, zero, zero, zero_me, zero_n);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DW_FUSED_FAST_WAVES, DW_FUSED_FAST_WAVES)))
+void step_stream_fused2_land_left_pw(const plane_t* __restrict__ inL, const plane_t* __restrict__ inD,
+                                     plane_t* __restrict__ outL, plane_t* __restrict__ outD, FusedGeom G, PhysF32 P1, PhysF32 P2,
+                                     unsigned long long* __restrict__ zero_me, int zero_n) {
+    const PhysF64 dummy{};
+    const double zero = 0.0;
+    fused2_body<kFusedOvl, false, false, false, false, plane_t, plane_t, false, true, kSeamLeft, true>(inL, inD, outL, outD, G, P1, P2,
+                                                                                                      dummy, zero, zero, zero_me, zero_n);
 }
 
 // Waves per SIMD of the exact kernels: the plain variants fit 3 waves/SIMD (151-161 VGPRs), and since the constant
