@@ -347,8 +347,7 @@ int dw_reduce_tiles(dw_handle* h, double L, const dw_frame_spec* spec,
  * evaluates no float64 field.  nsteps == 0 is a no-op.  Synchronises.
  * DW_EINVAL (before anything is launched or allocated; the state is untouched): dw_reduce_tiles' cases, a null L_schedule,
  * stride < 1, nsteps < 0; DW_ESTATE: no state; DW_ENOMEM: a buffer could not be allocated (nothing is kept).
- * Out of scope: per-world luminosities or constants, and frames inside the episode loops (dw_run_episode*) - there, call
- * dw_reduce_tiles between the calls. */
+ * Out of scope: per-world luminosities or constants.  Frames of a run with agents: dw_run_episode_frames. */
 int dw_step_n_frames(dw_handle* h, int32_t nsteps, const double* L_schedule /* [nsteps] */, const dw_frame_spec* spec,
                      int32_t stride, dw_tile_cover* cover /* [F][S][TH][TW], may be NULL */,
                      double* temp_mean /* [F][S][TH][TW], may be NULL */, dw_world_stats* trace /* [nsteps][B], may be NULL */);
@@ -708,6 +707,53 @@ int dw_run_episode_mlp_trace(dw_handle* h, int32_t nsteps, const double* L_sched
                              uint8_t* done /* [K][B][N], may be NULL */, dw_world_stats* trace /* [K][B], may be NULL */,
                              dw_temp_stats* temps /* [K][B], may be NULL */);
 
+/* dw_run_episode_trace_temperature with frames: the pictures of the reference's animation with an agent in it
+ * (daisy/notebook_helpers.py:180-258 `update_fig_agent` redraws env.grid[:, :3], env.temp and the agent channel
+ * env.grid[:, 4] after every env.step(action)) from ONE device-resident run, instead of one dw_run_episode of one step, one
+ * dw_reduce_tiles and one dw_download_agents per step.  F = nsteps / stride frames; frame f belongs to step
+ * t_f = (f + 1) * stride - 1, the rule of dw_step_n_frames; steps after the last whole stride are taken and recorded but
+ * have no frame.  `spec` is dw_step_n_frames'.
+ * Contract for the handle and the records: for the same arguments this call leaves what dw_run_episode_trace_temperature
+ * leaves (without trace and temps: what dw_run_episode leaves) - the planes, the retained previous state, the agents,
+ * dw_reduce, the device action buffer, dw_last_fixup_count, the flags, the records, the temperature rows - bit for bit, in
+ * DW_PRECISION_EXACT and DW_PRECISION_FAST, n_agents == 0 allowed.
+ * Contract for a frame: let "the state after t_f + 1 steps" be the handle after the first t_f + 1 steps of the call, taken
+ * one dw_run_episode step at a time.
+ *   cover[f]         byte for byte what dw_reduce_tiles(h, ., spec, cover, NULL) returns on that state: the tiles of
+ *                    env.grid[:, 1] and env.grid[:, 2] after the step.
+ *   temp_mean[f]     byte for byte what dw_reduce_tiles(h, ., spec, NULL, temp_mean) returns on that state: the field step
+ *                    t_f computes from the grazed state at L_schedule[t_f] (env.temp after the step), in the same fixed
+ *                    summation order per (tile_h, tile_w).  float64 in both precisions.
+ *   agents[f][s][n]  what dw_download_agents returns for world worlds[s], agent n, on that state: position and energy store
+ *                    after step t_f's update_agents (the reference writes the store into channel 4 at that position).
+ * At least one of cover, temp_mean and agents is required (records only: dw_run_episode_trace*).  Only the selected worlds
+ * produce frames.  A call with neither temps nor temp_mean evaluates no float64 field; one with temp_mean but without
+ * temps evaluates it only in frame steps of selected worlds.
+ * The forms (dw_kernel_info: "; episode frames: one wave per world" / "launches per step") are dw_run_episode_trace's.
+ * H*W <= 256 with at most 64 agents: one wave per world (episode_wave_frames_pw, csrc/dw_episode_wave_frames_pw.hpp: a wave
+ * learns from a device map whether its world is selected; in a frame step it adds the cover tiles from the new plane in
+ * LDS, sums the staged cell temperatures in dw_reduce_tiles' order and stores its agents, straight into the ring).  Every
+ * other shape, DW_NO_EPISODE_WAVE and DW_NO_EPISODE_KERNEL: launches per step, with dw_reduce_tiles' kernels around a frame
+ * step.  Both forms return the same bytes.  At most 32 MiB of frame records wait on the device (at least one frame); the
+ * wave form splits the call into launches at whole strides whose frames fit, and the ring comes down by stream-ordered
+ * copies: there is no other host synchronisation between the steps.
+ * Checked before anything is launched or allocated (the state is untouched): the rules of dw_run_episode_trace, those of
+ * dw_frame_spec (dw_reduce_tiles), and DW_EINVAL for a null handle, schedule or spec, stride < 1, all three frame outputs
+ * null, and agents with n_agents == 0.  DW_ENOMEM keeps nothing.  Synchronises.
+ * Out of scope: frames in dw_run_episode_ensemble* and dw_run_episode_mlp*, an LDS workgroup kernel with frames, per-tile
+ * extrema, pinned frame arrays. */
+typedef struct dw_agent_frame { int32_t row, col; double state; } dw_agent_frame;   /* 16 bytes */
+int dw_run_episode_frames(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
+                          const uint8_t* use_table, const int8_t* table, uint32_t threshold_k,
+                          uint8_t* world_alive      /* [K][B], may be NULL */,
+                          uint8_t* agent_ok         /* [K][B][N], may be NULL */,
+                          dw_world_stats* trace     /* [K][B], may be NULL */,
+                          dw_temp_stats* temps      /* [K][B], may be NULL */,
+                          const dw_frame_spec* spec, int32_t stride,
+                          dw_tile_cover* cover      /* [F][S][TH][TW], may be NULL */,
+                          double* temp_mean         /* [F][S][TH][TW], may be NULL */,
+                          dw_agent_frame* agents    /* [F][S][N], may be NULL */);
+
 /* ---- plumbing ------------------------------------------------------------------------------- */
 
 /* Use an existing HIP stream (e.g. torch's current stream) instead of the handle's own. */
@@ -726,7 +772,8 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark);
  * writes a NUL-terminated description into buf.  Appended fragments name the forms of the other entry points:
  * "; trace: ...", "; per-world L: ...", "; ensemble episode: ..." (dw_run_episode_ensemble), "; episode trace: ..."
  * (dw_run_episode_trace), "; episode temperature: ..." (dw_run_episode_trace_temperature), "; ensemble trace: ..."
- * (dw_run_episode_ensemble_trace), "; mlp trace: ..." (dw_run_episode_mlp_trace) and
+ * (dw_run_episode_ensemble_trace), "; mlp trace: ..." (dw_run_episode_mlp_trace), behind it "; episode frames: ..."
+ * (dw_run_episode_frames), and
  * "; episode: F; mlp episode: F" - the form dw_run_episode and
  * dw_run_episode_mlp take for the handle's shape, agent count, precision, collision mode and switches, F one of
  * "one wave per world" (H*W <= 256 and at most 64 agents, MLP: at most 4), "workgroup (LDS)" (H*W <= 4096) and

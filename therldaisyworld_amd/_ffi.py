@@ -61,6 +61,13 @@ class DwTileCover(C.Structure):
 TILE_COVER_DTYPE = np.dtype([("sum_light_k", "<u4"), ("sum_dark_k", "<u4")])
 
 
+class DwAgentFrame(C.Structure):
+    _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("state", C.c_double)]
+
+
+AGENT_FRAME_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("state", "<f8")])
+
+
 class DwFrameSpec(C.Structure):
     _fields_ = [("tile_h", C.c_int32), ("tile_w", C.c_int32), ("n_worlds", C.c_int32), ("worlds", C.POINTER(C.c_int32))]
 
@@ -144,6 +151,9 @@ SIGNATURES = {
                                        C.POINTER(DwWorldStats)]),
     "dw_run_episode_trace_temperature": (C.c_int, [_vp, _i32, _pd, C.c_int, _pu8, C.POINTER(C.c_int8), _u32, _pu8, _pu8,
                                                    C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
+    "dw_run_episode_frames": (C.c_int, [_vp, _i32, _pd, C.c_int, _pu8, C.POINTER(C.c_int8), _u32, _pu8, _pu8,
+                                        C.POINTER(DwWorldStats), C.POINTER(DwTempStats), C.POINTER(DwFrameSpec), _i32,
+                                        C.POINTER(DwTileCover), _pd, C.POINTER(DwAgentFrame)]),
     "dw_run_episode_ensemble_trace": (C.c_int, [_vp, _i32, C.POINTER(DwWorldParams), _pd, C.c_int, _pu8, C.POINTER(C.c_int8),
                                                 _u32, _pu8, _pu8, C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
     "dw_set_stream": (C.c_int, [_vp, _vp]),

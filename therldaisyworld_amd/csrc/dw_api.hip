@@ -146,6 +146,9 @@ struct dw_handle {
     DevBuf<TileCoverDev> frame_cover;
     DevBuf<double> frame_temp;
     DevBuf<double> tile_part;
+    // dw_run_episode_frames: the agents of the frames that wait for their download, [frames][S][N]; in the
+    // one-wave-per-world form frame_sel holds every world's place among the selected ones [B] instead of the selection
+    DevBuf<AgentFrameDev> frame_agents;
     // dw_step_n_trace_per_world: the constants of a chunk of steps, one entry per step and world (PwLayout), and their
     // page-locked host image
     DevBuf<unsigned char> pw_tab;
@@ -856,17 +859,20 @@ static int launch_tile_temp(dw_handle* h, bool current, double L, const FrameSha
     return DW_OK;
 }
 
-// The frames of one dw_step_n_frames call: they wait in a ring of `cap` frames on the device (32 MiB of records, at least
-// one frame) and come down when it is full and at the end of the run.
+// The frames of one dw_step_n_frames or dw_run_episode_frames call: they wait in a ring of `cap` frames on the device
+// (32 MiB of records, at least one frame) and come down when it is full and at the end of the run.
 struct FrameRun {
     dw_handle* h;
     FrameShape sh;
     int stride;
     dw_tile_cover* cover;             // the caller's arrays [F][S][TH][TW] (either may be null)
     double* temp;
+    dw_agent_frame* agents = nullptr; // dw_run_episode_frames: the caller's [F][S][N] (may be null)
     size_t total = 0, cap = 1, done = 0;
+    size_t agent_records() const { return (size_t)sh.S * (size_t)h->prm.n_agents; }   // of one frame, each of 16 bytes
     void plan(size_t nframes) {
-        const size_t bytes = sh.records() * ((cover ? sizeof(TileCoverDev) : 0) + (temp ? sizeof(double) : 0));
+        const size_t bytes = sh.records() * ((cover ? sizeof(TileCoverDev) : 0) + (temp ? sizeof(double) : 0)) +
+                             (agents ? sizeof(AgentFrameDev) * agent_records() : 0);
         total = nframes;
         cap = h->sw.frame_ring >= 1 ? (size_t)h->sw.frame_ring : ((size_t)32 << 20) / bytes;
         cap = cap < 1 ? 1 : cap;
@@ -874,20 +880,36 @@ struct FrameRun {
     }
     size_t cover_bytes() const { return cover ? sizeof(TileCoverDev) * cap * sh.records() : 0; }
     size_t temp_bytes() const { return temp ? sizeof(double) * cap * sh.records() : 0; }
+    size_t agents_bytes() const { return agents ? sizeof(AgentFrameDev) * cap * agent_records() : 0; }
+    // the first `k` frames of the ring are frames f0 .. f0 + k - 1 of the call: down to the caller's arrays, on the stream
+    int download(size_t f0, size_t k) {
+        const size_t at = f0 * sh.records(), n = k * sh.records();
+        if (cover && n) HIPCHK(hipMemcpyAsync(cover + at, h->frame_cover.get(), sizeof(TileCoverDev) * n, hipMemcpyDeviceToHost, h->stream));
+        if (temp && n) HIPCHK(hipMemcpyAsync(temp + at, h->frame_temp.get(), sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        if (agents && k)
+            HIPCHK(hipMemcpyAsync(agents + f0 * agent_records(), h->frame_agents.get(), sizeof(AgentFrameDev) * k * agent_records(),
+                                  hipMemcpyDeviceToHost, h->stream));
+        return DW_OK;
+    }
     // in front of a frame step: the field it computes, from its input planes
     int before(double L) {
         return temp ? launch_tile_temp(h, true, L, sh, h->frame_temp.get() + done % cap * sh.records()) : DW_OK;
     }
-    // behind it: the cover of the state it left; the ring goes down when it is full or the last frame is in
+    // behind it: the cover of the state it left (and the agents on it); the ring goes down when it is full or the last
+    // frame is in
     int after() {
         if (cover)
             if (int rc = launch_tile_cover(h, sh, h->cur, h->frame_cover.get() + done % cap * sh.records())) return rc;
+        if (agents) {
+            hipLaunchKernelGGL(frame_agents_pw, dim3((unsigned)((agent_records() + 255) / 256)), dim3(256), 0, h->stream, h->idx.get(),
+                               h->st.get(), sh.listed ? h->frame_sel.get() : nullptr, sh.S, h->prm.n_agents,
+                               h->frame_agents.get() + done % cap * agent_records());
+            HIPCHK(hipGetLastError());
+        }
         ++done;
         if (done % cap != 0 && done != total) return DW_OK;
-        const size_t k = (done - 1) % cap + 1, at = (done - k) * sh.records(), n = k * sh.records();
-        if (cover) HIPCHK(hipMemcpyAsync(cover + at, h->frame_cover.get(), sizeof(TileCoverDev) * n, hipMemcpyDeviceToHost, h->stream));
-        if (temp) HIPCHK(hipMemcpyAsync(temp + at, h->frame_temp.get(), sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-        return DW_OK;
+        const size_t k = (done - 1) % cap + 1;
+        return download(done - k, k);
     }
 };
 
@@ -2402,6 +2424,9 @@ static EpisodeIO episode_io(const dw_handle* h, int policy_mode, const EpisodeSt
 // launch_forward_pw) the step is that per-world single step of dw_step_n_trace_ensemble, from rows that go up as in the
 // trace calls (PwTable, the table chunks of plan_series without the test hook).  Fused step pairs only without either: the
 // step-1 sums of a pair would have to include the patch kernel's corrections, and the pair kernels take one constant set.
+// With `frames` (dw_run_episode_frames; the caller has allocated the ring and uploaded the selection): single steps as with
+// `trace`; around every stride-th step FrameRun::before - launch_tile_temp on the current planes, between update_agents
+// and the step kernel - and FrameRun::after - launch_tile_cover and frame_agents_pw behind it.
 // With `temps` (dw_run_episode_trace_temperature; the caller has allocated the reduction's partials): between a step's
 // update_agents and its step kernel, the statistics of the temperature field that step computes - temp_moments_pw on the
 // current planes at L_schedule[t], or with `worlds` (dw_run_episode_ensemble_trace) at each world's float64 row of the
@@ -2409,12 +2434,12 @@ static EpisodeIO episode_io(const dw_handle* h, int policy_mode, const EpisodeSt
 static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode,
                                 const uint8_t* use_table, const int8_t* table, uint32_t threshold_k, uint8_t* world_alive,
                                 uint8_t* agent_ok, dw_world_stats* trace, WorldRows* worlds = nullptr, bool sym = false,
-                                dw_temp_stats* temps = nullptr) {
+                                dw_temp_stats* temps = nullptr, FrameRun* frames = nullptr) {
     using R = EpisodeStaging;
     const dw_params& p = h->prm;
     const int N = p.n_agents, B = p.batch;
     const size_t K = (size_t)nsteps, Bz = (size_t)B, bn = Bz * N;
-    const bool plain = !trace && !worlds && !temps;
+    const bool plain = !trace && !worlds && !temps && !frames;
     EpisodeRegions regions;
     regions.trace = trace != nullptr || temps != nullptr; regions.temps = temps != nullptr; regions.pairs = plain; regions.slack = 256;
     EpisodeBuffers E(h, EpisodeStaging(K, Bz, (size_t)N, regions));
@@ -2506,6 +2531,9 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
         if (temps)                                              // (worlds: each world at its own float64 row of the step)
             if (int rc = tab ? launch_temp_moments(h, /*current=*/true, 0.0, tab->lay.p64(tab->dev(), q.row_of[t]), trows + t * Bz)
                              : launch_temp_moments(h, /*current=*/true, L_schedule[t], nullptr, trows + t * Bz)) return rc;
+        const bool frame = frames && (t + 1) % (size_t)frames->stride == 0;
+        if (frame)                                              // the tile means of the field this step computes
+            if (int rc = frames->before(L_schedule[t])) return rc;
         if (tab) {
             const size_t tr = q.row_of[t];
             if (int rc = launch_forward_pw(h, tab->lay.p32(tab->dev(), tr), tab->lay.p64(tab->dev(), tr), tab->lay.fb(tab->dev()), sym, true)) return rc;
@@ -2518,6 +2546,8 @@ static int run_episode_stepwise(dw_handle* h, int32_t nsteps, const double* L_sc
             hipLaunchKernelGGL(episode_stats_row_pw, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream,
                                h->stats2[h->sp].get(), B, rows + t * Bz);
         HIPCHK(hipGetLastError());
+        if (frame)                                              // the cover it left and the agents on it
+            if (int rc = frames->after()) return rc;
     }
     if (int rc = E.finish(world_alive, agent_ok, trace, temps)) return rc;
     guard.disarm();
@@ -2741,6 +2771,95 @@ int dw_run_episode_ensemble_trace(dw_handle* h, int32_t nsteps, const dw_world_p
     NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
     return run_episode_ensemble_impl(h, nsteps, worlds, L_schedule, policy_mode, use_table, table, threshold_k, world_alive,
                                      agent_ok, true, trace, temps);
+}
+
+// ---- dw_run_episode_frames: dw_run_episode_trace_temperature with frames of selected worlds ------------------------------
+// One wave per world (episode_wave_frames_pw) wherever dw_run_episode_trace takes episode_wave_stats_pw: the call is split
+// into launches at whole strides whose frames fit the ring (plan_frame_launches); the rows of every step go up once, a
+// launch reads them from its first step on, and the ring comes down behind each launch by stream-ordered copies.
+static int run_episode_frames_wave(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode, const uint8_t* use_table,
+                                   const int8_t* table, uint32_t threshold_k, uint8_t* world_alive, uint8_t* agent_ok,
+                                   dw_world_stats* trace, dw_temp_stats* temps, FrameRun& fr, const int* d_slot_of) {
+    const dw_params& p = h->prm;
+    const int C = p.height * p.width, N = p.n_agents, B = p.batch;
+    const size_t K = (size_t)nsteps;
+    const size_t lds = episode_wave_frames_lds_bytes(C, N);     // (<= 64 KB for every shape of the form: static_assert there)
+    EpisodeRegions regions;
+    regions.rows = K; regions.use_table = true; regions.trace = true; regions.temps = temps != nullptr;   // (the kernel always writes the records)
+    EpisodeBuffers E(h, EpisodeStaging(K, (size_t)B, (size_t)N, regions));
+    if (int rc = E.alloc(E.S.fits_image())) return rc;
+    PhysF32* p32 = E.p32();
+    for (size_t t = 0; t < K; ++t) p32[t] = derive_f32(p, L_schedule[t]);
+    SyncOnExit guard(h->stream);                              // E's images and the caller's arrays
+    if (int rc = E.upload(L_schedule, K, true, use_table, table)) return rc;
+    const PhysF64 P64 = make_f64(p, L_schedule[0]);
+    const dim3 grid((unsigned)((B + 3) / 4));
+    const bool ex = p.precision == DW_PRECISION_EXACT;
+    const int field = temps ? 2 : (fr.temp ? 1 : 0);
+    const TileGeom& G = fr.sh.G;
+    const EwFrameOut F{d_slot_of, fr.cover ? h->frame_cover.get() : nullptr, fr.temp ? h->frame_temp.get() : nullptr,
+                       fr.agents ? h->frame_agents.get() : nullptr, fr.sh.S, fr.stride, G.th, G.tw, G.TW, (int)fr.sh.tiles, fr.sh.map};
+    for (const FrameLaunch& l : plan_frame_launches(K, (size_t)fr.stride, fr.cap)) {
+        EpisodeIO io = episode_io(h, policy_mode, E.S, l.t0, true, use_table != nullptr, table && E.S.bn);
+        io.P32 += l.t0;                                         // (the rows of the whole call are on the device)
+        io.Ls += l.t0;
+        const EpisodeWaveFramesArgs A{io, E.dev<StatsDev>(EpisodeStaging::TRACE) + l.t0 * (size_t)B,
+                                      temps ? reinterpret_cast<TempStatsDev*>(h->ep_buf.get() + E.S.temps_off()) + l.t0 * (size_t)B : nullptr,
+                                      F, B, N, p.height, p.width, (int)l.steps, policy_mode, p.obs_mask, threshold_k, p.agent_gamma, P64};
+        with_bool(ex, [&](auto EX) {
+            with_int<0, 1, 2>(field, [&](auto FIELD) {
+                hipLaunchKernelGGL((episode_wave_frames_pw<EX, FIELD>), grid, dim3(256), lds, h->stream, A);
+            });
+        });
+        HIPCHK(hipGetLastError());
+        episode_done(h, L_schedule[l.t0 + l.steps - 1], false);
+        if (int rc = fr.download(l.f0, l.frames)) return rc;
+    }
+    release_unquantised(h);
+    if (int rc = E.finish(world_alive, agent_ok, trace, temps)) return rc;      // flags and records are returned
+    guard.disarm();
+    return DW_OK;
+}
+
+int dw_run_episode_frames(dw_handle* h, int32_t nsteps, const double* L_schedule, int policy_mode, const uint8_t* use_table,
+                          const int8_t* table, uint32_t threshold_k, uint8_t* world_alive, uint8_t* agent_ok, dw_world_stats* trace,
+                          dw_temp_stats* temps, const dw_frame_spec* spec, int32_t stride, dw_tile_cover* cover, double* temp_mean,
+                          dw_agent_frame* agents) {
+    static_assert(sizeof(dw_agent_frame) == 16 && sizeof(dw_agent_frame) == sizeof(AgentFrameDev), "agent frame record layout");
+    NEED(h && L_schedule && spec, DW_EINVAL, "null argument");
+    NEED(policy_mode >= 0 && policy_mode <= 3, DW_EINVAL, "bad policy mode");
+    NEED(stride >= 1, DW_EINVAL, "stride < 1");
+    NEED(cover || temp_mean || agents, DW_EINVAL, "none of cover, temp_mean and agents is wanted (records only: dw_run_episode_trace*)");
+    const dw_params& p = h->prm;
+    NEED(!agents || p.n_agents > 0, DW_EINVAL, "agents are wanted of a handle without agents");
+    HIPCHK(hipSetDevice(p.device));
+    if (int rc = check_episode_call(h, nsteps, policy_mode, use_table, table)) return rc;
+    FrameRun fr{h, FrameShape{}, stride, cover, temp_mean, agents};
+    if (int rc = check_frame_spec(h, spec, &fr.sh)) return rc;
+    fr.plan((size_t)(nsteps / stride));
+    const bool wave = episode_form(h) == EPISODE_WAVE;
+    // on the device: the selection [S] (a listed one) for the launches per step; for the waves every world's place in it [B]
+    const size_t B = (size_t)p.batch;
+    std::vector<int> slot_of(wave ? B : 0, -1);
+    for (size_t s = 0; wave && s < (size_t)fr.sh.S; ++s) slot_of[fr.sh.listed ? (size_t)fr.sh.worlds[s] : s] = (int)s;
+    if (int rc = alloc_group(h, "the frame buffers", {{h->frame_sel, wave ? sizeof(int) * B : fr.sh.sel_bytes()},
+                                                       {h->frame_cover, fr.cover_bytes()}, {h->frame_temp, fr.temp_bytes()},
+                                                       {h->frame_agents, fr.agents_bytes()},
+                                                       {h->tile_part, !wave && temp_mean ? fr.sh.part_bytes() : 0},
+                                                       {h->temp_part, !wave && temps ? temp_part_bytes(h) : 0}})) return rc;
+    SyncOnExit sync(h->stream);                                 // the selection comes from the caller's array, the map from slot_of
+    int rc;
+    if (wave) {
+        HIPCHK(hipMemcpyAsync(h->frame_sel.get(), slot_of.data(), sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+        rc = run_episode_frames_wave(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace,
+                                     temps, fr, h->frame_sel.get());
+    } else {
+        if ((rc = upload_selection(h, fr.sh))) return rc;
+        rc = run_episode_stepwise(h, nsteps, L_schedule, policy_mode, use_table, table, threshold_k, world_alive, agent_ok, trace,
+                                  nullptr, false, temps, &fr);
+    }
+    if (!rc) sync.disarm();                                     // (either form has synchronised)
+    return rc;
 }
 
 // ---- device-side snapshots of the current state ----------------------------------------------------
@@ -2984,6 +3103,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_run_episode_mlp_trace takes
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, "; mlp trace: %s", episode_mlp_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
+    }
+    {                                                           // the form dw_run_episode_frames takes
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; episode frames: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

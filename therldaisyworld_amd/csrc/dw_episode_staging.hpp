@@ -4,6 +4,7 @@
 // compiles it alone (tests/episode_staging_driver.cpp).
 #pragma once
 #include <cstddef>
+#include <vector>
 
 #include "dw_plan.hpp"
 
@@ -66,5 +67,26 @@ struct EpisodeStaging {
     template <class T>
     T* at(unsigned char* base, Region r) const { return reinterpret_cast<T*>(base + off[r]); }
 };
+
+// ---- the launches of an episode call with frames (dw_run_episode_frames, one wave per world) ---------------------------
+// Step t of the call leaves a frame when (t + 1) % stride == 0, and at most `ring` frames (>= 1) wait on the device: the
+// call is split into launches at whole strides, each of at most `ring` frames, the last one taking the steps behind the
+// last frame too.  A launch continues from the planes and agents the one before it wrote back and writes its flags and
+// records from row t0 of their blocks on; its frames are f0 .. f0 + frames - 1 of the call, at ring places 0 .. frames - 1.
+struct FrameLaunch { size_t t0, steps, f0, frames; };
+
+inline std::vector<FrameLaunch> plan_frame_launches(size_t K, size_t stride, size_t ring) {
+    std::vector<FrameLaunch> out;
+    const size_t F = K / stride;
+    ring = ring < 1 ? 1 : ring;
+    size_t t0 = 0, f0 = 0;
+    while (F - f0 > ring) {
+        out.push_back({t0, ring * stride, f0, ring});
+        t0 += ring * stride;
+        f0 += ring;
+    }
+    out.push_back({t0, K - t0, f0, F - f0});
+    return out;
+}
 
 }  // namespace dw

@@ -18,6 +18,7 @@
 //   dw_episode_wave_temp_pw.hpp episode_wave_temp_pw  ... and the temperature statistics of every step (dw_run_episode_trace_temperature)
 //   dw_episode_wave_ens_trace_pw.hpp episode_wave_ens_trace_pw  ... both with each world's own constants (dw_run_episode_ensemble_trace)
 //   dw_episode_mlp_wave_trace_pw.hpp episode_mlp_wave_trace_pw  episode_mlp_wave with the records of every step (dw_run_episode_mlp_trace)
+//   dw_episode_wave_frames_pw.hpp episode_wave_frames_pw  episode_wave_temp_pw with frames of selected worlds (dw_run_episode_frames)
 //   dw_agents.hpp         agents_update (ref :181-244), observe (ref get_obs :246-263), policy_greedy
 //                         (agents/greedy.py:14-36), policy_mlp (agents/mlp.py:97-116), reward/done, lifespans
 //   dw_agents_fused.hpp   agents_lookahead_patch: the agents' step between the two steps of a fused launch
@@ -50,3 +51,4 @@
 #include "dw_episode_wave_ens_trace_pw.hpp"
 #include "dw_episode_mlp_wave_trace_pw.hpp"
 #include "dw_tile_maps.hpp"
+#include "dw_episode_wave_frames_pw.hpp"

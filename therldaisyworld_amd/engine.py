@@ -506,6 +506,44 @@ class Engine:
             _ffi.ptr_u8(ok) if self.N else None, stats.ctypes.data_as(C.POINTER(DwWorldStats))))
         return stats, alive.view(np.bool_), ok.view(np.bool_)
 
+    def run_episode_frames(self, L_schedule, policy_mode, use_table=None, table=None, threshold_k=5, stride=1, tile=(1, 1),
+                           worlds=None, cover=True, temperature=True, agents=True, trace=True, temps=False):
+        """`run_episode_trace` with pictures (`dw_run_episode_frames`): the K device-resident steps of an ensemble with
+        grazing agents that also leave, at every `stride`-th step, a frame of the worlds in `worlds` (None: all) - `cover`
+        and `temperature` as `reduce_tiles` returns them after that step (tiles of `tile` cells), `agents` as
+        `download_agents` returns them after it, as records of dtype `_ffi.AGENT_FRAME_DTYPE` (`row`, `col`, `state`).
+        Returns `(cover, temp, agents, ...)` - (F, S, TH, TW), (F, S, TH, TW) and (F, S, N) arrays with F = K // stride, None
+        for what was not asked for - followed by `run_episode_trace`'s tuple `(stats, world_alive, agent_ok)` (`stats` None
+        with `trace=False`), with `temps=True` that of `run_episode_trace(..., temperature=True)`.  State, flags and records
+        are those calls', bit for bit."""
+        Ls = np.ascontiguousarray(L_schedule, dtype=np.float64)
+        K = Ls.shape[0]
+        ut = None if use_table is None else np.ascontiguousarray(use_table, dtype=np.uint8)
+        tb = None if table is None else np.ascontiguousarray(table, dtype=np.int8)
+        if ut is not None and ut.shape != (K,):
+            raise ValueError("use_table must have shape (K,)")
+        if tb is not None and tb.shape != (K, self.B, self.N):
+            raise ValueError(f"table must have shape {(K, self.B, self.N)}")
+        spec, sel, shape = self._frame_spec(tile, worlds)
+        stride = int(stride)
+        F = K // stride if stride >= 1 else 0
+        cov = np.zeros((F, *shape), dtype=_ffi.TILE_COVER_DTYPE) if cover else None
+        tmp = np.zeros((F, *shape), dtype=np.float64) if temperature else None
+        ag = np.zeros((F, shape[0], self.N), dtype=_ffi.AGENT_FRAME_DTYPE) if agents else None
+        stats = np.zeros((K, self.B), dtype=_ffi.STATS_DTYPE) if trace else None
+        trows = np.zeros((K, self.B), dtype=_ffi.TEMP_STATS_DTYPE) if temps else None
+        alive = np.empty((K, self.B), dtype=np.uint8)
+        ok = np.empty((K, self.B, self.N), dtype=np.uint8)
+        self._check(self._lib.dw_run_episode_frames(
+            self._h, K, _ffi.ptr_d(Ls), int(policy_mode), _ffi.ptr_u8(ut),
+            None if tb is None else tb.ctypes.data_as(C.POINTER(C.c_int8)), int(threshold_k), _ffi.ptr_u8(alive),
+            _ffi.ptr_u8(ok) if self.N else None, stats.ctypes.data_as(C.POINTER(DwWorldStats)) if trace else None,
+            trows.ctypes.data_as(C.POINTER(DwTempStats)) if temps else None, C.byref(spec), stride,
+            cov.ctypes.data_as(C.POINTER(_ffi.DwTileCover)) if cover else None, _ffi.ptr_d(tmp) if temperature else None,
+            ag.ctypes.data_as(C.POINTER(_ffi.DwAgentFrame)) if agents else None))
+        out = (cov, tmp, ag, stats, alive.view(np.bool_), ok.view(np.bool_))
+        return out + (trows,) if temps else out
+
     def run_episode_ensemble(self, worlds, Ls, mode, use_table=None, table=None, threshold_k=5, trace=False,
                              temperature=False):
         """`run_episode` with the physics constants `worlds[b]` (as `step_n_trace_ensemble` takes them) and the luminosity

@@ -358,6 +358,69 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None, temperature=False):
     `dw_run_episode_trace_temperature` (the first step and the host loop: `reduce_temperature` after the step).  The
     dict gains `mean_temp`, `std_temp`, `min_temp`, `max_temp` (n, B) in kelvin and `dead_temp` (n,); everything else,
     the state afterwards and the generator's final state are those of the cover-only run."""
+    return _grazing_run(env, agent, nsteps, chunk, obs, temperature)
+
+
+class _GrazingFrames:
+    """The frames of a `_grazing_run`: step t of the run leaves a frame when (t + 1) % stride == 0."""
+
+    def __init__(self, env, n, stride, tile, worlds, temperature):
+        self.stride, self.tile, self.worlds, self.temperature = int(stride), tile, worlds, bool(temperature)
+        if self.stride < 1:
+            raise ValueError("stride must be at least 1")
+        self.sel = None if worlds is None else np.asarray(worlds, dtype=np.int64).reshape(-1)
+        self.at = np.arange(self.stride - 1, n - n % self.stride, self.stride)    # the frames' steps within the run
+        self.cover, self.temp, self.agents = [], [], []
+
+    def call(self, t, K, n):
+        """(steps, stride) of the device call that starts at step t of the run: from a whole stride of the run on, `K` rounded
+        down to a multiple of the stride (at least one stride), so that a frame never straddles a call; a call that starts
+        elsewhere (behind the run's first step, which the host takes) ends at the next whole stride, with one frame there."""
+        s, off = self.stride, t % self.stride
+        if off:
+            return min(s - off, n - t), s - off
+        return min(max(K // s * s, s), n - t), s
+
+    def host(self, eng, t, L_t, N):
+        """Step t was taken by `env.step`: its frame, if it leaves one, from the on-demand calls."""
+        if (t + 1) % self.stride:
+            return
+        cov, tmp = eng.reduce_tiles(L_t, tile=self.tile, worlds=self.worlds, cover=True, temperature=self.temperature)
+        self.cover.append(cov[None])
+        if self.temperature:
+            self.temp.append(tmp[None])
+        if N:
+            idx, st = eng.download_agents()
+            pick = slice(None) if self.sel is None else self.sel
+            rec = np.zeros((1,) + st[pick].shape, dtype=_ffi.AGENT_FRAME_DTYPE)
+            rec["row"][0], rec["col"][0], rec["state"][0] = idx[pick][..., 0], idx[pick][..., 1], st[pick]
+            self.agents.append(rec)
+
+    def device(self, cov, tmp, ag):
+        self.cover.append(cov)
+        if self.temperature:
+            self.temp.append(tmp)
+        if ag is not None:
+            self.agents.append(ag)
+
+    def into(self, out, env, step0, N):
+        th, tw = (int(self.tile), int(self.tile)) if np.isscalar(self.tile) else (int(self.tile[0]), int(self.tile[1]))
+        cells = float(th * tw)
+        cover = np.concatenate(self.cover) if self.cover else np.zeros((0,), dtype=_ffi.TILE_COVER_DTYPE)
+        out.update(frame_steps=step0 + self.at + 1, frame_L=out["L"][self.at],
+                   light=cover["sum_light_k"] / 1000.0 / cells, dark=cover["sum_dark_k"] / 1000.0 / cells, cover=cover,
+                   worlds=np.arange(int(env.batch_size)) if self.sel is None else self.sel)
+        if self.temperature:
+            out.update(temp=np.concatenate(self.temp) if self.temp else np.zeros((0,)),
+                       frame_dead_temp=dead_temperature(env, out["L"][self.at]))
+        if N:
+            ag = np.concatenate(self.agents) if self.agents else np.zeros((0,), dtype=_ffi.AGENT_FRAME_DTYPE)
+            out.update(agent_pos=np.stack([ag["row"], ag["col"]], axis=-1), agent_state=ag["state"])
+
+
+def _grazing_run(env, agent, nsteps, chunk, obs, temperature, frames=None):
+    """`simulate_grazing` and, with `frames` (stride, tile, worlds, temperature), `simulate_grazing_frames`: one loop, one
+    policy handling."""
     n = int(nsteps)
     if n < 1:
         raise ValueError("nsteps must be at least 1")
@@ -367,6 +430,8 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None, temperature=False):
     if obs is None:
         obs = env.reset()
     B, N = int(env.batch_size), int(env.n_agents)
+    step0 = int(env.step_count)
+    fr = _GrazingFrames(env, n, *frames) if frames is not None else None
     L = np.zeros(n, dtype=np.float64)
     stats = np.zeros((n, B), dtype=_ffi.STATS_DTYPE)
     ok = np.zeros((n, B, N), dtype=bool)
@@ -382,6 +447,8 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None, temperature=False):
             stats[f][t] = row[f]
         if temperature:
             temps[t] = env._engine.reduce_temperature(L[t])
+        if fr is not None:
+            fr.host(env._engine, t, L[t], N)
         if N:
             ok[t] = ~np.asarray(done).reshape(B, N)
         return obs
@@ -396,7 +463,7 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None, temperature=False):
         eng = env._engine
         t = 1
         while t < n:
-            k = min(K, n - t)
+            k, stride = (min(K, n - t), 0) if fr is None else fr.call(t, K, n)
             use_table = np.zeros(k, dtype=np.uint8)
             table = np.zeros((k, B, N), dtype=np.int8)
             if agent is not None:                              # the reference's order: one coin per call, then the batch's actions
@@ -406,7 +473,15 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None, temperature=False):
                         table[i] = agent.draw_random_actions(B, N)[..., 0]
             Ls = np.asarray(_luminosity_schedule(env, k), dtype=np.float64)
             L[t:t + k] = Ls
-            if temperature:
+            if fr is not None:
+                res = eng.run_episode_frames(Ls, mode, use_table, table, LIFESPAN_THRESHOLD_K, stride=stride, tile=fr.tile,
+                                             worlds=fr.worlds, cover=True, temperature=fr.temperature, agents=N > 0, trace=True,
+                                             temps=bool(temperature))
+                fr.device(*res[:3])
+                stats[t:t + k], ok[t:t + k] = res[3], res[5]
+                if temperature:
+                    temps[t:t + k] = res[6]
+            elif temperature:
                 stats[t:t + k], _, ok[t:t + k], temps[t:t + k] = eng.run_episode_trace(Ls, mode, use_table, table,
                                                                                        LIFESPAN_THRESHOLD_K, temperature=True)
             else:
@@ -416,7 +491,32 @@ def simulate_grazing(env, agent, nsteps, chunk=64, obs=None, temperature=False):
     out = _series_dict(env, L, stats, temps)
     out["agent_ok"] = ok
     out["agents_alive"] = ok.sum(axis=2)
+    if fr is not None:
+        fr.into(out, env, step0, N)
     return out
+
+
+def simulate_grazing_frames(env, agent, nsteps, stride=1, tile=1, worlds=None, temperature=True, chunk=64, obs=None):
+    """`simulate_grazing` with pictures: the reference's animation with an agent in it (daisy/notebook_helpers.py:180-258
+    `update_fig_agent` redraws `env.grid[:, :3]`, `env.temp` and the agent channel `env.grid[:, 4]` after every
+    `env.step(action)`) without a host round trip per step.  `agent`, `chunk` and `obs` are `simulate_grazing`'s, and so is
+    the handling of the policy, an epsilon-greedy one's host-drawn table included.  Step t of the run leaves a frame of the
+    worlds in `worlds` (None: all) when (t + 1) % stride == 0: F = nsteps // stride frames, reduced to tiles of `tile` cells
+    (an int or (tile_h, tile_w); 1: the planes and the field themselves).
+
+    The first step goes through `env.step` (its frame, if it leaves one, through `reduce_tiles` and `download_agents`); the
+    others run device-resident (`dw_run_episode_frames`) in chunks of `chunk` steps rounded down to a multiple of `stride`
+    (at least `stride`), so that a frame never straddles a call; with `stride > 1` the first device call ends at the
+    run's first whole stride.
+
+    Returns `simulate_grazing`'s dict plus `frame_steps` (F,), `env.step_count` after each frame's step; `frame_L` (F,);
+    `light`, `dark` (F, S, TH, TW), the mean cover of each tile after that step; `cover`, the raw records; `worlds` (S,);
+    `temp` (F, S, TH, TW) in kelvin, the tile means of `env.temp` after that step, and `frame_dead_temp` (F,) - unless
+    `temperature=False`; and, with agents, `agent_pos` (F, S, N, 2), row and column, and `agent_state` (F, S, N), the energy
+    store the reference writes into channel 4 at that position (an agent-free environment is served without the two).  The
+    temperature CURVES of `simulate_grazing(temperature=True)` are not recorded here.  Precision "f64", `collision_mode == 1`
+    and any other callable agent: the same dict from a host loop."""
+    return _grazing_run(env, agent, nsteps, chunk, obs, False, frames=(stride, tile, worlds, temperature))
 
 
 def simulate_luminosity_sweep(env, L_values, nsteps, obs=None, temperature=False):
