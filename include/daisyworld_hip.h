@@ -107,7 +107,10 @@ typedef struct dw_params {
     int32_t precision;        /* DW_PRECISION_* */
     int32_t obs_mask;         /* 9-bit row-major 3x3 neighbourhood mask applied to observations
                                  (bit 4 = centre); von Neumann = 0x0BA, Moore = 0x1FF
-                                 (ref: nn/functional.py:51-103, daisy_world_rl.py:261) */
+                                 (ref: nn/functional.py:51-103, daisy_world_rl.py:261).  Any 9-bit value
+                                 is admitted, 0 included, and may be changed on a live handle with
+                                 dw_set_params: a greedy candidate it hides counts as 0.0, a corner it shows
+                                 reaches the MLP policies (tested in every form: tests/test_gpu_obs_masks.py) */
     int32_t collision_mode;   /* 0 or 1 (ref :44, :220-242) */
     int32_t reserved0;
     int64_t world_offset;     /* global id of world 0 of this shard; keys the device RNG so that an
