@@ -494,6 +494,36 @@ int dw_run_episode_mlp(dw_handle* h, int32_t nsteps, const double* L_schedule, c
                        int32_t n_members, const int32_t* member_a /* [B] */, const int32_t* member_b /* [B] */,
                        int32_t split, double L_init, double* reward /* [K][B][N] */, uint8_t* done /* [K][B][N] */);
 
+/* The bookkeeping of those fitness episodes on the device (additive, ABI 6): what the reference's loop keeps per step,
+ * daisy/evo/sges.py:160-176 - whether every agent is done, one more step counted in done_at and total_steps for every
+ * agent that is not, the mean reward of the first half of the agents added to the sum, and the loop left behind the step
+ * at which all are done - per member of a population evaluated as one ensemble: member block m owns worlds [m * worlds_per_member,
+ * (m + 1) * worlds_per_member), P = B / worlds_per_member blocks (worlds_per_member = B: the single pair of get_fitness).
+ * The accumulators stay on the device: sum_reward[P] float64, done_at[B][N] int32 (total_steps is the same count),
+ * running[P].  A chunk of K steps is accounted for t = 0 .. K-1 in order; where member m runs at the start of step t:
+ * done_at[b][n] += !done[t][b][n] for its worlds, sum_reward[m] += the mean of reward[t][b][0..half) over its worlds, and
+ * the member stops running if every done flag of its block is set at step t.  That mean is the reference's call on the
+ * block bit for bit: the n = worlds_per_member * half values taken world-major and agent-minor, added in NumPy's pairwise
+ * order (csrc/dw_fitness_order.hpp) and divided by n with a correctly rounded float64 division.
+ * *executed = 1 + the first t after which no member runs, with *finished = 1; otherwise *executed = K, *finished = 0 (a
+ * chunk accounted when no member runs: 1 and 1, and nothing changes).  Steps behind `executed` change nothing.
+ *   dw_fitness_begin     zeroes sums and counters, every member running
+ *   dw_fitness_account   accounts the host arrays reward / done [K][B][N] of a chunk (uploads them)
+ *   dw_run_episode_mlp_fitness   dw_run_episode_mlp with reward = done = NULL - it leaves planes, agents, actions, the
+ *                        resident parameter sets and dw_last_fixup_count exactly so - and then accounts the chunk where
+ *                        the episode kernels left its rewards and flags (every form of the call); 8 bytes come down
+ *   dw_fitness_download  the accumulators (any pointer may be NULL); synchronises
+ * DW_EINVAL: worlds_per_member does not divide B, half outside 1..N, nsteps outside 1..4096, a null handle or array;
+ * DW_ESTATE: account, run or download before dw_fitness_begin; each leaves the handle untouched.  The accumulators are
+ * not part of the snapshots: a harness that replays the executed steps of a chunk does so with dw_run_episode_mlp. */
+int dw_fitness_begin(dw_handle* h, int32_t worlds_per_member, int32_t half);
+int dw_fitness_account(dw_handle* h, int32_t nsteps, const double* reward /* [K][B][N] */, const uint8_t* done /* [K][B][N] */,
+                       int32_t* executed, int32_t* finished);
+int dw_run_episode_mlp_fitness(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params /* [n_members][1808] */,
+                               int32_t n_members, const int32_t* member_a /* [B] */, const int32_t* member_b /* [B] */,
+                               int32_t split, double L_init, int32_t* executed, int32_t* finished);
+int dw_fitness_download(dw_handle* h, double* sum_reward /* [P] */, int32_t* done_at /* [B][N] */, uint8_t* running /* [P] */);
+
 /* Device-side snapshot of the handle's state (current planes, the retained previous state that
  * observations and caches are derived from, agents, per-world reductions) and its restoration: lets an episode harness run chunks of steps ahead (dw_run_episode) and, when the episode
  * turns out to have ended inside a chunk, replay exactly the steps the reference's loop

@@ -144,6 +144,10 @@ SIGNATURES = {
     "dw_run_episode_mlp": (C.c_int, [_vp, _i32, _pd, _pd, _i32, _pi, _pi, _i32, _dbl, _pd, _pu8]),
     "dw_run_episode_mlp_trace": (C.c_int, [_vp, _i32, _pd, _pd, _i32, _pi, _pi, _i32, _dbl, _pd, _pu8,
                                            C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
+    "dw_fitness_begin": (C.c_int, [_vp, _i32, _i32]),
+    "dw_fitness_account": (C.c_int, [_vp, _i32, _pd, _pu8, _pi, _pi]),
+    "dw_run_episode_mlp_fitness": (C.c_int, [_vp, _i32, _pd, _pd, _i32, _pi, _pi, _i32, _dbl, _pi, _pi]),
+    "dw_fitness_download": (C.c_int, [_vp, _pd, _pi, _pu8]),
     "dw_run_episode": (C.c_int, [_vp, _i32, _pd, C.c_int, _pu8, C.POINTER(C.c_int8), _u32, _pu8, _pu8]),
     "dw_run_episode_ensemble": (C.c_int, [_vp, _i32, C.POINTER(DwWorldParams), _pd, C.c_int, _pu8, C.POINTER(C.c_int8), _u32,
                                           _pu8, _pu8]),

@@ -168,6 +168,18 @@ struct dw_handle {
         DevBuf<unsigned char> stats;
         bool valid = false, agents = false;
     } snap[DW_SNAPSHOT_SLOTS];
+    // dw_fitness_*: the accumulators of a population's fitness bookkeeping, carried across chunks (one group: sum_reward [P],
+    // done_at [B][N], running [P], the three words of a chunk's outcome and their page-locked image), and the scratch of
+    // the chunk in flight (a group of its own: means, all-done flags and run_t, [K][P] each).  Not part of the snapshots.
+    DevBuf<double> fit_sum;
+    DevBuf<int> fit_done_at;
+    DevBuf<unsigned char> fit_running;
+    DevBuf<int> fit_out;
+    PinnedBuf<int> fit_out_host;
+    DevBuf<double> fit_means;
+    DevBuf<unsigned char> fit_all_done;
+    DevBuf<unsigned char> fit_run_t;
+    int fit_wpm = 0, fit_half = 0;    // worlds per member and agents per world whose rewards count; 0: no dw_fitness_begin yet
     std::vector<std::pair<const void*, size_t>> lds_limit;   // set_lds_limit: kernel -> dynamic LDS limit set
     bool created = false;             // dw_create has returned it (DW_TEST_FAIL_GROUP_ALLOC counts from then on)
 };
@@ -2148,9 +2160,14 @@ int dw_policy_mlp_population(dw_handle* h, const double* params, int32_t n_membe
 // episode_mlp_wave_trace_pw<EXACT, temps given>; every other form - and the first steps of an episode - launches per step,
 // with temp_moments_pw on the grazed current state (in its own format while it is the un-quantised upload) in front of the
 // step kernel and episode_stats_row_pw behind it: no LDS workgroup kernel, the stated price of the records.
+// `account_fitness` (dw_run_episode_mlp_fitness): the fitness bookkeeping of the chunk goes on the stream behind its last
+// step, in front of the downloads and the one synchronisation - it reads the rewards and flags where the steps left them;
+// its scratch is allocated behind this call's checks, with the staging buffer.
+static int ensure_fitness_scratch(dw_handle* h, size_t K);
+static int launch_fitness_account(dw_handle* h, size_t K, const double* d_reward, const unsigned char* d_done);
 static int run_episode_mlp_impl(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params, int32_t n_members,
                                 const int32_t* member_a, const int32_t* member_b, int32_t split, double L_init, double* reward,
-                                uint8_t* done, dw_world_stats* trace, dw_temp_stats* temps) {
+                                uint8_t* done, dw_world_stats* trace, dw_temp_stats* temps, bool account_fitness = false) {
     const bool records = trace || temps;
     const dw_params& p = h->prm;
     HIPCHK(hipSetDevice(p.device));
@@ -2180,6 +2197,8 @@ static int run_episode_mlp_impl(dw_handle* h, int32_t nsteps, const double* L_sc
     const size_t o_ma = S.off[R::MEMBER_A], o_mb = S.off[R::MEMBER_B], o_p32 = S.off[R::P32], o_ls = S.off[R::LS];
     if (temps)                                                  // the partials of temp_moments_pw (the rows live in the staging buffer)
         if (int rc = alloc_group(h, "the temperature reduction", {{h->temp_part, temp_part_bytes(h)}})) return rc;
+    if (account_fitness)
+        if (int rc = ensure_fitness_scratch(h, K)) return rc;
     if (int erc = ensure_ep_buf(h, S.total)) return erc;
     if (params) {                                               // the sets stay on the device for later calls (params == NULL)
         if (h->mlp_members != n_members) {
@@ -2278,6 +2297,8 @@ static int run_episode_mlp_impl(dw_handle* h, int32_t nsteps, const double* L_sc
         }
         ++t;
     }
+    if (account_fitness)
+        if (int rc = launch_fitness_account(h, K, d_r, d_d)) return rc;
     if (reward) HIPCHK(hipMemcpyAsync(reward, d_r, sizeof(double) * K * bn, hipMemcpyDeviceToHost, h->stream));
     if (done) HIPCHK(hipMemcpyAsync(done, d_d, K * bn, hipMemcpyDeviceToHost, h->stream));
     if (trace) HIPCHK(hipMemcpyAsync(trace, d_rows, S.stats_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -2309,6 +2330,120 @@ int dw_run_episode_mlp_trace(dw_handle* h, int32_t nsteps, const double* L_sched
     static_assert(sizeof(dw_world_stats) == sizeof(StatsDev), "record layout");
     return run_episode_mlp_impl(h, nsteps, L_schedule, params, n_members, member_a, member_b, split, L_init, reward, done, trace,
                                 temps);
+}
+
+// ---- dw_fitness_*: the bookkeeping of a population's fitness episodes on the device (dw_fitness.hpp) -------------------------
+// P = B / worlds_per_member members; the accumulators stay on the device from dw_fitness_begin to dw_fitness_download, a
+// chunk brings (executed, finished) down and nothing else.
+static int fitness_members(const dw_handle* h) { return h->prm.batch / h->fit_wpm; }
+
+static int check_fitness_chunk(const dw_handle* h, int32_t nsteps) {
+    NEED(nsteps >= 1 && nsteps <= 4096, DW_EINVAL, "nsteps must be in 1..4096");
+    NEED(h->fit_wpm > 0, DW_ESTATE, "no dw_fitness_begin on this handle yet");
+    return DW_OK;
+}
+
+// the scratch of a chunk of K steps: one group, all or nothing
+static int ensure_fitness_scratch(dw_handle* h, size_t K) {
+    const size_t kp = K * (size_t)fitness_members(h);
+    return alloc_group(h, "the fitness bookkeeping of a chunk",
+                       {{h->fit_means, sizeof(double) * kp}, {h->fit_all_done, kp}, {h->fit_run_t, kp}});
+}
+
+// The three launches of a chunk whose rewards and flags are on the device, and the copy of (executed, finished) into the
+// page-locked words: the caller synchronises and reads them with fitness_outcome.
+static int launch_fitness_account(dw_handle* h, size_t K, const double* d_reward, const unsigned char* d_done) {
+    const dw_params& p = h->prm;
+    const int P = fitness_members(h);
+    const FitnessArgs A{d_reward, d_done, (int)K, p.batch, p.n_agents, h->fit_wpm, h->fit_half, P,
+                        h->fit_means.get(), h->fit_all_done.get(), h->fit_run_t.get(), h->fit_out.get(),
+                        h->fit_sum.get(), h->fit_done_at.get(), h->fit_running.get()};
+    const size_t kp = K * (size_t)P, bn = (size_t)p.batch * p.n_agents;
+    hipLaunchKernelGGL(fitness_means_pw, dim3((unsigned)((kp + kFitGroups - 1) / kFitGroups)), dim3(256), 0, h->stream, A);
+    hipLaunchKernelGGL(fitness_scan_pw, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, h->stream, A);
+    hipLaunchKernelGGL(fitness_counts_pw, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, h->stream, A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->fit_out_host.get(), h->fit_out.get() + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return DW_OK;
+}
+
+static void fitness_outcome(const dw_handle* h, int32_t* executed, int32_t* finished) {
+    if (executed) *executed = h->fit_out_host.get()[0];
+    if (finished) *finished = h->fit_out_host.get()[1];
+}
+
+int dw_fitness_begin(dw_handle* h, int32_t worlds_per_member, int32_t half) {
+    NEED(h, DW_EINVAL, "null handle");
+    const dw_params& p = h->prm;
+    HIPCHK(hipSetDevice(p.device));
+    NEED(worlds_per_member >= 1 && p.batch % worlds_per_member == 0, DW_EINVAL,
+         "worlds_per_member (%d) must divide the batch (%d)", worlds_per_member, p.batch);
+    NEED(half >= 1 && half <= p.n_agents, DW_EINVAL, "half (%d) outside 1..n_agents (%d)", half, p.n_agents);
+    const size_t P = (size_t)(p.batch / worlds_per_member), bn = (size_t)p.batch * p.n_agents;
+    NEED(bn <= (size_t)0x7fffffff, DW_EINVAL, "the fitness bookkeeping indexes B * N with 32 bits");
+    if (int rc = alloc_group(h, "the fitness accumulators", {{h->fit_sum, sizeof(double) * P}, {h->fit_done_at, sizeof(int) * bn},
+                                                              {h->fit_running, P}, {h->fit_out, 3 * sizeof(int)}})) {
+        h->fit_wpm = 0;                                         // nothing of an earlier begin is left to account into
+        return rc;
+    }
+    if (int rc = reserve(h->fit_out_host, "the page-locked fitness outcome", 2 * sizeof(int))) return rc;
+    HIPCHK(hipMemsetAsync(h->fit_sum.get(), 0, sizeof(double) * P, h->stream));
+    HIPCHK(hipMemsetAsync(h->fit_done_at.get(), 0, sizeof(int) * bn, h->stream));
+    HIPCHK(hipMemsetAsync(h->fit_running.get(), 1, P, h->stream));
+    HIPCHK(hipMemsetAsync(h->fit_out.get(), 0, 3 * sizeof(int), h->stream));
+    h->fit_wpm = worlds_per_member;
+    h->fit_half = half;
+    return DW_OK;
+}
+
+int dw_fitness_account(dw_handle* h, int32_t nsteps, const double* reward, const uint8_t* done, int32_t* executed,
+                       int32_t* finished) {
+    NEED(h && reward && done, DW_EINVAL, "null argument");
+    const dw_params& p = h->prm;
+    HIPCHK(hipSetDevice(p.device));
+    if (int rc = check_fitness_chunk(h, nsteps)) return rc;
+    const size_t K = (size_t)nsteps, bn = (size_t)p.batch * p.n_agents;
+    EpisodeRegions regions;
+    regions.mlp = true;                                         // the REWARD and DONE regions of a dw_run_episode_mlp chunk
+    const EpisodeStaging S(K, (size_t)p.batch, (size_t)p.n_agents, regions);
+    if (int rc = ensure_fitness_scratch(h, K)) return rc;
+    if (int rc = ensure_ep_buf(h, S.total)) return rc;
+    double* d_r = S.at<double>(h->ep_buf.get(), EpisodeStaging::REWARD);
+    unsigned char* d_d = S.at<unsigned char>(h->ep_buf.get(), EpisodeStaging::DONE);
+    SyncOnExit guard(h->stream);                              // reward / done are the caller's
+    HIPCHK(hipMemcpyAsync(d_r, reward, sizeof(double) * K * bn, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_d, done, K * bn, hipMemcpyHostToDevice, h->stream));
+    if (int rc = launch_fitness_account(h, K, d_r, d_d)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    guard.disarm();
+    fitness_outcome(h, executed, finished);
+    return DW_OK;
+}
+
+int dw_run_episode_mlp_fitness(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params, int32_t n_members,
+                               const int32_t* member_a, const int32_t* member_b, int32_t split, double L_init,
+                               int32_t* executed, int32_t* finished) {
+    NEED(h && L_schedule, DW_EINVAL, "null argument");
+    HIPCHK(hipSetDevice(h->prm.device));
+    if (int rc = check_fitness_chunk(h, nsteps)) return rc;
+    if (int rc = run_episode_mlp_impl(h, nsteps, L_schedule, params, n_members, member_a, member_b, split, L_init, nullptr, nullptr,
+                                      nullptr, nullptr, /*account_fitness=*/true))
+        return rc;
+    fitness_outcome(h, executed, finished);
+    return DW_OK;
+}
+
+int dw_fitness_download(dw_handle* h, double* sum_reward, int32_t* done_at, uint8_t* running) {
+    NEED(h, DW_EINVAL, "null handle");
+    const dw_params& p = h->prm;
+    HIPCHK(hipSetDevice(p.device));
+    NEED(h->fit_wpm > 0, DW_ESTATE, "no dw_fitness_begin on this handle yet");
+    const size_t P = (size_t)fitness_members(h), bn = (size_t)p.batch * p.n_agents;
+    if (sum_reward) HIPCHK(hipMemcpyAsync(sum_reward, h->fit_sum.get(), sizeof(double) * P, hipMemcpyDeviceToHost, h->stream));
+    if (done_at) HIPCHK(hipMemcpyAsync(done_at, h->fit_done_at.get(), sizeof(int) * bn, hipMemcpyDeviceToHost, h->stream));
+    if (running) HIPCHK(hipMemcpyAsync(running, h->fit_running.get(), P, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return DW_OK;
 }
 
 int dw_lifespan_reset(dw_handle* h) {

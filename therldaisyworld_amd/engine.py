@@ -36,6 +36,25 @@ def default_params(batch, height, width, n_agents) -> DwParams:
     return p
 
 
+def _mlp_episode_args(B, N, params, n_members, member_a, member_b, split):
+    """What run_episode_mlp and run_episode_mlp_fitness pass alike: (parameter sets or None, their number, the two
+    member maps as int32 or None, the split)."""
+    if params is None:
+        if n_members is None:
+            raise ValueError("params=None needs n_members (the sets uploaded by an earlier call)")
+        w, nm = None, int(n_members)
+    else:
+        w = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 1808)
+        nm = w.shape[0]
+    ma = None if member_a is None else np.ascontiguousarray(member_a, dtype=np.int32)
+    mb = None if member_b is None else np.ascontiguousarray(member_b, dtype=np.int32)
+    for m in (ma, mb):
+        if m is not None and m.shape != (B,):
+            raise ValueError(f"member maps must have shape {(B,)}")
+    split = N // 2 if split is None else int(split)
+    return w, nm, ma, mb, split
+
+
 class Engine:
     def __init__(self, params: DwParams, lib_path=None):
         self._lib = _ffi.load(lib_path)
@@ -605,19 +624,7 @@ class Engine:
         Rewards, done flags, state and agents are unchanged by either."""
         Ls = np.ascontiguousarray(L_schedule, dtype=np.float64)
         K = Ls.shape[0]
-        if params is None:
-            if n_members is None:
-                raise ValueError("params=None needs n_members (the sets uploaded by an earlier call)")
-            w, nm = None, int(n_members)
-        else:
-            w = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 1808)
-            nm = w.shape[0]
-        ma = None if member_a is None else np.ascontiguousarray(member_a, dtype=np.int32)
-        mb = None if member_b is None else np.ascontiguousarray(member_b, dtype=np.int32)
-        for m in (ma, mb):
-            if m is not None and m.shape != (self.B,):
-                raise ValueError(f"member maps must have shape {(self.B,)}")
-        split = self.N // 2 if split is None else int(split)
+        w, nm, ma, mb, split = _mlp_episode_args(self.B, self.N, params, n_members, member_a, member_b, split)
         n = K * self.B * self.N
         if reuse_buffers is not False and reuse_buffers is not None and n:
             buf = self._pinned_block(9 * n, 0 if reuse_buffers is True else int(reuse_buffers))
@@ -638,6 +645,51 @@ class Engine:
         self._check(self._lib.dw_run_episode_mlp(self._h, K, _ffi.ptr_d(Ls), _ffi.ptr_d(w), nm, _ffi.ptr_i(ma),
                                            _ffi.ptr_i(mb), split, float(L_init), _ffi.ptr_d(reward), _ffi.ptr_u8(done)))
         return reward, done.view(np.bool_)
+
+    # -- the fitness bookkeeping of an ES population on the device (ref daisy/evo/sges.py:160-176) --------------------
+    def fitness_begin(self, worlds_per_member, half):
+        """Zero the device-resident accumulators of a population's fitness episodes - `sum_reward` (P,), `done_at`
+        (B, N), `running` (P,) all True - for P = B // worlds_per_member members, member m owning worlds
+        [m * worlds_per_member, (m + 1) * worlds_per_member); `half`: the agents [0, half) of a world whose rewards count."""
+        self._check(self._lib.dw_fitness_begin(self._h, int(worlds_per_member), int(half)))
+        self._fitness_members = self.B // int(worlds_per_member)
+
+    def fitness_account(self, rewards, dones):
+        """Account a chunk of host arrays - rewards (K, B, N[, 1]) float64 (`reward * (reward > 0)`), dones the same shape,
+        bool - exactly as `harness._population_chunk` does; returns its `(executed, finished)`."""
+        r = np.ascontiguousarray(rewards, dtype=np.float64)
+        K = r.shape[0] if r.ndim else 0
+        d = np.ascontiguousarray(dones).astype(np.uint8, copy=False)
+        if r.size != K * self.B * self.N or d.size != r.size:
+            raise ValueError(f"rewards and dones must have shape {(K, self.B, self.N)} (a trailing axis of 1 is allowed)")
+        executed, finished = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.dw_fitness_account(self._h, K, _ffi.ptr_d(r), _ffi.ptr_u8(d), C.byref(executed),
+                                                 C.byref(finished)))
+        return executed.value, bool(finished.value)
+
+    def run_episode_mlp_fitness(self, L_schedule, params, member_a=None, member_b=None, split=None, L_init=0.75,
+                                n_members=None):
+        """`run_episode_mlp` whose rewards and done flags stay on the device and are accounted there
+        (`dw_run_episode_mlp_fitness`): state, agents, actions and the resident parameter sets are left as `run_episode_mlp`
+        leaves them; returns `(executed, finished)` of the chunk - the only bytes that come down."""
+        Ls = np.ascontiguousarray(L_schedule, dtype=np.float64)
+        w, nm, ma, mb, split = _mlp_episode_args(self.B, self.N, params, n_members, member_a, member_b, split)
+        executed, finished = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.dw_run_episode_mlp_fitness(self._h, Ls.shape[0], _ffi.ptr_d(Ls), _ffi.ptr_d(w), nm, _ffi.ptr_i(ma),
+                                                         _ffi.ptr_i(mb), split, float(L_init), C.byref(executed),
+                                                         C.byref(finished)))
+        return executed.value, bool(finished.value)
+
+    def fitness_download(self):
+        """`(sum_reward (P,) float64, done_at (B, N, 1) int32, running (P,) bool)` as they stand on the device."""
+        P = getattr(self, "_fitness_members", 0)
+        if not P:                                                # (the library says so itself: DW_ESTATE)
+            self._check(self._lib.dw_fitness_download(self._h, None, None, None))
+        sum_reward = np.zeros(P)
+        done_at = np.zeros((self.B, self.N, 1), dtype=np.int32)
+        running = np.zeros(P, dtype=np.uint8)
+        self._check(self._lib.dw_fitness_download(self._h, _ffi.ptr_d(sum_reward), _ffi.ptr_i(done_at), _ffi.ptr_u8(running)))
+        return sum_reward, done_at, running.view(np.bool_)
 
     def _pinned_block(self, nbytes, index=0):
         """Page-locked host buffer number `index` of at least nbytes owned by this engine (grown geometrically, freed by

@@ -833,7 +833,12 @@ def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_c
     for a population of 64 x 32 worlds - costs more than the chunk's kernel.  Chunk c + 1 does not depend on it except
     for "has the episode ended": its rewards go to the engine's second page-locked buffer, the state at its start to
     snapshot slot (c + 1) % 2, and when chunk c turns out to end the episode the speculative chunk is undone from the
-    snapshots (slot c % 2 + a replay of the executed steps, or slot (c + 1) % 2 as it is when chunk c ran to its end)."""
+    snapshots (slot c % 2 + a replay of the executed steps, or slot (c + 1) % 2 as it is when chunk c ran to its end).
+
+    `after_chunk=None`: the bookkeeping is the device's (``dw_run_episode_mlp_fitness`` between `Engine.fitness_begin` and
+    `Engine.fitness_download`, the caller's): the same loop, each chunk's call returns its `(executed, finished)` and nothing
+    else comes down.  The speculative chunk's accounting changes nothing when chunk c ended the episode - no member runs
+    any more - and the replay of the executed steps is the plain ``dw_run_episode_mlp``."""
     eng = env._engine
     n_members = np.asarray(params).reshape(-1, 1808).shape[0]
     if env.step_count >= max_steps:
@@ -845,6 +850,9 @@ def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_c
             eng.snapshot_save(c & 1)                     # and it is never undone - it always runs to its end)
         # the parameter sets go up with the first chunk and stay on the device; rewards / done flags come back in the
         # engine's page-locked buffers (consumed by after_chunk before the chunk after the next overwrites them)
+        if after_chunk is None:
+            return eng.run_episode_mlp_fitness(Ls, params if first else None, member_a, member_b, half, L_init,
+                                               n_members=n_members)
         return eng.run_episode_mlp(Ls, params if first else None, member_a, member_b, half, L_init,
                                    reuse_buffers=c & 1, n_members=n_members)
 
@@ -855,7 +863,7 @@ def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_c
         L_init = env._L_pass
         pending = pool.submit(on_device, c, Ls, L_init, True)
         while True:
-            rewards, dones = pending.result()
+            outcome = pending.result()
             ahead = None
             left = max_steps - (env.step_count + K)
             if left > 0:                                 # chunk c + 1, before chunk c is accounted for
@@ -865,7 +873,7 @@ def _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, after_c
                 ahead = pool.submit(on_device, c + 1, Ls_n, L_init_n, False)
             # (the device already returns reward * (reward > 0), ref step :490: agent states are clipped to [0, 1], so the
             # product is the state itself - a second pass over the (K,B,N,1) array would change no bit of it)
-            executed, finished = after_chunk(rewards, dones)
+            executed, finished = outcome if after_chunk is None else after_chunk(*outcome)
             if executed < K or finished:
                 if ahead is not None:
                     ahead.result()                       # the speculative chunk has to leave the device first
@@ -1010,18 +1018,44 @@ def _population_chunk(acc, rewards, dones, half, worlds_per_member):
     return executed, none_left.size > 0
 
 
-def get_fitness(env, agent, adversary, max_steps=768, chunk=64):
+def _check_bookkeeping(bookkeeping, half):
+    if bookkeeping not in ("host", "device"):
+        raise ValueError(f'bookkeeping must be "host" or "device", got {bookkeeping!r}')
+    if bookkeeping == "device" and half == 0:
+        raise ValueError('bookkeeping="device" needs at least one agent in the first half (n_agents >= 2): with a single '
+                         'agent the reference takes the mean of an empty slice - bookkeeping="host" is the route')
+    return bookkeeping == "device"
+
+
+def _device_fitness(env, params, member_a, member_b, half, worlds_per_member, max_steps, chunk):
+    """The chunk loop with the bookkeeping on the device: `(sum_reward (P,), done_at (B, N, 1) int)` after the episode."""
+    eng = env._ensure_engine()
+    eng.fitness_begin(worlds_per_member, half)
+    _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk, None)
+    sum_reward, done_at, _ = eng.fitness_download()
+    return sum_reward, done_at.astype(int)
+
+
+def get_fitness(env, agent, adversary, max_steps=768, chunk=64, bookkeeping="host"):
     """ref SimpleGaussianES.get_fitness (daisy/evo/sges.py:144-181): one episode in which the first half
     of every world's agents is driven by `agent` and the second half by `adversary` (both MLP policies);
     returns (fitness, total_steps, done_at) exactly as the reference computes them.  Observations,
     policies, grazing and physics stay on the device for `chunk` steps at a time; only the (K,B,N) rewards
-    and done flags come back, for the reference's float64 means in step order."""
+    and done flags come back, for the reference's float64 means in step order.
+
+    `bookkeeping="device"`: those means, the sums in step order and the counters are kept on the device too
+    (``dw_run_episode_mlp_fitness``: NumPy's pairwise order, the same bits); a chunk brings down 8 bytes and the episode
+    one download of the accumulators.  A single agent per world (an empty first half) has only the host route."""
+    on_device = _check_bookkeeping(bookkeeping, int(env.n_agents) // 2)   # refused before anything is reset
     agent.reset()
     obs = env.reset()
     B, N = obs.shape[0], obs.shape[1]
     half = N // 2
     params = np.stack([agent.get_parameters(), adversary.get_parameters()])
     member_a, member_b = np.zeros(B, dtype=np.int32), np.ones(B, dtype=np.int32)
+    if on_device:
+        sum_reward, done_at = _device_fitness(env, params, member_a, member_b, half, B, max_steps, chunk)
+        return sum_reward[0] / (B * N), done_at.copy(), done_at.tolist()
     acc = {"done_at": np.zeros((B, N, 1), dtype=int), "total_steps": 0, "sum_reward": 0.0}
     _mlp_chunks(env, params, member_a, member_b, half, max_steps, chunk,
                 lambda rewards, dones: _fitness_chunk(acc, rewards, dones, half))
@@ -1029,7 +1063,8 @@ def get_fitness(env, agent, adversary, max_steps=768, chunk=64):
     return fitness, acc["total_steps"], acc["done_at"].tolist()
 
 
-def get_fitness_population(env, population, adversary_of=None, worlds_per_member=32, max_steps=768, chunk=64):
+def get_fitness_population(env, population, adversary_of=None, worlds_per_member=32, max_steps=768, chunk=64,
+                           bookkeeping="host"):
     """All members of an evolution-strategy population evaluated as ONE batched ensemble (SURVEY.md §8f
     N3; the reference runs `get_fitness` once per member and farms members out to MPI workers,
     daisy/evo/sges.py:314-349).  `population` is a list of MLP policies (or a (P,1808) array);
@@ -1041,16 +1076,24 @@ def get_fitness_population(env, population, adversary_of=None, worlds_per_member
     Each member's episode ends when all ITS agents are done (or at max_steps), as in the reference; the
     ensemble keeps stepping until every member has finished, and a finished member's statistics are
     frozen at its own stopping step.  (With the legacy-RNG reset the worlds differ from P separate
-    `reset()` calls of the reference; the per-member arithmetic is the same.)"""
+    `reset()` calls of the reference; the per-member arithmetic is the same.)
+
+    `bookkeeping="device"`: as in `get_fitness` - per-member means, sums and counters on the device, the same bits."""
     params = np.stack([m.get_parameters() if hasattr(m, "get_parameters") else np.asarray(m) for m in population])
     P = params.shape[0]
     adversary_of = np.arange(P) if adversary_of is None else np.asarray(adversary_of, dtype=int)
+    on_device = _check_bookkeeping(bookkeeping, int(env.n_agents) // 2)   # refused before anything is reset
     env.batch_size = P * worlds_per_member
     obs = env.reset()
     B, N = obs.shape[0], obs.shape[1]
     half = N // 2
     member = np.repeat(np.arange(P), worlds_per_member).astype(np.int32)
     adv_member = adversary_of[member].astype(np.int32)
+    if on_device:
+        sum_reward, done_at = _device_fitness(env, params, member, adv_member, half, worlds_per_member, max_steps, chunk)
+        fitness = sum_reward / (worlds_per_member * N)
+        return [(fitness[m], done_at[m * worlds_per_member:(m + 1) * worlds_per_member].copy(),
+                 done_at[m * worlds_per_member:(m + 1) * worlds_per_member].tolist()) for m in range(P)]
     done_at = np.zeros((B, N, 1), dtype=int)
     total_steps = np.zeros((B, N, 1), dtype=int)
     sum_reward = np.zeros(P)
