@@ -740,6 +740,39 @@ int dw_run_episode_mlp_trace(dw_handle* h, int32_t nsteps, const double* L_sched
                              uint8_t* done /* [K][B][N], may be NULL */, dw_world_stats* trace /* [K][B], may be NULL */,
                              dw_temp_stats* temps /* [K][B], may be NULL */);
 
+/* dw_run_episode_mlp_trace (cover records only) with a number of agents PER WORLD: the agent-count scans of the reference's
+ * title notebook (notebooks/daisy_world_existential_risk_and_agency.ipynb, cells fd8ad489 .. 227e4895: n_agents over 1, 31,
+ * 61, .. 271 on the 16x16 world, 10 worlds per count, under the trained MLP and the scripted policies) as ONE device-resident
+ * run instead of one handle, one reset and one run per count.  In world b only agents [0, n_active[b]) exist.
+ * An absent agent is not a dead one: the reference's forward stamps the state of every agent, dead or alive, into channel 4
+ * at its cell (daisy_world_rl.py:454-459) and the MLP reads that channel, so the stamps of absent agents are not there.
+ * Contract for world b, k = n_active[b]: take a one-world handle with n_agents = k that holds world b's planes (current and
+ * retained previous state) and its first k agents, same precision and parameters, and step it K times with
+ * dw_policy_mlp_population for [0, min(split, k)) with member_a[b] and for [min(split, k), k) with member_b[b], then
+ * dw_step_device_actions, dw_get_reward_done, dw_reduce (k = 0: an agent-free handle, dw_step / dw_reduce).  This call
+ * leaves for world b exactly what that handle holds, bit for bit, in DW_PRECISION_EXACT and DW_PRECISION_FAST: the planes,
+ * the previous planes, dw_reduce, positions and states of agents < k, their entries of the action buffer, and reward /
+ * done [:, b, :k]; trace[t*B + b] is that handle's dw_reduce after step t, reserved = 0.  dw_last_fixup_count is the sum
+ * over the worlds of what those handles report.
+ * Absent agents (n >= k): the state is set to 0.0 and stays 0.0, the position is left as uploaded, reward is 0 and done is 1
+ * at every step, the action code is 0; they are neither observed nor stamped into channel 4.
+ * The counts are an argument of THIS CALL, not a property of the handle: afterwards the handle has N agents of which those
+ * have state 0, and a count-unaware call such as dw_get_obs sees them as dead agents (stamps included).
+ * The forms (dw_kernel_info: "; mlp counts: workgroup (LDS)" / "launches per step", csrc/dw_counts_plan.hpp).  H*W <= 4096
+ * where the LDS fits, once the current and the retained previous state are quantised: episode_mlp_counts_pw
+ * (csrc/dw_episode_mlp_counts_pw.hpp), worlds in LDS with ~20 bytes per agent and 16 KiB of static LDS per workgroup for the
+ * observation / activation blocks of its sixteen 16-lane groups.  Every other shape, the first steps of an episode and
+ * DW_NO_EPISODE_KERNEL: launches per step (observe_counts_pw, policy_mlp, grazing, the step kernel, the record row).  Both
+ * forms leave the same bytes.
+ * Checked before anything is launched, allocated or uploaded (state and resident parameter sets untouched): the rules of
+ * dw_run_episode_mlp; DW_EINVAL for a null n_active, for a count outside 0..N (the message names the world), for
+ * collision_mode 1 and DW_PRECISION_F64.  All counts 0 is an agent-free run.  Synchronises. */
+int dw_run_episode_mlp_counts(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params /* [n_members][1808] or NULL */,
+                              int32_t n_members, const int32_t* member_a /* [B] */, const int32_t* member_b /* [B] */,
+                              int32_t split, const int32_t* n_active /* [B], each in 0..N */, double L_init,
+                              double* reward /* [K][B][N], may be NULL */, uint8_t* done /* [K][B][N], may be NULL */,
+                              dw_world_stats* trace /* [K][B], may be NULL */);
+
 /* dw_run_episode_trace_temperature with frames: the pictures of the reference's animation with an agent in it
  * (daisy/notebook_helpers.py:180-258 `update_fig_agent` redraws env.grid[:, :3], env.temp and the agent channel
  * env.grid[:, 4] after every env.step(action)) from ONE device-resident run, instead of one dw_run_episode of one step, one
@@ -806,7 +839,7 @@ int dw_device_planes(dw_handle* h, int which, void** light, void** dark);
  * "; trace: ...", "; per-world L: ...", "; ensemble episode: ..." (dw_run_episode_ensemble), "; episode trace: ..."
  * (dw_run_episode_trace), "; episode temperature: ..." (dw_run_episode_trace_temperature), "; ensemble trace: ..."
  * (dw_run_episode_ensemble_trace), "; mlp trace: ..." (dw_run_episode_mlp_trace), behind it "; episode frames: ..."
- * (dw_run_episode_frames), and
+ * (dw_run_episode_frames), "; mlp counts: workgroup (LDS)" / "launches per step" (dw_run_episode_mlp_counts), and
  * "; episode: F; mlp episode: F" - the form dw_run_episode and
  * dw_run_episode_mlp take for the handle's shape, agent count, precision, collision mode and switches, F one of
  * "one wave per world" (H*W <= 256 and at most 64 agents, MLP: at most 4), "workgroup (LDS)" (H*W <= 4096) and

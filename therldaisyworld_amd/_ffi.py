@@ -144,6 +144,8 @@ SIGNATURES = {
     "dw_run_episode_mlp": (C.c_int, [_vp, _i32, _pd, _pd, _i32, _pi, _pi, _i32, _dbl, _pd, _pu8]),
     "dw_run_episode_mlp_trace": (C.c_int, [_vp, _i32, _pd, _pd, _i32, _pi, _pi, _i32, _dbl, _pd, _pu8,
                                            C.POINTER(DwWorldStats), C.POINTER(DwTempStats)]),
+    "dw_run_episode_mlp_counts": (C.c_int, [_vp, _i32, _pd, _pd, _i32, _pi, _pi, _i32, _pi, _dbl, _pd, _pu8,
+                                            C.POINTER(DwWorldStats)]),
     "dw_fitness_begin": (C.c_int, [_vp, _i32, _i32]),
     "dw_fitness_account": (C.c_int, [_vp, _i32, _pd, _pu8, _pi, _pi]),
     "dw_run_episode_mlp_fitness": (C.c_int, [_vp, _i32, _pd, _pd, _i32, _pi, _pi, _i32, _dbl, _pi, _pi]),

@@ -126,6 +126,7 @@ struct dw_handle {
     DevBuf<unsigned char> ep_buf;     // device staging of dw_run_episode (schedules, tables, flags)
     DevBuf<double> mlp_w;             // parameter sets of the last dw_run_episode_mlp call that passed them
     int mlp_members = 0;
+    DevBuf<int> n_active_d;           // [B] dw_run_episode_mlp_counts: the agents each world has in the call in flight
     PinnedBuf<unsigned char> ep_pinned;   // page-locked host image of ep_buf (LDS-resident episode kernels: ONE upload
                                           // and ONE download per chunk instead of six pageable copies)
     DevBuf<double> reward_d;          // [B][N]
@@ -326,6 +327,12 @@ static bool episode_kernel_applies(const dw_handle* h);
 enum EpisodeForm { EPISODE_STEPWISE, EPISODE_WORKGROUP, EPISODE_WAVE };   // launches per step | episode_small / episode_mlp | one wave per world
 static EpisodeForm episode_form(const dw_handle* h);
 static EpisodeForm episode_mlp_form(const dw_handle* h, size_t* lds_bytes = nullptr);
+// dw_run_episode_mlp_counts (dw_counts_plan.hpp): the workgroup kernel, or launches per step
+static bool episode_mlp_counts_workgroup(const dw_handle* h) {
+    const dw_params& p = h->prm;
+    return dw::episode_mlp_counts_workgroup(p.height * p.width, p.n_agents, p.precision == DW_PRECISION_F64, p.collision_mode,
+                                            h->sw.no_episode_kernel);
+}
 // worlds a workgroup of the LDS-resident episode kernels holds (dw_episode.hpp: 256 / wpb threads per world)
 static int worlds_per_block(int cells) { return cells <= 256 ? 4 : (cells <= 1024 ? 2 : 1); }
 static int observe_into_scratch(dw_handle* h, double L_init, size_t extra_bytes, bool reward_tail = false);
@@ -2332,6 +2339,134 @@ int dw_run_episode_mlp_trace(dw_handle* h, int32_t nsteps, const double* L_sched
                                 temps);
 }
 
+// ---- dw_run_episode_mlp_counts: dw_run_episode_mlp_trace (cover records) with a number of agents per world ----------------
+// run_episode_mlp_impl's chain with the counts: the states of absent agents are zeroed once; then, once the current and the
+// retained previous state are quantised, the rest of the chunk in ONE launch of episode_mlp_counts_pw (where
+// dw_counts_plan.hpp says so); until then and everywhere else per step observe_counts_pw -> policy_mlp (zero rows: action
+// 0) -> grazing (a state-0 agent is inert) -> the step kernel -> episode_stats_row_pw.  Both forms leave the same bytes.
+int dw_run_episode_mlp_counts(dw_handle* h, int32_t nsteps, const double* L_schedule, const double* params, int32_t n_members,
+                              const int32_t* member_a, const int32_t* member_b, int32_t split, const int32_t* n_active,
+                              double L_init, double* reward, uint8_t* done, dw_world_stats* trace) {
+    NEED(n_active, DW_EINVAL, "n_active is null");
+    NEED(h && L_schedule, DW_EINVAL, "null argument");
+    const dw_params& p = h->prm;
+    HIPCHK(hipSetDevice(p.device));
+    NEED(nsteps >= 1 && nsteps <= 4096, DW_EINVAL, "nsteps must be in 1..4096");
+    NEED(n_members >= 1, DW_EINVAL, "n_members < 1");
+    NEED(params || (h->mlp_w.get() && h->mlp_members == n_members), DW_ESTATE,
+         "params == NULL but no parameter sets of %d members are on the device", n_members);
+    NEED(p.collision_mode == 0, DW_EINVAL, "collision_mode=1 is not implemented on the device");
+    NEED(p.precision != DW_PRECISION_F64, DW_EINVAL, "dw_run_episode_mlp_counts takes DW_PRECISION_EXACT and DW_PRECISION_FAST");
+    NEED(split >= 0 && split <= p.n_agents, DW_EINVAL, "split outside 0..n_agents");
+    NEED(h->have_state && h->have_agents, DW_ESTATE, "no state / agents");
+    const int B = p.batch, N = p.n_agents;
+    const size_t K = (size_t)nsteps, bn = (size_t)B * N;
+    NEED(bn > 0, DW_EINVAL, "no agents");
+    for (int b = 0; b < B; ++b) {
+        NEED(!member_a || (member_a[b] >= 0 && member_a[b] < n_members), DW_EINVAL, "world %d: member out of range", b);
+        NEED(!member_b || (member_b[b] >= 0 && member_b[b] < n_members), DW_EINVAL, "world %d: member out of range", b);
+        NEED(n_active[b] >= 0 && n_active[b] <= N, DW_EINVAL, "world %d: %d agents, outside 0..%d", b, n_active[b], N);
+    }
+    NEED(n_members == 1 || (member_a && member_b), DW_EINVAL, "several parameter sets need both member maps");
+    NEED_SHARED_L(h, "the episode's first observation");
+    const size_t wbytes = sizeof(double) * 1808 * (size_t)n_members;
+    EpisodeRegions regions;
+    regions.rows = K; regions.mlp = true; regions.trace = trace != nullptr;
+    const EpisodeStaging S(K, (size_t)B, (size_t)N, regions);
+    using R = EpisodeStaging;
+    const size_t o_ma = S.off[R::MEMBER_A], o_mb = S.off[R::MEMBER_B], o_p32 = S.off[R::P32], o_ls = S.off[R::LS];
+    if (int rc = alloc_group(h, "the agent counts", {{h->n_active_d, sizeof(int) * (size_t)B}})) return rc;
+    if (int rc = ensure_scratch(h, sizeof(double) * bn * 63)) return rc;
+    if (int rc = ensure_ep_buf(h, S.total)) return rc;
+    if (params && h->mlp_members != n_members) {                // the sets stay on the device for later calls (params == NULL)
+        h->mlp_w.reset();
+        h->mlp_members = 0;
+        if (int rc = reserve(h->mlp_w, "the parameter sets", wbytes)) return rc;
+        h->mlp_members = n_members;
+    }
+    const double* d_w = h->mlp_w.get();
+    const int* d_na = h->n_active_d.get();
+    const int* d_ma = member_a ? reinterpret_cast<const int*>(h->ep_buf.get() + o_ma) : nullptr;
+    const int* d_mb = member_b ? reinterpret_cast<const int*>(h->ep_buf.get() + o_mb) : nullptr;
+    double* d_r = S.at<double>(h->ep_buf.get(), R::REWARD);
+    unsigned char* d_d = S.at<unsigned char>(h->ep_buf.get(), R::DONE);
+    StatsDev* const d_rows = S.at<StatsDev>(h->ep_buf.get(), R::TRACE);
+    SyncOnExit guard(h->stream);                              // params / member maps / counts are the caller's
+    if (params) HIPCHK(hipMemcpyAsync(h->mlp_w.get(), params, wbytes, hipMemcpyHostToDevice, h->stream));
+    if (member_a) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ma, member_a, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    if (member_b) HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_mb, member_b, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->n_active_d.get(), n_active, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(zero_absent_states_pw, dim3((unsigned)((bn + 255) / 256)), dim3(256), 0, h->stream, h->st.get(), d_na, B, N);
+    HIPCHK(hipGetLastError());
+    const int Cc = p.height * p.width;
+    const int wpb = counts_worlds_per_block(Cc);
+    const bool small = episode_mlp_counts_workgroup(h);
+    const size_t lds = episode_mlp_counts_dynamic_lds(Cc, N);
+    std::vector<PhysF32> p32;
+    SyncOnExit guard2(h->stream);                             // p32 (filled below) must outlive its upload
+    size_t t = 0;
+    while (t < K) {
+        if (small && cur_quantised(h) && h->stepped && h->unq == OWN_NONE) {
+            const size_t Kr = K - t;
+            p32.resize(Kr);
+            for (size_t i = 0; i < Kr; ++i) p32[i] = derive_f32(p, L_schedule[t + i]);
+            HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_p32, p32.data(), sizeof(PhysF32) * Kr, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->ep_buf.get() + o_ls, L_schedule + t, sizeof(double) * Kr, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemsetAsync(h->stats2[h->sp].get(), 0, sizeof(StatsDev) * (B + 1), h->stream));
+            EpisodeMlpCountsArgs A;
+            fill_episode_io(A.io, h, S);
+            A.io.weights = d_w; A.io.member_a = d_ma; A.io.member_b = d_mb;
+            A.io.reward = d_r + t * bn; A.io.done = d_d + t * bn;
+            A.io.action = h->action.get();
+            A.n_active = d_na;
+            A.trace = trace ? d_rows + t * B : nullptr;
+            A.B = B; A.N = N; A.H = p.height; A.W = p.width; A.wpb = wpb; A.K = (int)Kr; A.obs_mask = p.obs_mask; A.split = (int)split;
+            A.agent_gamma = p.agent_gamma; A.L_prev0 = h->L_last; A.P64 = make_f64(p, L_schedule[t]);
+            auto kern = p.precision == DW_PRECISION_EXACT ? episode_mlp_counts_pw<true> : episode_mlp_counts_pw<false>;
+            if (int rc = set_lds_limit(h, kern, lds)) return rc;
+            hipLaunchKernelGGL(kern, dim3((unsigned)((B + wpb - 1) / wpb)), dim3(kCountsThreads), lds, h->stream, A);
+            HIPCHK(hipGetLastError());
+            h->stepped = true;
+            h->L_last = L_schedule[K - 1];
+            h->L_per_world = false;
+            t = K;
+            break;
+        }
+        {                                                       // observe_into_scratch with the counts
+            NEED_SHARED_L(h, "an observation");
+            const dim3 g((unsigned)((bn * 9 + 127) / 128));
+            const PhysF64 P = make_f64(p, h->stepped ? h->L_last : L_init);
+            const plane_t* cL = h->L16[h->cur].get();          // read by the POST variants only
+            const plane_t* cD = h->D16[h->cur].get();
+            with_derived_from(h, [&](auto* pL, auto* pD, auto POST) {
+                hipLaunchKernelGGL((observe_counts_pw<elem_t<decltype(pL)>, POST>), g, dim3(128), 0, h->stream, pL, pD, cL, cD,
+                                   h->idx.get(), h->st.get(), d_na, B, N, p.height, p.width, P, p.obs_mask, h->scratch.get());
+            });
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(policy_mlp, dim3((unsigned)((bn + 3) / 4)), dim3(64), 0, h->stream, h->scratch.get(), d_w, d_ma, B, N,
+                           0, N, h->action.get(), d_mb, split);
+        HIPCHK(hipGetLastError());
+        int rc = launch_agents(h, h->action.get(), B, N, false, d_r + t * bn, d_d + t * bn);
+        if (rc) return rc;
+        rc = launch_forward(h, L_schedule[t]);
+        if (rc) return rc;
+        if (trace) {
+            hipLaunchKernelGGL(episode_stats_row_pw, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream,
+                               h->stats2[h->sp].get(), B, d_rows + t * B);
+            HIPCHK(hipGetLastError());
+        }
+        ++t;
+    }
+    if (reward) HIPCHK(hipMemcpyAsync(reward, d_r, sizeof(double) * K * bn, hipMemcpyDeviceToHost, h->stream));
+    if (done) HIPCHK(hipMemcpyAsync(done, d_d, K * bn, hipMemcpyDeviceToHost, h->stream));
+    if (trace) HIPCHK(hipMemcpyAsync(trace, d_rows, S.stats_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    guard2.disarm();
+    guard.disarm();
+    return DW_OK;
+}
+
 // ---- dw_fitness_*: the bookkeeping of a population's fitness episodes on the device (dw_fitness.hpp) -------------------------
 // P = B / worlds_per_member members; the accumulators stay on the device from dw_fitness_begin to dw_fitness_download, a
 // chunk brings (executed, finished) down and nothing else.
@@ -3242,6 +3377,10 @@ int dw_kernel_info(dw_handle* h, char* buf, size_t buflen) {
     {                                                           // the form dw_run_episode_frames takes
         const size_t n = std::strlen(buf);
         snprintf(buf + n, buflen - n, "; episode frames: %s", episode_form(h) == EPISODE_WAVE ? "one wave per world" : "launches per step");
+    }
+    {                                                           // the form dw_run_episode_mlp_counts takes
+        const size_t n = std::strlen(buf);
+        snprintf(buf + n, buflen - n, "; mlp counts: %s", episode_mlp_counts_workgroup(h) ? "workgroup (LDS)" : "launches per step");
     }
     if (pl.first_stream) {                                      // the first step's wave-strips have a height of their own
         const size_t n = std::strlen(buf);

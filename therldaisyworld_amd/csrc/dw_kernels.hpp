@@ -26,6 +26,8 @@
 //   dw_temp_moments.hpp   temp_moments_pw   per-world mean / std / min / max of the local temperature (ref :410,415)
 //   dw_tile_maps.hpp      tile_cover_pw, tile_temp_pw   per-tile cover sums and temperature means of selected worlds (frames)
 //   dw_fitness.hpp        fitness_means_pw, fitness_scan_pw, fitness_counts_pw   the ES fitness bookkeeping of a chunk (sges.py:160-176)
+//   dw_counts_plan.hpp    host and device: the form and the LDS bytes of dw_run_episode_mlp_counts (no HIP)
+//   dw_episode_mlp_counts_pw.hpp episode_mlp_counts_pw, observe_counts_pw   MLP episodes with a number of agents per world
 //
 // Wavefront = 64 lanes, 256-thread workgroups (4 waves), no MFMA.  Planes are binary16 per-mille integers: 8
 // algorithmic bytes per cell-update (2 planes read + 2 written).  Measured bounds (DESIGN.md sections 3 and 6): the
@@ -54,3 +56,4 @@
 #include "dw_tile_maps.hpp"
 #include "dw_episode_wave_frames_pw.hpp"
 #include "dw_fitness.hpp"
+#include "dw_episode_mlp_counts_pw.hpp"

@@ -646,6 +646,29 @@ class Engine:
                                            _ffi.ptr_i(mb), split, float(L_init), _ffi.ptr_d(reward), _ffi.ptr_u8(done)))
         return reward, done.view(np.bool_)
 
+    def run_episode_mlp_counts(self, L_schedule, params, n_active, member_a=None, member_b=None, split=None, L_init=0.75,
+                               n_members=None, trace=True):
+        """`run_episode_mlp(..., trace=True)` with a number of agents per world (`dw_run_episode_mlp_counts`): in world b
+        only agents [0, n_active[b]) exist - the others are neither observed nor stamped into channel 4, their state is set
+        to 0, their reward is 0, their done flag True and their action 0.  Returns (reward (K,B,N,1) float64, done (K,B,N,1)
+        bool, stats (K,B) of dtype `_ffi.STATS_DTYPE` or None without `trace`).  For world b the call leaves what an engine
+        of one world with n_active[b] agents holds after the same steps, bit for bit.  The counts belong to this call, not
+        to the engine: afterwards the absent agents are N - n_active[b] agents of state 0."""
+        Ls = np.ascontiguousarray(L_schedule, dtype=np.float64)
+        K = Ls.shape[0]
+        w, nm, ma, mb, split = _mlp_episode_args(self.B, self.N, params, n_members, member_a, member_b, split)
+        na = None if n_active is None else np.ascontiguousarray(n_active, dtype=np.int32)
+        if na is not None and na.shape != (self.B,):
+            raise ValueError(f"n_active must have shape {(self.B,)}")
+        reward = np.empty((K, self.B, self.N, 1))
+        done = np.empty((K, self.B, self.N, 1), dtype=np.uint8)
+        stats = np.zeros((K, self.B), dtype=_ffi.STATS_DTYPE) if trace else None
+        self._check(self._lib.dw_run_episode_mlp_counts(
+            self._h, K, _ffi.ptr_d(Ls), _ffi.ptr_d(w), nm, _ffi.ptr_i(ma), _ffi.ptr_i(mb), split, _ffi.ptr_i(na),
+            float(L_init), _ffi.ptr_d(reward), _ffi.ptr_u8(done),
+            None if stats is None else stats.ctypes.data_as(C.POINTER(DwWorldStats))))
+        return reward, done.view(np.bool_), stats
+
     # -- the fitness bookkeeping of an ES population on the device (ref daisy/evo/sges.py:160-176) --------------------
     def fitness_begin(self, worlds_per_member, half):
         """Zero the device-resident accumulators of a population's fitness episodes - `sum_reward` (P,), `done_at`

@@ -675,6 +675,9 @@ def simulate_lifespan_sweep(env, scenarios, worlds_per_scenario, chunk=32, obs=N
     `env.batch_size == len(scenarios) * worlds_per_scenario`.  Every world follows the environment's own luminosity
     ramp; `agent_gamma`, the observation mask and the initial-state fields are the environment's and shared.
     `obs=None`: reset the environment first; or pass the observations of a reset already done (`reset_synthetic`).
+    A scenario may carry `"n_agents": k` with 0 <= k <= env.n_agents: its worlds have the first k agents only - the states
+    of the others are uploaded as 0 before step 1, which is exact for `Greedy` and None (they read channels 1 and 2 only,
+    and an agent of state 0 never moves, grazes or revives); their `agents_done_at` entries are 0.
 
     The first step starts from the un-quantised state: the policies' actions from the reset observations (block by
     block), `dw_update_agents`, one step of `dw_step_n_trace_ensemble`, `dw_get_reward_done`.  Then chunks of `chunk`
@@ -695,12 +698,20 @@ def simulate_lifespan_sweep(env, scenarios, worlds_per_scenario, chunk=32, obs=N
     for s, sc in enumerate(scenarios):
         if sc.get("agent") is not None and type(sc["agent"]) is not Greedy:
             raise ValueError(f"scenario {s}: the agent must be a Greedy or None")
+        if "n_agents" in sc and not 0 <= int(sc["n_agents"]) <= int(env.n_agents):
+            raise ValueError(f"scenario {s}: n_agents ({sc['n_agents']}) outside 0..env.n_agents ({int(env.n_agents)})")
     if env.precision == "f64" or env.collision_mode != 0:
         raise ValueError("simulate_lifespan_sweep runs device-resident: precision 'exact' or 'fast', collision_mode 0")
     table = _sweep_param_table(env, scenarios, Bs)
     if obs is None:
         obs = env.reset()
     B, N = S * Bs, int(env.n_agents)
+    if N and any("n_agents" in sc for sc in scenarios):
+        states = np.array(env.agent_states, dtype=np.float64)
+        for s, sc in enumerate(scenarios):
+            if "n_agents" in sc:
+                states[s * Bs:(s + 1) * Bs, int(sc["n_agents"]):] = 0.0
+        env.agent_states = states                               # uploaded by _sync_to_device below, before step 1
     done_at = np.zeros((S, Bs), dtype=int)
     agents_done_at = np.zeros((S, Bs, N, 1), dtype=int)
     running = np.ones(S, dtype=bool)
@@ -727,6 +738,69 @@ def simulate_lifespan_sweep(env, scenarios, worlds_per_scenario, chunk=32, obs=N
         _sweep_account(done_at, agents_done_at, running, alive_k, ok_k)
         _advance_host_scalars(env, K)
     return done_at, agents_done_at, table
+
+
+def simulate_agent_count_sweep(env, agent, counts, worlds_per_count, chunk=64, max_steps=None, obs=None):
+    """The reference's agent-count scan (notebooks/daisy_world_existential_risk_and_agency.ipynb, cells fd8ad489 ..
+    227e4895: how long the biosphere lives with n_agents = 1, 31, .. 271 grazers on the 16x16 world, 10 worlds per count,
+    under the trained MLP, the greedy and the anti-greedy policy) as ONE device-resident run instead of one environment,
+    one `reset()` and one run per count.
+
+    Block s owns the worlds [s * Bs, (s + 1) * Bs), Bs = `worlds_per_count`, and has the first `counts[s]` of the
+    environment's agents; `env.batch_size == len(counts) * Bs` and `env.n_agents >= max(counts)`, else ValueError before
+    anything is reset.  `agent` is an `MLP`, a `Greedy` with `epsilon == 0`, or None (ref step(None): action 0).
+
+    An `MLP` runs in chunks of `chunk` steps of `dw_run_episode_mlp_counts` with every agent on the one parameter set: the
+    absent agents are neither observed nor stamped into channel 4 of the grid the MLP reads, so a block is bit for bit an
+    environment of `counts[s]` agents.  A `Greedy` or None is delegated to `simulate_lifespan_sweep` with `"n_agents"`
+    scenarios (`max_steps` must then be None: that run has no step limit).  The notebook's rule holds per block
+    (`_sweep_account`): a block's counts stop at the step at which all of its worlds have maximum cover <= 0.005; the run
+    ends at the end of the chunk in which the last block ended, or after `max_steps` steps.
+
+    Returns `(done_at (S, Bs), agents_done_at (S, Bs, N, 1), n_active (S * Bs,))`; entries of absent agents are 0.  As after
+    `simulate_lifespan_sweep` the environment is of no further use until `reset()`."""
+    from .agents.mlp import MLP
+    counts = [int(c) for c in counts]
+    S, Bs, N = len(counts), int(worlds_per_count), int(env.n_agents)
+    if S < 1 or Bs < 1 or int(env.batch_size) != S * Bs:
+        raise ValueError(f"env.batch_size ({int(env.batch_size)}) must be len(counts) * worlds_per_count ({S} * {Bs})")
+    if min(counts) < 0 or max(counts) > N:
+        raise ValueError(f"counts must lie in 0..env.n_agents ({N}), got {counts}")
+    scripted = agent is None or (type(agent) is Greedy and agent.epsilon == 0)
+    if not scripted and not isinstance(agent, MLP):
+        raise ValueError("the agent must be an MLP, a Greedy with epsilon == 0, or None")
+    n_active = np.repeat(np.asarray(counts, dtype=np.int32), Bs)
+    if scripted:
+        if max_steps is not None:
+            raise ValueError("max_steps applies to an MLP: the scripted policies run until every block has ended")
+        scenarios = [{"agent": agent, "n_agents": c} for c in counts]
+        done_at, agents_done_at, _ = simulate_lifespan_sweep(env, scenarios, Bs, chunk=chunk, obs=obs)
+        return done_at, agents_done_at, n_active
+    K = int(chunk)
+    if K < 1 or (max_steps is not None and int(max_steps) < 1):
+        raise ValueError("chunk and max_steps must be at least 1")
+    if N < 1:
+        raise ValueError("an MLP needs env.n_agents >= 1")
+    if env.precision == "f64" or env.collision_mode != 0:
+        raise ValueError("simulate_agent_count_sweep runs device-resident: precision 'exact' or 'fast', collision_mode 0")
+    if obs is None:
+        env.reset()
+    params = np.asarray(agent.get_parameters(), dtype=np.float64).reshape(1, 1808)
+    done_at = np.zeros((S, Bs), dtype=int)
+    agents_done_at = np.zeros((S, Bs, N, 1), dtype=int)
+    running = np.ones(S, dtype=bool)
+    eng = env._ensure_engine()
+    env._sync_to_device()
+    steps = 0
+    while running.any() and (max_steps is None or steps < int(max_steps)):
+        k = K if max_steps is None else min(K, int(max_steps) - steps)
+        Ls = np.asarray(_luminosity_schedule(env, k), dtype=np.float64)
+        _, done, stats = eng.run_episode_mlp_counts(Ls, params if steps == 0 else None, n_active, split=N, L_init=env._L_pass,
+                                                    n_members=1)
+        _sweep_account(done_at, agents_done_at, running, stats["max_k"] > LIFESPAN_THRESHOLD_K, ~done[..., 0])
+        _advance_host_scalars(env, k)
+        steps += k
+    return done_at, agents_done_at, n_active
 
 
 def simulate_grazing_sweep(env, scenarios, worlds_per_scenario, nsteps, chunk=64, obs=None, temperature=False):
